@@ -1,11 +1,23 @@
 #!/usr/bin/env python
 """bench.py -- disparity-volumes/s of the MGM hot path on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg3] [--batch B] [--mode pairs|directions] [--extras auto|on|off]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR] [--workload cfg3] [--batch B]
+                    [--mode pairs|directions] [--extras auto|on|off]
 
 One "step" = one full pass of the hot path over one batch of synthetic stereo pairs whose images are
 already resident in HBM: census transform + W*H*L cost volume (K1, K2), all-direction MGM
 aggregation (K3), ordered sum + over-count fix + WTA + V-fit (K4-K6).  Outputs stay on the device.
+
+A plain run (no --full) does only what the headline needs: set up, warm up, time EXACTLY K steps, write the last step's
+outputs (--dump-outputs), print the line.  `--full` adds everything else the bench measures or checks: the parity gate and
+the CPU baselines below, further timed blocks (`repeat_values`) and, on the plain command line, the extra legs.
+
+--dump-outputs DIR: after the timed steps, the refined disparity and cost maps the LAST timed step computed (what a caller of
+the path receives) go to DIR/disparity.npy and DIR/cost.npy (float32, pairs x rows x columns); where all of them would exceed
+DUMP_MAX_BYTES, the same seeded sample of pixels of every pair (DIR/pixel_index.npy: their row-major indices, float64).  The
+files hold finite numbers only: the NaN of a pixel without a disparity (and any infinity) is 0 there, and
+DIR/<map>_nonfinite.npy says which (dump_outputs).  The inputs are seeded: the same arguments give the same inputs on every
+run, so two builds can be compared output for output.
 
 N > 1: one process per GPU.  `python bench.py --gpus N` started WITHOUT a torch.distributed.run environment
 launches itself under it (N ranks on 127.0.0.1); started by `python -m torch.distributed.run ... bench.py --gpus N`
@@ -13,7 +25,7 @@ it is one of the ranks.  The HEADLINE (`value`) is always the `pairs` mode on th
 processes its own independent pairs -- the reference has no cross-pair coupling, so there is no data-path collective
 -- and the job rate is all volumes of all ranks over the slowest rank's time (weak scaling).
 
-With the driver's plain command line (no --workload / --batch / --mode) two more legs run after the headline and
+With `--full` and the driver's plain command line (no --workload / --batch / --mode) two more legs run after the headline and
 land in the SAME json line (`--extras`):
     "cfg5_replicas"   BASELINE config 5: 16 independent 1024x1024x128 pairs per step and GPU, replicas only
     "directions"      BASELINE config 4: ONE 4096x4096x192 volume, its 8 passes sharded over the N GPUs with the ordered
@@ -32,7 +44,7 @@ Workload matrix (BASELINE.json configs; cfg1 is the reference's CPU-runnable cas
     --workload cfg5   1024x1024x128, census 3x3, -O 4, TSGM 2, 16 pairs per step and GPU (throughput mode)
 
 Rank 0 prints ONE JSON line, the last thing on stdout; fields `roofline`, `cpu_baseline` and `parity` are described
-in DESIGN.md.  PARITY GATE: the disparity and cost maps of ONE pair of the batch -- its index drawn from the step count --
+in DESIGN.md.  PARITY GATE (--full): the disparity and cost maps of ONE pair of the batch -- its index drawn from the step count --
 computed by the LAST timed step are compared, bit for bit, with the CPU oracle run on the same seeded pair in the same
 process (and with the reference's own maps where oracle/_ref travelled); a mismatch fails the run (exit code 3).
 torch is used for the process group, the barrier and the max-reduction only.
@@ -129,6 +141,8 @@ TEST_CONTEXT_FACTORY = None
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
 HBM_ACHIEVABLE_GBS = 6300.0  # what a float4 copy kernel reaches on this part (MI355X_MICROARCH.md: 6.29 TB/s): the practical ceiling
 PARITY_MAX_CELLS = 1.2e9  # the in-run oracle takes whole volumes up to this size (cfg4: see tests/test_gpu_fullsize.py)
+DUMP_MAX_BYTES = 48 << 20  # what --dump-outputs writes at most, all files together
+DUMP_SEED = 20250611  # the pixels --dump-outputs keeps when the maps are larger than that
 
 
 def labels_of(w):
@@ -400,6 +414,45 @@ def nd(a, b):
     """Differing float32 words of two arrays, NaN == NaN."""
     a, b = np.ascontiguousarray(a, np.float32), np.ascontiguousarray(b, np.float32)
     return int(np.sum((a.view(np.uint32) != b.view(np.uint32)) & ~(np.isnan(a) & np.isnan(b))))
+
+
+NONFINITE_CODES = {"nan": 1.0, "+inf": 2.0, "-inf": 3.0}  # how --dump-outputs writes what is not a finite number (0: finite)
+
+
+def finite_split(a):
+    """A float array as two finite ones: its values with every NaN / +-inf set to 0, and the code of each element
+    (NONFINITE_CODES; 0 = the value is the element).  Lossless but for NaN payloads."""
+    code = np.zeros(a.shape, np.float32)
+    code[np.isnan(a)] = NONFINITE_CODES["nan"]
+    code[np.isposinf(a)] = NONFINITE_CODES["+inf"]
+    code[np.isneginf(a)] = NONFINITE_CODES["-inf"]
+    return np.where(code == 0, a, 0).astype(a.dtype), code
+
+
+def dump_outputs(d, outs, outcs, nx, ny):
+    """--dump-outputs DIR: the refined disparity and cost maps of every pair of the last timed step (float32), whole where
+    they fit in DUMP_MAX_BYTES, else the same DUMP_SEED-drawn pixels of every pair.  A pixel without a disparity holds NaN
+    in both maps (as in the reference): every file holds finite numbers only, so each map is written as its finite values
+    (<map>.npy, 0 where the map is not finite) and the code of every pixel (<map>_nonfinite.npy, NONFINITE_CODES).  Returns
+    what was written."""
+    os.makedirs(d, exist_ok=True)
+    B, npix = len(outs), nx * ny
+    maps = {"disparity": np.stack([np.asarray(h.download(), np.float32).reshape(npix) for h in outs]),
+            "cost": np.stack([np.asarray(h.download(), np.float32).reshape(npix) for h in outcs])}
+    idx = None
+    if 2 * sum(a.nbytes for a in maps.values()) > DUMP_MAX_BYTES:
+        n = min(npix, DUMP_MAX_BYTES // (4 * 4 * B + 8))
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(npix, n, replace=False))
+    arrays = {}
+    for name, a in maps.items():
+        a = a.reshape(B, ny, nx) if idx is None else a[:, idx]
+        arrays[name], arrays[name + "_nonfinite"] = finite_split(a)
+    if idx is not None:
+        arrays["pixel_index"] = idx.astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), np.ascontiguousarray(a))
+    return {"dir": d, "sampled": idx is not None, "arrays": {k: list(a.shape) for k, a in arrays.items()},
+            "nonfinite_codes": NONFINITE_CODES, "bytes": int(sum(a.nbytes for a in arrays.values()))}
 
 
 # ---- launcher -----------------------------------------------------------------------------------------------------------
@@ -1073,11 +1126,17 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default=None, choices=sorted(WORKLOADS))
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: the parity gate, the CPU baselines, further timed blocks "
+                         "(`repeat_values`) and, on the plain command line, the extra legs; a plain run only times the K steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the disparity and cost maps of the last timed step to DIR/*.npy (float32, finite values plus a "
+                         "code of the non-finite ones; a fixed seeded sample of pixels beyond %d MB)" % (DUMP_MAX_BYTES >> 20))
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-parity", action="store_true", help="skip the in-run parity gate (profiling runs)")
     ap.add_argument("--repeats", type=int, default=None,
                     help="further timed blocks of K steps after the reported one (their rates go to `repeat_values`); "
-                         "default: as many as make the GPU phase last about 10 s, at most 8")
+                         "default: none, and with --full as many as make the GPU phase last about 10 s, at most 8")
     ap.add_argument("--batch", type=int, default=None, choices=list(range(1, 17)),
                     help="pairs per step and GPU: their volumes share ONE launch of the pass kernel.  Default: "
                          "12 (204 GB of Lr volumes at 1920x1080x256 x 8 directions), 16 for workloads of at most 128 labels "
@@ -1090,12 +1149,19 @@ def main():
                          "leg: ONE volume per step, its passes sharded over the GPUs with the ordered slab exchange (strong); "
                          "'pairs2' = one stereo pair per step and pair of GPUs, its two mgm() runs on one GPU each (strong)")
     ap.add_argument("--extras", default="auto", choices=["auto", "on", "off"],
-                    help="the cfg5-replicas and cfg4-directions legs after the headline; auto = on for the plain command line")
+                    help="the variants, cfg5-replicas and cfg4-directions legs after the headline; auto = on for the plain "
+                         "command line with --full")
     ap.add_argument("--extras-timeout", type=float, default=420.0, help="seconds the guarded extras may take altogether (round 6: the gated variants run CPU legs too)")
     ap.add_argument("--exchange-timeout", type=float, default=90.0, help="seconds one direction-sharded step may take")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs is not None and args.mode != "pairs":
+        ap.error("--dump-outputs writes what the pairs mode computes (--mode pairs)")
     plain = args.workload is None and args.batch is None and args.mode == "pairs" and args.pipeline == 1
-    extras = args.extras == "on" or (args.extras == "auto" and plain)
+    extras = args.extras == "on" or (args.extras == "auto" and plain and args.full)
+    if args.repeats is None and not args.full:
+        args.repeats = 0  # (pairs_leg: None = the --full default, about 10 s of further blocks)
     wname = args.workload or ("cfg4" if args.mode in ("directions", "pairs2") else "cfg3")
     w = WORKLOADS[wname]
     stub = TEST_CONTEXT_FACTORY is not None  # (tests/run_bench_stub.py: gloo ranks on CPU, a context that computes nothing)
@@ -1181,14 +1247,16 @@ def main():
             "repeat_values": [vols_per_block / t for t in m["rep_dt"]],
             "parity": None,
             "mcell_updates_per_s": vols_per_block * cells * w["NDIR"] / dt / 1e6}
+        if args.dump_outputs is not None:  # what the last timed step handed its caller, before anything else touches the device
+            res["outputs"] = dump_outputs(args.dump_outputs, m["outs"], m["outcs"], nx, ny)
 
-    # ---- parity gate: pair 0 of the last timed step against the CPU oracle; CPU baseline --------------------------------
+    # ---- parity gate (--full): pair 0 of the last timed step against the CPU oracle; CPU baseline ------------------------
     parity, whole_s, T = None, None, 1
     gate = (args.steps + args.warmup) % B  # which pair of the batch is gated: not always the first
-    if rank == 0 and not stub:
+    if rank == 0 and not stub and (args.full or extras):
         from oracle.oracle import usable_cpus
         T = min(32, usable_cpus())
-        if not args.no_parity:
+        if args.full and not args.no_parity:
             if cells > PARITY_MAX_CELLS:
                 parity = {"status": "skipped", "why": "%.1f G cells: beyond the in-run oracle (covered by tests/test_gpu_fullsize.py)" % (cells / 1e9)}
             else:
@@ -1201,7 +1269,7 @@ def main():
                 if bad:
                     line.code = 3
             res["parity"] = parity
-        if n_ranks == 1 and not args.no_cpu_baseline and cells <= PARITY_MAX_CELLS:
+        if args.full and n_ranks == 1 and not args.no_cpu_baseline and cells <= PARITY_MAX_CELLS:
             res["cpu_baseline"], ref_out = cpu_baseline(w, whole_s, T, pair=gate)
             if ref_out and parity is not None and parity.get("status") != "skipped":  # the reference's own maps, while we have them
                 got_o, got_c = m["outs"][gate].download()[0], m["outcs"][gate].download()[0]

@@ -5,6 +5,8 @@ and bench.py labels the line `"data": "stub (no device work)"`."""
 import os
 import time
 
+import numpy as np
+
 
 class _Handle:
     def __init__(self, shape=None):
@@ -15,6 +17,9 @@ class _Handle:
 
     def update(self, a):
         pass
+
+    def download(self):
+        return np.zeros(self.shape, np.float32)
 
 
 class StubContext:

@@ -191,10 +191,10 @@ def _run_bench(args, extra_env=None, timeout=600):
 
 
 def test_driver_command_line_runs_the_extra_legs():
-    """`python bench.py --gpus 2 --steps K --warmup W` and nothing else -- the driver's command: after the cfg3 headline the
+    """`python bench.py --gpus 2 --steps K --warmup W --full` and nothing else: after the cfg3 headline the
     SAME json line carries the cfg5 replicas and the direction-sharded leg (here: agreement + ordered slab exchange over
     gloo on the stub's host tensors), and it is still ONE line."""
-    r, d, lines = _run_bench(["--gpus", "2", "--steps", "3", "--warmup", "1", "--repeats", "0"])
+    r, d, lines = _run_bench(["--gpus", "2", "--steps", "3", "--warmup", "1", "--repeats", "0", "--full"])
     assert r.returncode == 0, r.stderr[-2000:]
     assert len(lines) == 1
     assert d["n_gpus"] == 2 and d["scaling"] == "weak" and d["config"]["workload"].startswith("cfg3")
@@ -217,7 +217,7 @@ def test_driver_command_line_runs_the_extra_legs():
 def test_extras_watchdog_prints_the_headline_when_a_leg_hangs():
     """A leg that never returns (the stub sleeps in the cfg5 leg when told to) must not take the headline with it: the
     watchdog prints the one line with what had been measured and ends every rank."""
-    r, d, lines = _run_bench(["--gpus", "2", "--steps", "2", "--warmup", "1", "--repeats", "0", "--extras-timeout", "6"],
+    r, d, lines = _run_bench(["--gpus", "2", "--steps", "2", "--warmup", "1", "--repeats", "0", "--extras-timeout", "6", "--full"],
                              {"MGM_STUB_HANG_AT": "cfg5"}, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
     assert len(lines) == 1 and d["value"] > 0 and d["config"]["workload"].startswith("cfg3")
@@ -225,7 +225,7 @@ def test_extras_watchdog_prints_the_headline_when_a_leg_hangs():
 
 
 def test_single_rank_default_line_has_both_legs():
-    r, d, lines = _run_bench(["--steps", "2", "--warmup", "1", "--repeats", "0"])
+    r, d, lines = _run_bench(["--steps", "2", "--warmup", "1", "--repeats", "0", "--full"])
     assert r.returncode == 0, r.stderr[-2000:]
     assert len(lines) == 1 and d["n_gpus"] == 1
     assert d["cfg5_replicas"]["n_gpus"] == 1 and d["directions"]["ranks"] == 1 and d["directions"]["transport"] == "single"
@@ -237,6 +237,38 @@ def test_single_rank_default_line_has_both_legs():
     assert "frac_range_proportional" in v["cfg3r x1"]
     r = d["roofline"]
     assert 0 < r["moved_over_algorithmic"] <= 1.0 and r["frac_of_achievable"] > 0 and isinstance(r["saturated"], bool)
+
+
+def test_plain_line_is_lean_and_dumps_the_last_step(tmp_path):
+    """`bench.py --steps K --warmup W` without --full: the headline alone (exactly K timed steps, no further blocks, no gate, no
+    CPU legs, no extra legs); --dump-outputs writes the last step's maps as float32 .npy files, a fixed sample where they are
+    large, within 64 MB, the same pixels on every run."""
+    import numpy as np
+    r, d, lines = _run_bench(["--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path / "a")])
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert len(lines) == 1 and d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["higher_is_better"] is True
+    assert d["metric"].startswith("disparity-volumes/sec") and d["unit"] == "disparity-volumes/s" and d["dtype"] == "f32"
+    assert abs(d["value"] - 3 * 12 / (d["ms_per_step"] * 3e-3)) < 1e-6 * d["value"]
+    assert d["kernel_ms_per_step"]["k_pass2"] == 12.0  # (the stub times 1 ms per volume and launch: 3 launches of 12 over 3 steps)
+    assert d["repeat_values"] == [] and d["parity"] is None
+    assert not {"cfg5_replicas", "directions", "variants", "cpu_baseline"} & set(d)
+    o = d["outputs"]
+    assert o["sampled"] and o["bytes"] <= 64 << 20
+    files = {f: np.load(tmp_path / "a" / (f + ".npy")) for f in ("disparity", "cost", "disparity_nonfinite", "cost_nonfinite", "pixel_index")}
+    n = files["pixel_index"].shape[0]
+    assert files["disparity"].shape == files["cost"].shape == files["cost_nonfinite"].shape == (12, n)
+    assert files["disparity"].dtype == files["cost_nonfinite"].dtype == np.float32
+    assert all(a.flags.c_contiguous and np.isfinite(a).all() for a in files.values())
+    assert files["pixel_index"].dtype == np.float64 and 0 <= files["pixel_index"].min() and files["pixel_index"].max() < 1920 * 1080
+    assert sum(a.nbytes for a in files.values()) == o["bytes"]
+    r, d, lines = _run_bench(["--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path / "b")])
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert np.array_equal(np.load(tmp_path / "b" / "pixel_index.npy"), files["pixel_index"])
+    # maps that fit are written whole
+    r, d, lines = _run_bench(["--workload", "cfg5", "--batch", "2", "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path / "c")])
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert not d["outputs"]["sampled"] and not (tmp_path / "c" / "pixel_index.npy").exists()
+    assert np.load(tmp_path / "c" / "disparity.npy").shape == np.load(tmp_path / "c" / "cost.npy").shape == (2, 1024, 1024)
 
 
 def test_exchange_rounds_and_timeout():
@@ -304,9 +336,9 @@ def test_pairs2_mode_and_the_sharding_model():
 
 
 def test_driver_command_line_on_four_ranks():
-    """The driver's SCALE command at N = 4 (stub ranks over gloo): one valid line, the direction-sharded leg ran on all four
+    """The driver's SCALE command at N = 4 with --full (stub ranks over gloo): one valid line, the direction-sharded leg ran on all four
     ranks (two rounds of the exchange), the pair split ran, and the line says what scales."""
-    r, d, lines = _run_bench(["--gpus", "4", "--steps", "2", "--warmup", "1", "--repeats", "0"], timeout=900)
+    r, d, lines = _run_bench(["--gpus", "4", "--steps", "2", "--warmup", "1", "--repeats", "0", "--full"], timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     assert len(lines) == 1 and d["n_gpus"] == 4 and d["scaling"] == "weak"
     dr = d["directions"]
@@ -320,12 +352,12 @@ def test_transport_fallbacks_keep_the_line_valid():
     """rccl fails -> the peer path's figure is the leg's; rccl AND peer fail -> "replicas": no figure, the chain says why, the
     headline and every other key of the line are still there (the first node run must not lose its line to a
     transport error)."""
-    r, d, lines = _run_bench(["--gpus", "2", "--steps", "2", "--warmup", "1", "--repeats", "0"], {"MGM_STUB_FAIL_AT": "rccl"})
+    r, d, lines = _run_bench(["--gpus", "2", "--steps", "2", "--warmup", "1", "--repeats", "0", "--full"], {"MGM_STUB_FAIL_AT": "rccl"})
     assert r.returncode == 0 and len(lines) == 1, r.stderr[-2000:]
     dr = d["directions"]
     assert dr["transport"] == "peer" and dr["ranks"] == 2 and dr["value"] == dr["peer"]["value"] and "error" in dr["rccl"]
     assert dr["fallback_chain"][0].startswith("rccl: failed") and dr["fallback_chain"][1] == "peer: ok" and "error" in dr["rccl_link_probe"]
-    r, d, lines = _run_bench(["--gpus", "2", "--steps", "2", "--warmup", "1", "--repeats", "0"], {"MGM_STUB_FAIL_AT": "rccl,peer"})
+    r, d, lines = _run_bench(["--gpus", "2", "--steps", "2", "--warmup", "1", "--repeats", "0", "--full"], {"MGM_STUB_FAIL_AT": "rccl,peer"})
     assert r.returncode == 0 and len(lines) == 1, r.stderr[-2000:]
     dr = d["directions"]
     assert dr["transport"] == "replicas" and dr["value"] is None and dr["ranks"] == 2 and d["value"] > 0
@@ -337,7 +369,7 @@ def test_a_rank_killed_mid_exchange_leaves_a_valid_line():
     agreement and its first transfer (SIGKILL: no Python teardown, its sockets just close) must not take the line with it.  The
     survivors' exchange fails or times out, torch.distributed.run terminates them (SIGTERM), and rank 0 still prints the ONE json
     line with the headline and everything measured before the leg; the exit code says a rank failed."""
-    r, d, lines = _run_bench(["--gpus", "2", "--steps", "2", "--warmup", "1", "--repeats", "0", "--extras-timeout", "120"],
+    r, d, lines = _run_bench(["--gpus", "2", "--steps", "2", "--warmup", "1", "--repeats", "0", "--extras-timeout", "120", "--full"],
                              {"MGM_STUB_DIE_AT": "exchange"}, timeout=600)
     assert len(lines) == 1, (r.returncode, r.stdout[-500:], r.stderr[-2000:])
     assert d["value"] > 0 and d["n_gpus"] == 2 and d["config"]["workload"].startswith("cfg3") and d["cfg5_replicas"]["value"] > 0

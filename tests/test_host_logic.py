@@ -80,3 +80,46 @@ def test_roofline_of_range_proportional_launch_prices_owned_cells():
     assert rel["frac"] < 1.0 < rel["frac_dense_hull_equivalent"]
     assert abs(hull["frac"] - hull["frac_dense_hull_equivalent"]) < 1e-12 and hull["frac_range_proportional"] < hull["frac"]
     assert rel["algorithmic_bytes_per_launch"] == 12.0 * w["NDIR"] * w["nx"] * w["ny"] * (2 * w["ragged"] + 1) * 4
+
+
+def test_dump_outputs_writes_finite_files_that_decode_exactly(tmp_path):
+    """bench.dump_outputs: maps holding NaN (a pixel without a disparity) and infinities go out as finite values plus the code
+    of every non-finite element, and decode to the very maps; large maps keep the same seeded pixels of every pair."""
+    import bench
+
+    class Img:
+        def __init__(self, a):
+            self.a = a
+
+        def download(self):
+            return self.a[None].copy()
+
+    rng = np.random.default_rng(3)
+    nx, ny, B = 37, 29, 3
+    maps = []
+    for b in range(2 * B):
+        a = rng.standard_normal((ny, nx)).astype(np.float32)
+        a.flat[rng.choice(nx * ny, 40, replace=False)] = rng.choice(np.array([np.nan, np.inf, -np.inf], np.float32), 40)
+        maps.append(a)
+    got = bench.dump_outputs(str(tmp_path / "w"), [Img(a) for a in maps[:B]], [Img(a) for a in maps[B:]], nx, ny)
+    assert not got["sampled"]
+    codes = {v: k for k, v in got["nonfinite_codes"].items()}
+    back = {"nan": np.nan, "+inf": np.inf, "-inf": -np.inf}
+    for name, want in (("disparity", maps[:B]), ("cost", maps[B:])):
+        v, c = np.load(tmp_path / "w" / (name + ".npy")), np.load(tmp_path / "w" / (name + "_nonfinite.npy"))
+        assert v.dtype == c.dtype == np.float32 and np.isfinite(v).all() and np.isfinite(c).all() and v.shape == (B, ny, nx)
+        dec = v.copy()
+        for code in np.unique(c[c != 0]):
+            dec[c == code] = back[codes[float(code)]]
+        assert np.array_equal(dec, np.stack(want), equal_nan=True)
+    old = bench.DUMP_MAX_BYTES
+    bench.DUMP_MAX_BYTES = 4096
+    try:
+        got = bench.dump_outputs(str(tmp_path / "s"), [Img(a) for a in maps[:B]], [Img(a) for a in maps[B:]], nx, ny)
+    finally:
+        bench.DUMP_MAX_BYTES = old
+    assert got["sampled"] and got["bytes"] <= 4096
+    idx = np.load(tmp_path / "s" / "pixel_index.npy").astype(np.int64)
+    v, c = np.load(tmp_path / "s" / "cost.npy"), np.load(tmp_path / "s" / "cost_nonfinite.npy")
+    want = np.stack(maps[B:]).reshape(B, -1)[:, idx]
+    assert np.isfinite(v).all() and np.array_equal(np.where(c == 0, v, np.nan), np.where(np.isfinite(want), want, np.nan), equal_nan=True)

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Runs ON THE GPU BOX (gpurun -- 'bash tools/collect_profiles.sh'): the round's measurement evidence.
-#   1. bench lines: the default command (cfg3, 12 pairs per step; parity gate + CPU baseline), then the workload / batch matrix
+#   1. bench lines: the full command (cfg3, 12 pairs per step; parity gate + CPU baseline + extra legs), then the workload / batch matrix
 #   2. per (workload, batch) in $PROFILED: rocprofv3 --kernel-trace --stats of the bench command  -> <tag>_kernel_stats.csv
 #      and rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE (separate passes, counters only)          -> <tag>_hbm_counters.md, <tag>_traffic.json
 # Everything lands in gpurun_out/profiles/; copy what is to be judged into profiles/ afterwards (prefixed with the round).
@@ -14,7 +14,7 @@ MATRIX=${MATRIX:-"cfg3h:12 cfg2:16 cfg5:16 cfg4:1 cfg4:2 cfg3:8 cfg3:4 cfg3:2 cf
 # a stream of single pairs / small batches through a pipelined context (mgm_ctx_set_pipeline): workload:batch:depth
 PIPED=${PIPED:-"cfg3:1:2 cfg3:1:4 cfg3:1:12 cfg3h:1:4 cfg2:1:4 cfg2:1:8 cfg3:2:2"}
 : > "$OUT/bench_lines.jsonl"
-timeout 900 python bench.py 2> "$OUT/bench_default.stderr" | tail -1 >> "$OUT/bench_lines.jsonl"
+timeout 900 python bench.py --full 2> "$OUT/bench_default.stderr" | tail -1 >> "$OUT/bench_lines.jsonl"
 for wb in $MATRIX; do
   w=${wb%%:*}; b=${wb##*:}
   st=20; case $w in cfg3nan|cfg3rinf|cfg3L1536|cfg3L2048) st=3;; esac   # (the slow fall-backs: 0.25-0.4 s per step)
@@ -22,7 +22,7 @@ for wb in $MATRIX; do
 done
 for wbd in $PIPED; do
   w=${wbd%%:*}; rest=${wbd#*:}; b=${rest%%:*}; d=${rest##*:}
-  timeout 600 python bench.py --workload $w --batch $b --pipeline $d --repeats 0 --no-cpu-baseline 2>/dev/null | tail -1 >> "$OUT/bench_lines.jsonl"
+  timeout 600 python bench.py --workload $w --batch $b --pipeline $d --repeats 0 --no-cpu-baseline --full 2>/dev/null | tail -1 >> "$OUT/bench_lines.jsonl"
 done
 for wb in $PROFILED; do
   w=${wb%%:*}; b=${wb##*:}; tag=${w}_b${b}
