@@ -128,7 +128,7 @@ static int costvolume_fill(mgm_ctx *c, const mgm_img *u, const mgm_img *v, int d
     // (a ragged single-word census volume first tries to be written as its range-proportional copy ALONE, below: no compact hull
     // is allocated for it unless that fails)
     const bool rel_direct_candidate = rloI && costfn == 2 && census_words == 1 && rel_enabled() && dev().lazy_f32 && tune_num("rel_direct", 1) != 0 &&
-                                      (truncDist == __builtin_huge_valf() || (truncDist >= 0.0f && truncDist <= 254.0f && truncDist == rintf(truncDist)));
+                                      (truncDist == __builtin_huge_valf() || (truncDist >= 0.0f && !std::signbit(truncDist) && truncDist <= 254.0f && truncDist == rintf(truncDist)));
     auto setup_c8 = [&]() -> int {
         if (c8_supported(dmax - dmin + 1) && dev().c8) {
             if (may_be_integer) {
@@ -237,7 +237,7 @@ static int costvolume_fill(mgm_ctx *c, const mgm_img *u, const mgm_img *v, int d
     const int LP = (!c8_supported(p.L) && dev().c8 && dev().pad && dev().lazy_f32 && !p.rlo) ? padded_labels(p.L) : 0;
     (*out)->rel_only = false;
     const bool census_fits = costfn == 2 && p.nch == 1 &&
-                             (p.trunc == __builtin_huge_valf() || (p.trunc >= 0.0f && p.trunc <= 254.0f && p.trunc == rintf(p.trunc)));
+                             (p.trunc == __builtin_huge_valf() || (p.trunc >= 0.0f && !std::signbit(p.trunc) && p.trunc <= 254.0f && p.trunc == rintf(p.trunc)));
     const bool diff_may_fit = (costfn == 0 || costfn == 1) && (pre == 0 || pre == 2) && p.trunc >= 0.0f && !std::signbit(p.trunc) &&
                               (long long)u->nx * u->ny < 0x7fffffffll;  // (what k_cost_diffx takes)
     // A ragged single-word census volume: the RANGE-PROPORTIONAL copy alone, straight from the descriptor words (mgm_pass_rel.hip,
@@ -311,7 +311,7 @@ static int costvolume_fill(mgm_ctx *c, const mgm_img *u, const mgm_img *v, int d
     // or an integer up to 254 every cost fits the compact form, and the fp32 volume -- which neither K3
     // nor k_wta reads then -- is only materialised on demand (ensure_f32).
     if (p.C8 && !p.rlo && costfn == 2 && p.nch == 1 &&
-        (p.trunc == __builtin_huge_valf() || (p.trunc >= 0.0f && p.trunc <= 254.0f && p.trunc == rintf(p.trunc))) &&
+        (p.trunc == __builtin_huge_valf() || (p.trunc >= 0.0f && !std::signbit(p.trunc) && p.trunc <= 254.0f && p.trunc == rintf(p.trunc))) &&
         dev().lazy_f32) {
         p.C = nullptr;
         (*out)->f32_state = 0;
@@ -820,6 +820,9 @@ int mgm_debug_download_lr(mgm_ctx *c, int pass, float *dense)
         // hull -- label o <-> slot o + dmin - base(p) of the pixel's 64, +INF where the pixel has no such label (test aid only)
         if (pass < 0 || pass >= c->rel_last_ndir) return fail(c, MGM_ERR_INVALID, "mgm_debug_download_lr: no such pass");
         const mgm_cv *C = c->rel_last_cvs[0];
+        // (a volume refilled since -- another slot count, other records -- no longer describes the Lr volumes of that launch)
+        if (C->gen != c->rel_last_gens[0] || C->rel_slots != c->rel_last_slots)
+            return fail(c, MGM_ERR_INVALID, "mgm_debug_download_lr: the volume of the last aggregation has been refilled since");
         const size_t npix = (size_t)C->nx * C->ny;
         const int L = C->dmax - C->dmin + 1;
         HIPCHK(c, hipSetDevice(c->device));

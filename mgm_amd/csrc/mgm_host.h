@@ -107,6 +107,7 @@ struct mgm_ctx {
     std::string tasks_rel_key;
     int ntasks_rel = 0;
     int rel_last_batch = 0, rel_last_ndir = 0;
+    int rel_last_slots = 0;  // label slots per pixel of volume 0's copy at that launch (the Lr stride mgm_debug_download_lr reads at)
     long long rel_last_stride = 0;
     const mgm_cv *rel_last_cvs[kMaxBatch] = {};
     unsigned long long rel_last_gens[kMaxBatch] = {};

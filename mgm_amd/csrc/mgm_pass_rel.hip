@@ -114,7 +114,9 @@ __global__ void __launch_bounds__(256) k_rel_gather(const float *__restrict__ C,
         float x = __builtin_huge_valf();
         if (d >= lo && d <= hi && d - dmin >= 0 && d - dmin < L) {
             x = C[p * L + (d - dmin)];
-            if (x != x || x < 0.0f) {  // (NaN: the operand-order-faithful kernel's; a negative cost: the hand-off tags need L >= +0)
+            // (NaN: the operand-order-faithful kernel's; a negative cost, -0 included: the hand-off tags need L >= +0 -- and -0 is the
+            // reference's cost under truncDist = -0, which the volume keeps on its dense hull rather than turning it into +0)
+            if (x != x || (__builtin_bit_cast(unsigned, x) >> 31)) {
                 bad |= 2u;
                 x = __builtin_huge_valf();
             }

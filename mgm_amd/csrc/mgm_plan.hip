@@ -1367,6 +1367,7 @@ int run_rel(mgm_ctx *c, const mgm_cv *const *Cs, const mgm_img *const *w8s, int 
     c->rel_last_batch = nb;
     c->rel_last_ndir = NDIR;
     c->rel_last_stride = stride;
+    c->rel_last_slots = Cs[0]->rel_slots;
     for (int v = 0; v < kMaxBatch; v++) {
         c->rel_last_cvs[v] = v < nb ? Cs[v] : nullptr;
         c->rel_last_gens[v] = v < nb ? Cs[v]->gen : 0;
