@@ -305,6 +305,74 @@ int mgm_leftright_dev(mgm_ctx *ctx, const mgm_img *d, const mgm_img *other, floa
  * (integer truncation of the reference's float index), u where that falls outside v. */
 int mgm_backproject_dev(mgm_ctx *ctx, const mgm_img *u, const mgm_img *v, const mgm_img *disp, mgm_img *out);
 
+/* ---- coarse-to-fine (multiscale) driver ------------------------------------------------------------------------
+ * The reference has no multiscale program; it ships the one step that only makes sense in one: update_dmin_dmax
+ * (mgm.cc:120-158) gives a pixel whose disparity is NaN -- one the left-right test rejected -- the GLOBAL range.  The
+ * definition below is this project's own, made of reference steps and three resampling rules that are exact in fp32
+ * (DESIGN.md "multiscale" has it in full).  Levels s = 0 (full size) .. S-1; n_{s+1} = (n_s + 1) / 2 for each of nx, ny,
+ * vnx, vny.
+ *   image zoom-out   out(x,y) = ((a + b) + (c + d)) * 0.25f over the 2x2 block at (2x,2y), indices clamped to the image
+ *   range zoom-out   lo' = floorf(0.5f * min lo), hi' = ceilf(0.5f * max hi) over the same four pixels
+ *   prior -> ranges  U(x,y) = 2.0f * D(x >> 1, y >> 1) of the coarser level's FINAL map (NaNs included), then
+ *                    update_dmin_dmax(U, lo, hi, slack, radius) + the two remove_nonfinite_values_Img calls on the level's
+ *                    base ranges; no clipping afterwards.
+ * mgm_multiscale_levels: the effective level count -- the largest S <= nscales (1..8) whose coarsest level still has
+ * min(nx, ny, vnx, vny) >= 16, at least 1 -- and, if dims != NULL, its sizes dims[s] = {nx, ny, vnx, vny}.  Pure host
+ * arithmetic: needs no device.  Returns S, or -MGM_ERR_INVALID (sizes < 1, nscales outside 1..8). */
+int mgm_multiscale_levels(int nx, int ny, int vnx, int vny, int nscales, int *dims);
+/* *out NULL: a new ((nx+1)/2, (ny+1)/2, nch) image; else one of that size, refilled.  `in` must hold no NaN for the
+ * result to be the definition's (the inputs of the path are NaN-free, mgm.cc:335-336). */
+int mgm_zoom_out_dev(mgm_ctx *ctx, const mgm_img *in, mgm_img **out);
+int mgm_ranges_zoom_out_dev(mgm_ctx *ctx, const mgm_img *lo, const mgm_img *hi, mgm_img **lo2, mgm_img **hi2);
+/* The prior -> ranges step as ONE kernel that reads only the coarse map: coarse_disp is ((nx+1)/2, (ny+1)/2), lo / hi are
+ * the fine level's nx*ny base ranges on entry and its updated ranges on return -- bit for bit what zooming the map in
+ * and mgm_update_ranges_dev give.  radius 0..16.  hull_min / hull_max (both or neither): min (int)lo / max (int)hi of
+ * the result, what mgm_costvolume_build_ranged_dev wants; asking for them synchronises (two words come back). */
+int mgm_ranges_from_coarse_dev(mgm_ctx *ctx, const mgm_img *coarse_disp, mgm_img *lo, mgm_img *hi, int slack, int radius,
+                               int *hull_min, int *hull_max);
+
+typedef struct mgm_ms_level {  /* what one level of mgm_multiscale_pair_dev ran on; index 0 = left->right, 1 = right->left */
+    int nx, ny, vnx, vny;
+    int hull_min[2], hull_max[2]; /* min (int)lo / max (int)hi of each run's ranges (a volume batched with the other run's
+                                     may have been built on a wider hull: labels nobody owns read +INF) */
+    int weighted[2];              /* the run's weights hold a value != 1: mgm() takes the weighted update functions */
+    int batched;                  /* both runs shared one launch of the pass kernel */
+} mgm_ms_level;
+
+typedef struct mgm_ms_params {
+    unsigned struct_size; /* sizeof(mgm_ms_params) of the caller: the struct may grow at its end */
+    int nscales;          /* requested levels, 1..8 (fewer run when the images are too small: mgm_multiscale_levels) */
+    int slack, radius;    /* of the prior -> ranges step (the reference's defaults: 3, 2) */
+    int dmin, dmax;       /* -r / -R */
+    const mgm_img *lo, *hi; /* optional level-0 range images of the left->right run (-m / -M after main()'s fix-ups,
+                               mgm.cc:342-353): both or neither */
+    float P1, P2;         /* already multiplied by the channel count (mgm.cc:356-357) */
+    int NDIR, TSGM, use_fh, fix_overcount;
+    float aP2, aThresh;   /* aP2 != 1: image-dependent weights, computed per level from that level's images */
+    const char *prefilter, *distance;
+    float truncDist;
+    int census_win;
+    const char *refine;
+    int iterations;       /* TSGM_ITER as main() counts it (>= 0; 0: mgm() is never called, the maps are zero) */
+    int median;           /* MEDIAN radius, 0 = none */
+    int testlrrl;         /* TESTLRRL: 0 = the left->right chain only */
+    float tau;            /* TESTLRRL_TAU */
+    int *levels_run;      /* optional out: the effective level count */
+    mgm_ms_level *levels; /* optional out: `nscales` entries, [s] filled for every level that ran */
+} mgm_ms_params;
+
+/* One stereo pair, coarse to fine.  Per level exactly what the `mgm` command line does for a pair (weights, ranged cost
+ * volumes, mgm(), refinement, iterations 2..TSGM_ITER, MEDIAN, the two left-right tests) with range images for BOTH
+ * runs; every level but the coarsest takes its ranges from the coarser level's final maps.  nscales = 1 (or images too
+ * small for a second level) is the single-scale result bit for bit.  The two runs of a level share one launch of the pass
+ * kernel when mgm_aggregate_batch_dev takes them and otherwise run one after the other: same results.  Between levels
+ * only the two hull integers per run (and one flag per weighted run) come back to the host; no image is downloaded or
+ * uploaded.  outL / costL: nx*ny; outR / costR: vnx*vny or NULL (with testlrrl = 0 they are left untouched);
+ * outL_nolr: nx*ny or NULL, the left map before the left-right test.  Not on a pipelined context with deferred work of
+ * its own outputs; a failure frees every intermediate object and leaves the context usable. */
+int mgm_multiscale_pair_dev(mgm_ctx *ctx, const mgm_img *u, const mgm_img *v, const mgm_ms_params *p, mgm_img *outL,
+                            mgm_img *costL, mgm_img *outR, mgm_img *costR, mgm_img *outL_nolr);
+
 #ifdef __cplusplus
 }
 #endif

@@ -31,6 +31,7 @@ ABI_SYMBOLS = [
     "mgm_multi_create", "mgm_multi_destroy", "mgm_multi_size", "mgm_multi_ctx", "mgm_multi_last_error", "mgm_multi_plan",
     "mgm_multi_aggregate", "mgm_multi_transport", "mgm_img_device", "mgm_cv_device", "mgm_aggregate_passes_at_dev",
     "mgm_ctx_set_workspace_limit", "mgm_ctx_mem_info", "mgm_ctx_set_pipeline", "mgm_img_update", "mgm_debug_probe_workspace", "mgm_ctx_set_placement_tries",
+    "mgm_multiscale_levels", "mgm_zoom_out_dev", "mgm_ranges_zoom_out_dev", "mgm_ranges_from_coarse_dev", "mgm_multiscale_pair_dev",
 ]
 
 MGM_OK, MGM_ERR_INVALID, MGM_ERR_UNSUPPORTED, MGM_ERR_HIP, MGM_ERR_NOMEM, MGM_ERR_INTERNAL = range(6)
@@ -43,6 +44,22 @@ class MgmError(RuntimeError):
 
 
 _lib = None
+
+
+class MsLevel(C.Structure):
+    """``mgm_ms_level``: what one level of the multiscale driver ran on ([0] left->right, [1] right->left)."""
+    _fields_ = [("nx", C.c_int), ("ny", C.c_int), ("vnx", C.c_int), ("vny", C.c_int), ("hull_min", C.c_int * 2),
+                ("hull_max", C.c_int * 2), ("weighted", C.c_int * 2), ("batched", C.c_int)]
+
+
+class MsParams(C.Structure):
+    """``mgm_ms_params`` (size-prefixed: ``struct_size`` first)."""
+    _fields_ = [("struct_size", C.c_uint), ("nscales", C.c_int), ("slack", C.c_int), ("radius", C.c_int), ("dmin", C.c_int),
+                ("dmax", C.c_int), ("lo", C.c_void_p), ("hi", C.c_void_p), ("P1", C.c_float), ("P2", C.c_float),
+                ("NDIR", C.c_int), ("TSGM", C.c_int), ("use_fh", C.c_int), ("fix_overcount", C.c_int), ("aP2", C.c_float),
+                ("aThresh", C.c_float), ("prefilter", C.c_char_p), ("distance", C.c_char_p), ("truncDist", C.c_float),
+                ("census_win", C.c_int), ("refine", C.c_char_p), ("iterations", C.c_int), ("median", C.c_int),
+                ("testlrrl", C.c_int), ("tau", C.c_float), ("levels_run", C.POINTER(C.c_int)), ("levels", C.POINTER(MsLevel))]
 
 
 def load_library():
@@ -123,6 +140,11 @@ def load_library():
     L.mgm_ctx_set_workspace_limit.argtypes = [vp, C.c_ulonglong]
     L.mgm_ctx_set_pipeline.argtypes = [vp, i]
     L.mgm_ctx_mem_info.argtypes = [vp, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]
+    L.mgm_multiscale_levels.argtypes = [i, i, i, i, i, ip]
+    L.mgm_zoom_out_dev.argtypes = [vp, vp, pp]
+    L.mgm_ranges_zoom_out_dev.argtypes = [vp, vp, vp, pp, pp]
+    L.mgm_ranges_from_coarse_dev.argtypes = [vp, vp, vp, vp, i, i, ip, ip]
+    L.mgm_multiscale_pair_dev.argtypes = [vp, vp, vp, C.POINTER(MsParams), vp, vp, vp, vp, vp]
     _lib = L
     return L
 
@@ -324,6 +346,58 @@ class Context:
     def update_ranges_dev(self, outoff, dminI, dmaxI, slack=3, radius=2):
         self._chk(self.lib.mgm_update_ranges_dev(self.h, outoff.h, dminI.h, dmaxI.h, slack, radius))
 
+    # ---- coarse to fine (mgm_pyramid.hip) ----
+    def zoom_out_dev(self, img, out=None):
+        """2x2 mean with clamped indices: ((a + b) + (c + d)) * 0.25f -> an image of ((nx+1)/2, (ny+1)/2)."""
+        h = C.c_void_p(out.h.value) if out is not None else C.c_void_p()
+        self._chk(self.lib.mgm_zoom_out_dev(self.h, img.h, C.byref(h)))
+        return out if out is not None else Image(self, h)
+
+    def ranges_zoom_out_dev(self, lo, hi):
+        """(floorf(0.5f * min lo), ceilf(0.5f * max hi)) over each 2x2 block: the base ranges of the next coarser level."""
+        a, b = C.c_void_p(), C.c_void_p()
+        self._chk(self.lib.mgm_ranges_zoom_out_dev(self.h, lo.h, hi.h, C.byref(a), C.byref(b)))
+        return Image(self, a), Image(self, b)
+
+    def ranges_from_coarse_dev(self, coarse_disp, lo, hi, slack=3, radius=2, want_hull=True):
+        """lo / hi (the fine level's base ranges) are updated in place from the coarser level's map; returns the integer hull
+        (min (int)lo, max (int)hi) or None."""
+        a, b = C.c_int(), C.c_int()
+        self._chk(self.lib.mgm_ranges_from_coarse_dev(self.h, coarse_disp.h, lo.h, hi.h, slack, radius,
+                                                      C.byref(a) if want_hull else None, C.byref(b) if want_hull else None))
+        return (a.value, b.value) if want_hull else None
+
+    def multiscale_pair(self, u, v, dmin, dmax, nscales, P1=8.0, P2=32.0, NDIR=4, TSGM=4, use_fh=0, fix_overcount=1, aP2=1.0,
+                        aThresh=5.0, prefilter="none", distance="ad", truncDist=float("inf"), census_win=3, refine="none",
+                        iterations=1, median=0, testlrrl=1, tau=1.0, slack=3, radius=2, lo=None, hi=None, want_nolr=True):
+        """mgm_multiscale_pair_dev on device images u, v (P1 / P2 as given: multiply by the channel count yourself).
+        Returns a dict of device images outL, costL, outR, costR (None with testlrrl=0), nolr (None unless wanted) and
+        `levels`: one dict per level that ran, [0] = full size."""
+        _, ny, nx = u.shape
+        _, vny, vnx = v.shape
+        res = dict(outL=self.new_image(nx, ny), costL=self.new_image(nx, ny), outR=None, costR=None, nolr=None)
+        if testlrrl:
+            res["outR"], res["costR"] = self.new_image(vnx, vny), self.new_image(vnx, vny)
+        if want_nolr:
+            res["nolr"] = self.new_image(nx, ny)
+        n = C.c_int(0)
+        lv = (MsLevel * 8)()
+        p = MsParams(C.sizeof(MsParams), nscales, slack, radius, dmin, dmax, lo.h if lo is not None else None,
+                     hi.h if hi is not None else None, P1, P2, NDIR, TSGM, use_fh, fix_overcount, aP2, aThresh, prefilter.encode(),
+                     distance.encode(), truncDist, census_win, (refine or "none").encode(), iterations, median, testlrrl, tau,
+                     C.pointer(n), lv)
+        hnd = lambda im: im.h if im is not None else None
+        r = self.lib.mgm_multiscale_pair_dev(self.h, u.h, v.h, C.byref(p), hnd(res["outL"]), hnd(res["costL"]), hnd(res["outR"]),
+                                             hnd(res["costR"]), hnd(res["nolr"]))
+        if r:
+            for im in res.values():
+                if im is not None:
+                    im.free()
+            self._chk(r)
+        res["levels"] = [dict(nx=l.nx, ny=l.ny, vnx=l.vnx, vny=l.vny, hull=[(l.hull_min[k], l.hull_max[k]) for k in range(2)],
+                              weighted=[bool(l.weighted[k]) for k in range(2)], batched=bool(l.batched)) for l in lv[:n.value]]
+        return res
+
     def median_dev(self, img, radius, out=None):
         nch, ny, nx = img.shape
         out = out or self.new_image(nx, ny, nch)
@@ -425,6 +499,16 @@ class Context:
             self._chk(self.lib.mgm_timing_get(self.h, k, C.byref(name), C.byref(ms)))
             res.append((name.value.decode(), ms.value))
         return res
+
+
+def multiscale_levels(nx, ny, vnx=None, vny=None, nscales=1):
+    """mgm_multiscale_levels: [(nx, ny, vnx, vny)] per level that would run, full size first (no device needed)."""
+    L = load_library()
+    dims = (C.c_int * 32)()
+    S = L.mgm_multiscale_levels(nx, ny, nx if vnx is None else vnx, ny if vny is None else vny, nscales, dims)
+    if S < 0:
+        raise MgmError(-S, "mgm_multiscale_levels: sizes must be >= 1 and nscales 1..8")
+    return [tuple(int(dims[4 * s + k]) for k in range(4)) for s in range(S)]
 
 
 def multi_plan(n, NDIR, ny):

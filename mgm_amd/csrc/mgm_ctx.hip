@@ -110,7 +110,7 @@ int reserve(mgm_ctx *c, Buf &b, size_t bytes)
 int ensure_words(mgm_ctx *c)
 {
     const void *before = c->words.p;
-    if (int r = reserve(c, c->words, sizeof(unsigned) * (4 + (size_t)kMaxBatch * kMaxDirs * 4096))) return r;
+    if (int r = reserve(c, c->words, sizeof(unsigned) * ((size_t)kCtrlWords + kPyrWords))) return r;
     if (c->words.p != before) HIPCHK(c, hipMemsetAsync(c->words.p, 0, c->words.cap, c->stream));
     return MGM_OK;
 }

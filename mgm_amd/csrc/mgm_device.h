@@ -217,6 +217,14 @@ hipError_t launch_refine(const float *S, long long npix, int L, int dmin, int me
                          float vout, float *out, float *outcost, hipStream_t s);
 hipError_t launch_update_ranges(const float *outoff, int nx, int ny, int slack, int radius, float *dminI, float *dmaxI,
                                 float *scratch2, hipStream_t s);
+hipError_t launch_minmax(const float *u, long long n, unsigned *mm, hipStream_t s);
+// mgm_pyramid.hip: the resampling steps of the coarse-to-fine driver ("multiscale")
+hipError_t launch_zoom_out(const float *in, int nx, int ny, int nch, float *out, hipStream_t s);
+hipError_t launch_ranges_zoom_out(const float *lo, const float *hi, int nx, int ny, float *lo2, float *hi2, hipStream_t s);
+hipError_t launch_ranges_from_coarse(const float *coarse, int nx, int ny, int slack, int radius, const unsigned *mm, float *lo,
+                                     float *hi, int *hull, hipStream_t s);
+hipError_t launch_ranges_hull(const float *lo, const float *hi, long long n, int *hull, hipStream_t s);
+hipError_t launch_fill(float *p, long long n, float value, hipStream_t s);
 hipError_t launch_census(const float *u, int nx, int ny, int nch, int winradius, uint32_t *out, hipStream_t s);
 struct CostParams {
     const float *u, *v;          // planar images (float, or census words reinterpreted)

@@ -175,6 +175,7 @@ struct mgm_ctx {
 constexpr int kR = 16;       // lines per band (waves per workgroup) of the pass kernel
 constexpr int kCtrlWords = 4 + kMaxBatch * kMaxDirs * 4096;  // ticket, err, flag, pad, prog[volume*8 + pass][maxbands]
 constexpr int kMaxBands = 4096;
+constexpr int kPyrWords = 4;  // behind the control block: the words of mgm_pyramid.hip (minimum / maximum of a coarse map, integer hull)
 
 // Development switches (A/B timing, tests of the fall-back paths), read once per process; everything is on by default.
 struct DevSwitches {

@@ -832,16 +832,24 @@ __global__ void __launch_bounds__(256) k_update_ranges(const float *__restrict__
     dmaxI[idx] = finite_bits(hi) ? hi : gmax;
 }
 
+// image_minmax alone: mm[0] / mm[1] receive the finite minimum / maximum of u as ordered bit patterns (+INF / -INF when
+// there is no finite sample); mgm_pyramid.hip reads them the same way
+hipError_t launch_minmax(const float *u, long long n, unsigned *mm, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_minmax_init, dim3(1), dim3(1), 0, s, mm);
+    long long nb = (n + 255) / 256;
+    if (nb > 1024) nb = 1024;
+    hipLaunchKernelGGL(k_minmax, dim3((unsigned)nb), dim3(256), 0, s, u, n, mm);
+    return hipGetLastError();
+}
+
 hipError_t launch_update_ranges(const float *outoff, int nx, int ny, int slack, int radius, float *dminI, float *dmaxI,
                                 float *scratch2, hipStream_t s)
 {
     unsigned *mm = reinterpret_cast<unsigned *>(scratch2);
     const long long n = (long long)nx * ny;
     if (slack < 0) slack = -slack;
-    hipLaunchKernelGGL(k_minmax_init, dim3(1), dim3(1), 0, s, mm);
-    long long nb = (n + 255) / 256;
-    if (nb > 1024) nb = 1024;
-    hipLaunchKernelGGL(k_minmax, dim3((unsigned)nb), dim3(256), 0, s, outoff, n, mm);
+    if (hipError_t e = launch_minmax(outoff, n, mm, s)) return e;
     hipLaunchKernelGGL(k_update_ranges, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, outoff, nx, ny, slack, radius, mm, dminI,
                        dmaxI);
     return hipGetLastError();

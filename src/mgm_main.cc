@@ -365,6 +365,7 @@ struct Job {
     // parsed
     Opts o{};
     std::string min_file, max_file, nolr_file, f_u, f_v, f_out, f_cost, f_back;
+    int nscales = 1;          // -S: levels of the coarse-to-fine driver (1: the single-scale path)
     int early = -1;           // >= 0: the command line ends before any work with this code ...
     std::string early_out;    // ... after these lines on stdout
     std::string early_err;    // ... and stderr
@@ -395,8 +396,12 @@ static void parse_job(Job &j)
         return early(0, "mgm [options] in_u in_v out_disp [out_cost [out_backflow]]   (in: png tif pgm ppm pfm npy; out: tif pfm npy)\n"
                         "options: -r dmin(-30) -R dmax(30) -O NDIR(4) -P1 (8) -P2 (32) -p prefilter(none) -t distance(ad)\n"
                         "         -truncDist (inf) -s subpix(none) -aP1 (1) -aP2 (1) -aThresh (5) -m FILE -M FILE -l FILE\n"
+                        "         -S nscales(1): coarse to fine over up to 8 half-size levels (this program's own mode, not the reference's)\n"
                         "environment: CENSUS_NCC_WIN=3 TESTLRRL=1 TESTLRRL_TAU=1.0 MEDIAN=0 TSGM=4 TSGM_ITER=1\n"
                         "             TSGM_FIX_OVERCOUNT=1 USE_TRUNCATED_LINEAR_POTENTIALS=0 MGM_DEVICE=0 MGM_DEVICES=0,1,...\n"
+                        "             MGM_MS_SLACK=3 MGM_MS_RADIUS=2 (-S: window around the coarser level's disparities)\n"
+                        "             (with several MGM_DEVICES, -S / -m -M / TSGM_ITER > 1 run on the first device; in --batch mode a FIRST line\n"
+                        "              of that kind brings up one device for the whole batch, a later one leaves the other lines their devices)\n"
                         "resident mode: mgm --batch FILE|-   (one such command line per line of FILE, one device context for all)");
     if (argc < 4)
         return early(1, nullptr, std::string("too few parameters\n   usage: ") + argv[0] +
@@ -418,6 +423,8 @@ static void parse_job(Job &j)
     o.refine = pick_option(&argc, argv, "s", "none");
     o.truncDist = (float)atof(pick_option(&argc, argv, "truncDist", "inf"));
     j.nolr_file = pick_option(&argc, argv, "l", "");
+    j.nscales = atoi(pick_option(&argc, argv, "S", "1"));
+    if (j.nscales < 1 || j.nscales > 8) return early(1, nullptr, "mgm: -S nscales must be 1..8\n");
     if (argc > 1) j.f_u = argv[1];
     if (argc > 2) j.f_v = argv[2];
     if (argc > 3) j.f_out = argv[3];
@@ -469,7 +476,7 @@ static void encode_job(Job &j)
     }
 }
 
-static void bring_up(Session &S, int ITER, bool ranged)
+static void bring_up(Session &S, int ITER, bool ranged, bool multiscale)
 {
     if (S.tried) return;  // (resident mode: the first job brings the device side up, the others find it there)
     S.tried = true;
@@ -485,6 +492,10 @@ static void bring_up(Session &S, int ITER, bool ranged)
         fprintf(stderr, "mgm: MGM_DEVICES: TSGM_ITER > 1 and range images run on the first device only\n");
         S.devs.resize(1);
     }
+    if (S.devs.size() > 1 && multiscale) {
+        fprintf(stderr, "mgm: MGM_DEVICES: -S (coarse to fine) runs on the first device only\n");
+        S.devs.resize(1);
+    }
     if (S.devs.size() > 1) {
         if ((S.rc_ctx = mgm_multi_create(S.devs.data(), (int)S.devs.size(), &S.multi)) == 0) S.ctx = mgm_multi_ctx(S.multi, 0);
     } else {
@@ -494,6 +505,84 @@ static void bring_up(Session &S, int ITER, bool ranged)
         if (S.rc_ctx == 0 && S.resident) (void)mgm_ctx_set_placement_tries(S.ctx, (int)env_param("MGM_PLACE_TRIES", 0));
         if (S.rc_ctx == 0 && getenv("MGM_HIP_KERNELS") && atoi(getenv("MGM_HIP_KERNELS")) != 0) (void)mgm_timing_enable(S.ctx, 1);
     }
+}
+
+// MGM_HIP_KERNELS=1: which kernels the job ran, in launch order, on stderr (tests assert which pass kernel a command line took)
+static void report_kernels(mgm_ctx *ctx, mgm_multi *multi)
+{
+    if (getenv("MGM_HIP_KERNELS") && atoi(getenv("MGM_HIP_KERNELS")) != 0 && !multi) {
+        const int n = mgm_timing_count(ctx);
+        fprintf(stderr, "[mgm kernels]");
+        for (int k = 0; k < n; k++) {
+            const char *name = nullptr;
+            float ms = 0;
+            if (mgm_timing_get(ctx, k, &name, &ms) == 0 && name) fprintf(stderr, " %s", name);
+        }
+        fprintf(stderr, "\n");
+        (void)mgm_timing_reset(ctx);
+    }
+}
+
+// -S nscales > 1: the pair coarse to fine (mgm_multiscale_pair_dev; DESIGN.md "multiscale" -- this program's own mode, the
+// reference has none).  stdout: level by level from the coarsest, the lines a single-scale job prints for that level.  The
+// nolr map, the cost map and the back-projected image refer to the full-size level.  Device objects are this job's own.
+static void multiscale_job(Session &S, Job &j, const Opts &o, const HostImg *plo, const HostImg *phi, int ITER, bool both, float tau,
+                           int median, Stopwatch &sw)
+{
+    mgm_ctx *ctx = S.ctx;
+    free_run(ctx, S.R);  // (kept from an earlier single-scale pair)
+    free_run(ctx, S.L);
+    const HostImg &u = j.u, &v = j.v;
+    struct Objs {
+        mgm_ctx *ctx;
+        mgm_img *du = nullptr, *dv = nullptr, *dlo = nullptr, *dhi = nullptr, *out = nullptr, *cost = nullptr, *nolr = nullptr, *syn = nullptr;
+        ~Objs()
+        {
+            for (mgm_img *im : {du, dv, dlo, dhi, out, cost, nolr, syn}) mgm_img_free(ctx, im);
+        }
+    } d{ctx};
+    int rc;
+    if ((rc = mgm_img_upload(ctx, u.data.data(), u.nx, u.ny, u.nch, &d.du)) || (rc = mgm_img_upload(ctx, v.data.data(), v.nx, v.ny, v.nch, &d.dv)))
+        die(ctx, rc, "upload");
+    if (plo && ((rc = mgm_img_upload(ctx, plo->data.data(), u.nx, u.ny, 1, &d.dlo)) || (rc = mgm_img_upload(ctx, phi->data.data(), u.nx, u.ny, 1, &d.dhi))))
+        die(ctx, rc, "upload");
+    for (mgm_img **im : {&d.out, &d.cost}) image_like(ctx, u.nx, u.ny, 1, im);
+    if (!j.nolr_file.empty()) image_like(ctx, u.nx, u.ny, 1, &d.nolr);
+    mgm_ms_level levels[8] = {};
+    int nlev = 0;
+    mgm_ms_params p{};
+    p.struct_size = sizeof p;
+    p.nscales = j.nscales;
+    p.slack = (int)env_param("MGM_MS_SLACK", 3);
+    p.radius = (int)env_param("MGM_MS_RADIUS", 2);
+    p.dmin = o.dmin, p.dmax = o.dmax;
+    p.lo = d.dlo, p.hi = d.dhi;
+    p.P1 = o.P1, p.P2 = o.P2, p.NDIR = o.NDIR, p.TSGM = o.TSGM, p.use_fh = o.FH, p.fix_overcount = o.FIX;
+    p.aP2 = o.aP2, p.aThresh = o.aThresh;
+    p.prefilter = o.prefilter.c_str(), p.distance = o.distance.c_str(), p.truncDist = o.truncDist, p.census_win = o.census_win;
+    p.refine = o.refine.c_str();
+    p.iterations = ITER, p.median = median, p.testlrrl = both, p.tau = tau;
+    p.levels_run = &nlev, p.levels = levels;
+    sw.mark("upload");
+    if ((rc = mgm_multiscale_pair_dev(ctx, d.du, d.dv, &p, d.out, d.cost, nullptr, nullptr, d.nolr))) die(ctx, rc, "mgm_multiscale_pair");
+    for (int s = nlev - 1; s >= 0; s--)
+        for (int k = 0; k < (both ? 2 : 1); k++)
+            for (int it = 0; it < ITER; it++) {
+                Run r;
+                r.weighted_msg = levels[s].weighted[k] != 0;
+                report_run(o, r);
+            }
+    sw.mark("enqueue");
+    if (!j.nolr_file.empty()) j.nolr = download(ctx, d.nolr, u.nx, u.ny, 1);
+    j.outoff = download(ctx, d.out, u.nx, u.ny, 1);
+    sw.mark("device+download");
+    if (!j.f_cost.empty()) j.outcost = download(ctx, d.cost, u.nx, u.ny, 1);
+    if (!j.f_back.empty()) {  // back-projected image (mgm.cc:433-443)
+        image_like(ctx, u.nx, u.ny, u.nch, &d.syn);
+        if ((rc = mgm_backproject_dev(ctx, d.du, d.dv, d.out, d.syn))) die(ctx, rc, "mgm_backproject");
+        j.syn = download(ctx, d.syn, u.nx, u.ny, u.nch);
+    }
+    sw.mark("download(rest)");
 }
 
 // DEVICE: everything between the decoded inputs and the downloaded maps; the job's stdout.  `decoded`: waits for the
@@ -512,7 +601,7 @@ static int device_job(Session &S, Job &j, const std::function<void()> &decoded, 
     const int ITER = TSGM_ITER > 0 ? (int)std::ceil(TSGM_ITER) : 0;
     const bool ranged = !j.min_file.empty();
     try {
-        bring_up(S, ITER, ranged);
+        bring_up(S, ITER, ranged, j.nscales > 1);
         sw.mark("context");
         decoded();
         sw.mark("decode(rest)");
@@ -526,6 +615,10 @@ static int device_job(Session &S, Job &j, const std::function<void()> &decoded, 
         if (S.rc_ctx) {
             fprintf(stderr, "mgm: no usable MI355X device (mgm_ctx_create = %d); there is no CPU path\n", S.rc_ctx);
             return 1;
+        }
+        if (multi && j.nscales > 1) {  // (resident mode: an earlier line brought several devices up)
+            fprintf(stderr, "mgm: MGM_DEVICES: -S (coarse to fine) runs on the first device only\n");
+            multi = nullptr;
         }
         if (multi && ranged) {
             fprintf(stderr, "mgm: --batch with MGM_DEVICES: range images are not supported on several devices\n");
@@ -550,6 +643,11 @@ static int device_job(Session &S, Job &j, const std::function<void()> &decoded, 
         int rc;
         Run &L = S.L, &R = S.R;
         const bool both = TESTLRRL != 0;
+        if (j.nscales > 1) {
+            multiscale_job(S, j, o, plo, phi, ITER, both, (float)TAU, (int)MEDIAN, sw);
+            report_kernels(ctx, multi);
+            return 0;
+        }
         if (!both && R.C) free_run(ctx, R);  // (kept from an earlier pair, not wanted by this one)
         prepare_run(ctx, u, v, o.dmin, o.dmax, o, L, plo, phi);
         bool together = false, r_ready = false;
@@ -632,18 +730,7 @@ static int device_job(Session &S, Job &j, const std::function<void()> &decoded, 
             mgm_img_free(ctx, dsyn);
         }
         sw.mark("download(rest)");
-        // MGM_HIP_KERNELS=1: which kernels the job ran, in launch order, on stderr (tests assert which pass kernel a command line took)
-        if (getenv("MGM_HIP_KERNELS") && atoi(getenv("MGM_HIP_KERNELS")) != 0 && !multi) {
-            const int n = mgm_timing_count(ctx);
-            fprintf(stderr, "[mgm kernels]");
-            for (int k = 0; k < n; k++) {
-                const char *name = nullptr;
-                float ms = 0;
-                if (mgm_timing_get(ctx, k, &name, &ms) == 0 && name) fprintf(stderr, " %s", name);
-            }
-            fprintf(stderr, "\n");
-            (void)mgm_timing_reset(ctx);
-        }
+        report_kernels(ctx, multi);
     } catch (const DeviceError &e) {
         fprintf(stderr, "mgm: %s\n", e.what());
         // whatever the failed job left half-made goes; the context stays (resident mode: the next job starts clean)
