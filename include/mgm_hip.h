@@ -97,7 +97,10 @@ const char *mgm_version(void);
 
 /* Per-kernel timing with HIP events on the ctx stream.  While enabled every
  * kernel launch is bracketed by an event pair; mgm_timing_get() synchronises
- * and reports elapsed milliseconds per launch in launch order. */
+ * and reports elapsed milliseconds per launch in launch order.  A cost-volume
+ * fill is listed TWICE with the same milliseconds: as "k_cost", then under the
+ * name of the kernel the dispatcher chose ("k_cost_diffx_1b", "k_cost_ncc",
+ * "k_cost_general", ...): sum the table by name, not over all of its rows. */
 int mgm_timing_enable(mgm_ctx *ctx, int enable);
 int mgm_timing_reset(mgm_ctx *ctx);
 int mgm_timing_count(mgm_ctx *ctx);

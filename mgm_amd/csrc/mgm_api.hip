@@ -251,6 +251,7 @@ static int costvolume_fill(mgm_ctx *c, const mgm_img *u, const mgm_img *v, int d
             HIPCHK(c, hipMemsetAsync(flag, 0, 4, c->stream));
             {
                 TimeScope t(c, "k_cost");
+                t.kernel = "k_cost_census_rel";
                 HIPCHK(c, launch_cost_census_rel(p.cu, p.cv, p.nx, p.ny, p.vnx, p.vny, dmin, p.L, p.trunc, p.rlo, p.rhi, slots, (*out)->relbuf, (*out)->rel_records(),
                                                  flag, c->stream));
             }
@@ -282,7 +283,7 @@ static int costvolume_fill(mgm_ctx *c, const mgm_img *u, const mgm_img *v, int d
             q.L = LP;
             {
                 TimeScope t(c, "k_cost");
-                HIPCHK(c, launch_cost(q, c->stream));
+                HIPCHK(c, launch_cost(q, c->stream, &t.kernel));
             }
             bool fits = census_fits;  // (min(popcount, trunc) in integers: fits and is NaN-free by construction, nothing to read back)
             if (!fits) {
@@ -329,7 +330,7 @@ static int costvolume_fill(mgm_ctx *c, const mgm_img *u, const mgm_img *v, int d
         for (;;) {
             {
                 TimeScope t(c, "k_cost");
-                HIPCHK(c, launch_cost(p, c->stream));
+                HIPCHK(c, launch_cost(p, c->stream, &t.kernel));
             }
             HIPCHK(c, hipMemcpyAsync(c->h_words + 3, (*out)->bad8, 4, hipMemcpyDeviceToHost, c->stream));
             HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -363,7 +364,7 @@ static int costvolume_fill(mgm_ctx *c, const mgm_img *u, const mgm_img *v, int d
     }
     {
         TimeScope t(c, "k_cost");
-        HIPCHK(c, launch_cost(p, c->stream));
+        HIPCHK(c, launch_cost(p, c->stream, &t.kernel));
     }
     // A ragged volume also gets its RANGE-PROPORTIONAL copy (mgm_pass_rel.hip): 64 cost bytes per pixel at the pixel's own
     // window -- what the aggregation then walks instead of the hull, if every window is at most 62 labels wide and every

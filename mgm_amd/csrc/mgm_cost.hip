@@ -401,11 +401,12 @@ hipError_t launch_compact(const float *C, long long n, uint8_t *C8, int cbytes, 
     return hipGetLastError();
 }
 
-hipError_t launch_cost(const CostParams &p, hipStream_t s)
+hipError_t launch_cost(const CostParams &p, hipStream_t s, const char **which)
 {
     bool taken = false;
-    const hipError_t e = launch_cost_fast(p, s, &taken);  // (mgm_cost_fast.hip)
+    const hipError_t e = launch_cost_fast(p, s, &taken, which);  // (mgm_cost_fast.hip)
     if (taken || e != hipSuccess) return e;
+    if (which) *which = "k_cost_general";
     const long long npix = (long long)p.nx * p.ny;
     if (p.Lreal != p.L) return hipErrorInvalidValue;  // (padded layouts: only the kernels of mgm_cost_fast.hip write them)
     hipLaunchKernelGGL(k_cost, dim3((unsigned)((npix + 3) / 4)), dim3(256), 0, s, p);

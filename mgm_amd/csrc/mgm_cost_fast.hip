@@ -678,9 +678,11 @@ static void launch_census8x(const CostParams &p, dim3 grid, unsigned tb, hipStre
     else hipLaunchKernelGGL((k_cost_census8x<L, true>), grid, dim3(256), 0, s, p.cu, p.cv, p.nx, p.ny, p.vnx, p.vny, p.dmin, tb, p.C8, p.Lreal);
 }
 // Launches the restructured kernel that serves `p`, if there is one (*taken), else leaves the volume to the general kernel.
-hipError_t launch_cost_fast(const CostParams &p, hipStream_t s, bool *taken)
+hipError_t launch_cost_fast(const CostParams &p, hipStream_t s, bool *taken, const char **which)
 {
     *taken = true;
+    const char *unused = nullptr;
+    const char *&name = which ? *which : unused;
     const long long npix = (long long)p.nx * p.ny;
     if (p.costfn == 3 && p.ncc_u && p.ncc_v && p.C && !p.C8 && !p.rlo && p.hwin >= 1 && p.hwin <= kNccMaxHw && p.L <= kNccMaxL && p.nch <= 4) {
         const long long vpix = (long long)p.vnx * p.vny;
@@ -690,6 +692,7 @@ hipError_t launch_cost_fast(const CostParams &p, hipStream_t s, bool *taken)
         const size_t lds = sizeof(float) * (size_t)p.nch * win * ((kNccPxb + 2 * p.hwin) + (kNccPxb + p.L - 1 + 2 * p.hwin));
         const dim3 grid((unsigned)(((p.nx + kNccPxb - 1) / kNccPxb) * (long long)p.ny));
         hipError_t e = hipSuccess;
+        name = "k_cost_ncc";
         switch (p.hwin) {
             case 1:
                 e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_cost_ncc<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -713,6 +716,7 @@ hipError_t launch_cost_fast(const CostParams &p, hipStream_t s, bool *taken)
         long long nw = ((long long)((p.nx + 3) / 4) * p.ny + 3) / 4;
         if (nw > 256 * 64) nw = 256 * 64;
         if (nw < 1) nw = 1;
+        name = p.nx % 4 ? "k_cost_btx_bt" : "k_cost_btx_bt_w4";
         if (p.costfn == 5) launch_btx<5>(p, nw, s);
         else launch_btx<4>(p, nw, s);
         return hipGetLastError();
@@ -722,6 +726,7 @@ hipError_t launch_cost_fast(const CostParams &p, hipStream_t s, bool *taken)
         long long nw = ((long long)((p.nx + 3) / 4) * p.ny + 3) / 4;
         if (nw > 256 * 64) nw = 256 * 64;
         if (nw < 1) nw = 1;
+        name = p.costfn == 2 ? (p.nx % 4 ? "k_cost_btx_census" : "k_cost_btx_census_w4") : (p.nx % 4 ? "k_cost_btx_diff" : "k_cost_btx_diff_w4");
         if (p.costfn == 0) launch_btx<0>(p, nw, s);
         else if (p.costfn == 1) launch_btx<1>(p, nw, s);
         else launch_btx<2>(p, nw, s);
@@ -730,6 +735,8 @@ hipError_t launch_cost_fast(const CostParams &p, hipStream_t s, bool *taken)
     // (k_cost_diffx takes truncDist = +INF or a non-negative number, sign bit clear; anything else goes to k_cost below)
     if (!p.C && p.C8 && (p.costfn == 0 || p.costfn == 1) && !p.rlo && npix < 0x7fffffffll && c8_supported(p.L) &&
         (p.cbytes == 1 || p.cbytes == 2) && p.L * p.cbytes <= 1024 && p.trunc >= 0.0f && !__builtin_signbit(p.trunc)) {
+        name = p.cbytes == 2 ? (p.nch == 1 || p.nch == 3 ? "k_cost_diffx_2b" : "k_cost_diffx_2b_anych")
+                             : (p.nch == 1 || p.nch == 3 ? "k_cost_diffx_1b" : "k_cost_diffx_1b_anych");
         if (p.cbytes == 2) p.costfn == 1 ? launch_diffx<2, true>(p, s) : launch_diffx<2, false>(p, s);
         else p.costfn == 1 ? launch_diffx<1, true>(p, s) : launch_diffx<1, false>(p, s);
         return hipGetLastError();
@@ -743,6 +750,7 @@ hipError_t launch_cost_fast(const CostParams &p, hipStream_t s, bool *taken)
             long long nw = ((long long)((p.nx + 3) / 4) * p.ny * 4 * p.L / 4096 + 3) / 4 + 1;
             if (nw > 256 * 32) nw = 256 * 32;
             const dim3 gridw((unsigned)nw);
+            name = p.nx % 4 ? "k_cost_census8x" : "k_cost_census8x_w4";
             switch (p.L) {
                 case 64: launch_census8x<64>(p, gridw, tb, s); break;
                 case 128: launch_census8x<128>(p, gridw, tb, s); break;
@@ -759,6 +767,7 @@ hipError_t launch_cost_fast(const CostParams &p, hipStream_t s, bool *taken)
             long long nw = (npix * p.L / 1024 + 3) / 4 + 1;
             if (nw > 256 * 32) nw = 256 * 32;
             const dim3 gridw((unsigned)nw);
+            name = "k_cost_census8w";
             switch (p.L) {
                 case 64: hipLaunchKernelGGL(k_cost_census8w<64>, gridw, block, 0, s, p.cu, p.cv, p.nx, p.ny, p.vnx, p.vny, p.dmin, tb, p.C8); break;
                 case 128: hipLaunchKernelGGL(k_cost_census8w<128>, gridw, block, 0, s, p.cu, p.cv, p.nx, p.ny, p.vnx, p.vny, p.dmin, tb, p.C8); break;
@@ -768,6 +777,7 @@ hipError_t launch_cost_fast(const CostParams &p, hipStream_t s, bool *taken)
             return hipGetLastError();
         }
         const dim3 grid((unsigned)nb);
+        name = "k_cost_census8";
         switch (p.L / 64) {
             case 1: hipLaunchKernelGGL(k_cost_census8<1>, grid, block, 0, s, p.cu, p.cv, p.nx, p.ny, p.vnx, p.vny, p.dmin, tb, p.C8, p.Lreal); break;
             case 2: hipLaunchKernelGGL(k_cost_census8<2>, grid, block, 0, s, p.cu, p.cv, p.nx, p.ny, p.vnx, p.vny, p.dmin, tb, p.C8, p.Lreal); break;

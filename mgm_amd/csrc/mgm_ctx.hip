@@ -276,6 +276,7 @@ int mgm_ctx_destroy(mgm_ctx *c)
     for (Buf *b : bufs)
         if (b->p) (void)hipFree(b->p);
     for (auto &t : c->tim) {
+        if (t.alias) continue;
         (void)hipEventDestroy(t.a);
         (void)hipEventDestroy(t.b);
     }
@@ -382,6 +383,7 @@ int mgm_timing_reset(mgm_ctx *c)
     if (!c) return MGM_ERR_INVALID;
     (void)hipStreamSynchronize(c->stream);
     for (auto &t : c->tim) {
+        if (t.alias) continue;
         (void)hipEventDestroy(t.a);
         (void)hipEventDestroy(t.b);
     }

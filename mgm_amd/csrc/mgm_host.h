@@ -92,6 +92,7 @@ struct Buf {  // grow-only device scratch
 struct Timing {
     const char *name;
     hipEvent_t a, b;
+    bool alias = false;  // a second name for the entry before it: the same two events (destroyed once, with that entry)
 };
 
 struct mgm_ctx {
@@ -217,6 +218,7 @@ struct TimeScope {  // brackets one kernel launch with events when timing is on
     mgm_ctx *c;
     Timing t{};
     bool on;
+    const char *kernel = nullptr;  // which kernel a dispatcher chose (launch_cost): listed after `name` with the same time
     TimeScope(mgm_ctx *ctx, const char *name) : c(ctx), on(ctx->timing)
     {
         if (!on) return;
@@ -232,6 +234,11 @@ struct TimeScope {  // brackets one kernel launch with events when timing is on
         if (!on) return;
         (void)hipEventRecord(t.b, c->stream);
         c->tim.push_back(t);
+        if (kernel) {
+            t.name = kernel;
+            t.alias = true;
+            c->tim.push_back(t);
+        }
     }
 };
 
