@@ -55,6 +55,7 @@ def build(force=False, verbose=False):
     os.makedirs(OBJDIR, exist_ok=True)
     cc = hipcc()
     headers = [os.path.join(CSRC, "mgm_device.h"), os.path.join(CSRC, "mgm_pass_common.h"), os.path.join(CSRC, "mgm_host.h"), os.path.join(CSRC, "mgm_cost_common.h"),
+               os.path.join(CSRC, "mgm_geom.h"), os.path.join(CSRC, "mgm_planner.h"),
                os.path.join(HERE, "..", "include", "mgm_hip.h"),
                os.path.abspath(__file__)]
     jobs = []

@@ -142,54 +142,6 @@ int refinement_index(const char *n)  // mgm_refine.h:15-35
 }
 
 
-// Canonical geometry of a pass (see PassGeom).  Returns false if the table
-// entry does not reduce to one of the two canonical neighbour orders.
-bool make_geom(int pass, int nx, int ny, int R, int MGM, bool slope1_ok, PassGeom &g)
-{
-    const RefPass &rp = kPasses[pass];
-    const long long sx = rp.inc_x ? 1 : -1, sy = rp.inc_y ? 1 : -1;
-    g.base = (long long)(rp.inc_y ? 0 : ny - 1) * nx + (rp.inc_x ? 0 : nx - 1);
-    if (rp.row_major) {
-        g.NL = ny;
-        g.LL = nx;
-        g.istep = sx;
-        g.jstep = sy * nx;
-    } else {
-        g.NL = nx;
-        g.LL = ny;
-        g.istep = sy * nx;
-        g.jstep = sx;
-    }
-    int kind[4];
-    for (int k = 0; k < 4; k++) {
-        const int dx = rp.d[k][0], dy = rp.d[k][1];
-        const int di = rp.row_major ? dx * (int)sx : dy * (int)sy;
-        const int dj = rp.row_major ? dy * (int)sy : dx * (int)sx;
-        if (di == -1 && dj == 0) kind[k] = 0;        // inline
-        else if (di == 0 && dj == -1) kind[k] = 1;   // same
-        else if (di == -1 && dj == -1) kind[k] = 2;  // back
-        else if (di == 1 && dj == -1) kind[k] = 3;   // fwd
-        else return false;
-        g.wplane[k] = kPassToChannel[k][pass];
-    }
-    if (kind[0] == 0 && kind[1] == 1 && kind[2] == 2 && kind[3] == 3) g.form = 0;
-    else if (kind[0] == 3 && kind[1] == 2 && kind[2] == 1 && kind[3] == 0) g.form = 1;
-    else return false;
-    g.nbands = (g.NL + R - 1) / R;
-    // form 0 sums inline, same, back, fwd: with MGM <= 3 the fwd neighbour (i+1, j-1) is never read,
-    // so a line only has to stay ONE pixel behind the previous one (second K3 build only)
-    g.slope = (slope1_ok && g.form == 0 && MGM <= 3) ? 1 : 2;
-    g.nstrips = 1;
-    g.split = g.LL;
-    g.hand_base = 0;
-    g.diag = 0;
-    g.wmax = 0;
-    g.swap = 0;
-    return true;
-}
-
-
-
 // The watchdog word of the pass kernel is STICKY on the device: no launch resets it, a copy of it follows every pass
 // launch into h_words[1], and only the host clears it, once it has seen it set.  A hand-off time-out of one launch is
 // therefore reported by whichever call next finds the stream idle (block = false: pass launches look without waiting --
@@ -204,7 +156,7 @@ int check_watchdog(mgm_ctx *c, bool block)
     if (c->h_words[1] != 0) {
         c->h_words[1] = 0;
         if (c->words.p) (void)hipMemsetAsync((unsigned *)c->words.p + 1, 0, sizeof(unsigned), c->stream);
-        c->hand_key.clear();  // (the launch may have left its hand-off slots half written)
+        c->hand_key = HandLayout{};  // (the launch may have left its hand-off slots half written)
         return fail(c, MGM_ERR_INTERNAL, "pass kernel watchdog: inter-band hand-off timed out");
     }
     return MGM_OK;
@@ -264,15 +216,15 @@ int mgm_ctx_destroy(mgm_ctx *c)
     (void)pipe_join(c);  // (deferred calls of a pipelined context still write the caller's images)
     (void)hipStreamSynchronize(c->stream);
     std::vector<Buf *> bufs = {&c->lr, &c->hand, &c->hand2, &c->handm, &c->exact_mins, &c->exact_scratch, &c->words, &c->census_u, &c->census_v, &c->dbg, &c->stmp, &c->ones8,
-                               &c->lr_rel, &c->hand_rel, &c->tasks_rel};  // (the range-proportional kernels' workspace: round 5 forgot it here)
+                               &c->lr_rel, &c->hand_rel};  // (the range-proportional kernels' workspace: round 5 forgot it here)
     for (int v = 0; v < kMaxBatch; v++) {
         bufs.push_back(&c->padf[v]);
         bufs.push_back(&c->pad8[v]);
         bufs.push_back(&c->wsel[v]);
     }
     bufs.push_back(&c->wvals);
-    for (auto &t : c->ttabs)
-        if (t.buf.p) (void)hipFree(t.buf.p);
+    c->dense_plans.free_all();
+    c->rel_plans.free_all();
     for (Buf *b : bufs)
         if (b->p) (void)hipFree(b->p);
     for (auto &t : c->tim) {
@@ -306,9 +258,8 @@ int mgm_ctx_trim(mgm_ctx *c)
     HIPCHK(c, hipSetDevice(c->device));
     if (int r = mgm_ctx_synchronize(c)) return r;
     std::vector<Buf *> bufs = {&c->lr, &c->hand, &c->hand2, &c->handm, &c->exact_mins, &c->exact_scratch, &c->census_u, &c->census_v, &c->dbg, &c->stmp, &c->ones8,
-                               &c->lr_rel, &c->hand_rel, &c->tasks_rel};
-    c->tasks_rel_key.clear();
-    c->hand_rel_key.clear();
+                               &c->lr_rel, &c->hand_rel};
+    c->hand_rel_key = HandLayout{};
     c->rel_last_batch = 0;
     for (int v = 0; v < kMaxBatch; v++) {
         bufs.push_back(&c->padf[v]);
@@ -321,13 +272,9 @@ int mgm_ctx_trim(mgm_ctx *c)
         b->p = nullptr;
         b->cap = 0;
     }
-    c->hand_key.clear();
-    c->tk_nx = c->tk_ny = c->tk_ndir = c->tk_r = -1;
-    c->ntasks = 0;
-    for (auto &t : c->ttabs)
-        if (t.buf.p) (void)hipFree(t.buf.p);
-    c->ttabs.clear();
-    c->tasks = Buf{};
+    c->hand_key = HandLayout{};
+    c->dense_plans.free_all();
+    c->rel_plans.free_all();
     c->last_ndir = c->last_batch = 0;
     for (int v = 0; v < kMaxBatch; v++) c->last_cvs[v] = nullptr;
     return MGM_OK;

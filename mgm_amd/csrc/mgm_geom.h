@@ -1,0 +1,57 @@
+// mgm_geom.h -- the limits, the reference's pass table and the canonical geometry of a pass: plain C++ shared by the kernels
+// (mgm_device.h) and the HIP-free launch planner (mgm_planner.h).  Standard headers only.
+#pragma once
+
+namespace mgm {
+
+constexpr int kMaxDirs = 8;
+constexpr int kMaxBands = 4096;
+constexpr int kR = 16;  // lines per band (waves per workgroup) of the pass kernel
+
+// Geometry of one pass in canonical coordinates (i = position along the scan
+// line, j = line index).  Derived on the host from the reference's pass table
+// (mgm_core.cc:463-471): pixel(i,j) = base + i*istep + j*jstep.  In these
+// coordinates every pass has the same four neighbours
+//   inline (i-1,j)   same (i,j-1)   back (i-1,j-1)   fwd (i+1,j-1)
+// and only the ORDER in which they are summed differs:
+//   form 0 (passes 0-3): inline, same, back, fwd
+//   form 1 (passes 4-7): fwd, back, same, inline
+struct PassGeom {
+    int NL, LL;        // number of lines, pixels per line
+    int form;          // 0 / 1
+    int nbands;        // ceil(NL / R)
+    int slope;         // pixels of lead a line keeps over the next one: 2, or 1 when no fwd neighbour is used
+    long long base;    // pixel index of (0,0)
+    long long istep;   // pixel-index step along the line
+    long long jstep;   // pixel-index step between lines
+    int wplane[4];     // weight plane of neighbour k (mgm_core.cc:481-484)
+    int nstrips, split;   // 2: the lines of this pass are walked as two strips [0, split) and [split, LL) by two workgroups per band
+                          // (k_pass2, TAGS, form 1 with 2 or 3 neighbours: no in-line dependency), both from the image edge inwards
+    long long hand_base;  // self-validating hand-off slabs (k_pass2, TAGS): first slab of this pass within a volume's region
+    int swap;             // k_pass_rel only (round 6): a form-0 pass with 2 or 3 neighbours walked with the roles of i and j exchanged (NL, LL, istep,
+                          // jstep are the exchanged ones): the in-line neighbour and the one on the line before swap places, the third stays
+    int diag, wmax;       // k_pass_rel only (round 6): 1 = the pass is walked along the ANTI-DIAGONALS of (i, j), all lines of a band at the
+                          // same step (form 1 with 2 or 3 neighbours: every neighbour sits on the line before); wmax: hand-off slots per line
+};
+
+// One launch of the pass kernel may aggregate several cost volumes of identical geometry (the
+// left->right and right->left volumes of a stereo pair, consecutive pairs): work items are then (volume, pass,
+// band), and the long dependency chains of one volume's column passes are hidden behind the other
+// volumes' work.
+constexpr int kMaxBatch = 16;
+
+// The reference's pass table, mgm_core.cc:463-471, as data.
+struct RefPass {
+    int d[4][2];
+    int inc_x, inc_y, row_major;
+};
+static const RefPass kPasses[8] = {
+    {{{-1, 0}, {0, -1}, {-1, -1}, {1, -1}}, 1, 1, 1}, {{{1, 0}, {0, 1}, {1, 1}, {-1, 1}}, 0, 0, 1},
+    {{{0, 1}, {-1, 0}, {-1, 1}, {-1, -1}}, 1, 0, 0},  {{{0, -1}, {1, 0}, {1, -1}, {1, 1}}, 0, 1, 0},
+    {{{-1, -1}, {1, -1}, {0, -1}, {1, 0}}, 0, 1, 1},  {{{1, -1}, {1, 1}, {1, 0}, {0, 1}}, 0, 0, 0},
+    {{{1, 1}, {-1, 1}, {0, 1}, {-1, 0}}, 1, 0, 1},    {{{-1, 1}, {-1, -1}, {-1, 0}, {0, -1}}, 1, 1, 0},
+};
+static const int kPassToChannel[4][8] = {  // mgm_core.cc:481-484
+    {0, 1, 2, 3, 4, 5, 6, 7}, {3, 2, 0, 1, 5, 6, 7, 4}, {4, 6, 7, 5, 3, 1, 2, 0}, {5, 7, 4, 6, 1, 2, 0, 3}};
+
+}  // namespace mgm

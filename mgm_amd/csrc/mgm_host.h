@@ -1,6 +1,7 @@
 // mgm_host.h -- host-side internals shared by the translation units behind the C ABI of libmgm_hip.so
-// (mgm_ctx.hip: contexts, device containers, compact cost copies; mgm_plan.hip: the launch plan of the pass kernels and the
-// winner search; mgm_api.hip: cost volumes, aggregation calls, the steps around them).  Nothing here is exported through
+// (mgm_ctx.hip: contexts, device containers, compact cost copies; mgm_planner.h: the launch plan of the pass kernels as pure
+// functions of a request; mgm_plan.hip: the stages of a pass launch around it, the plans' caches and the winner search;
+// mgm_api.hip: cost volumes, aggregation calls, the steps around them).  Nothing here is exported through
 // include/mgm_hip.h; no compute happens on the host and there is no CPU fallback.
 #pragma once
 #include <algorithm>
@@ -13,6 +14,7 @@
 
 #include "../../include/mgm_hip.h"
 #include "mgm_device.h"
+#include "mgm_planner.h"
 
 using namespace mgm;
 
@@ -89,6 +91,33 @@ struct Buf {  // grow-only device scratch
     size_t cap = 0;
 };
 
+// The task tables of earlier launches, by the request they were planned for (mgm_planner.h): request -> (plan, device table).
+// Bounded: the oldest entry is dropped (cache_put, mgm_plan.hip, which synchronises before it frees a buffer).  A caller that
+// launches the passes of a volume one by one alternates between eight of them.
+template <class Req, class Plan>
+struct PlanCache {
+    struct Entry {
+        Req req;
+        Plan plan;  // the decisions; its ticket order and table live on the device only (buf: plan.ntasks items behind the header)
+        Buf buf;
+        unsigned long long fnv;  // FNV-1a of the table's bytes (show_plan)
+    };
+    static constexpr size_t kMaxEntries = 24;
+    std::vector<Entry> entries;
+    const Entry *find(const Req &r) const
+    {
+        for (const Entry &e : entries)
+            if (same_request(e.req, r)) return &e;
+        return nullptr;
+    }
+    void free_all()  // (the caller has synchronised)
+    {
+        for (Entry &e : entries)
+            if (e.buf.p) (void)hipFree(e.buf.p);
+        entries.clear();
+    }
+};
+
 struct Timing {
     const char *name;
     hipEvent_t a, b;
@@ -101,12 +130,10 @@ struct mgm_ctx {
     std::string err;
     // workspace
     Buf exact_mins, exact_scratch;  // slab minima / (FH beyond 8192 labels) convolution arrays of the operand-order-faithful pass kernel
-    Buf lr, hand, hand2, handm, words, tasks, census_u, census_v, dbg, stmp, ones8;  // hand: self-validating slabs (TAGS); hand2: the other kernels' slots
+    Buf lr, hand, hand2, handm, words, census_u, census_v, dbg, stmp, ones8;  // hand: self-validating slabs (TAGS); hand2: the other kernels' slots
     // range-proportional aggregation of ragged volumes (mgm_pass_rel.hip): its Lr volumes [volume][pass][npix][64], hand-off slots,
-    // task table (+ what it was made for), and what the last such aggregation ran on (mgm_wta_windowed_dev searches it again)
-    Buf lr_rel, hand_rel, tasks_rel;
-    std::string tasks_rel_key;
-    int ntasks_rel = 0;
+    // and what the last such aggregation ran on (mgm_wta_windowed_dev searches it again)
+    Buf lr_rel, hand_rel;
     int rel_last_batch = 0, rel_last_ndir = 0;
     int rel_last_slots = 0;  // label slots per pixel of volume 0's copy at that launch (the Lr stride mgm_debug_download_lr reads at)
     long long rel_last_stride = 0;
@@ -133,19 +160,9 @@ struct mgm_ctx {
     size_t ws_limit = 0;  // mgm_ctx_set_workspace_limit: cap on the Lr + hand-off workspace of one pass launch (0 = none)
     int debug_stats = 0;  // MGM_HIP_DEBUG_STATS=1: per-workgroup timing summary of K3 on stderr
     unsigned *h_words = nullptr;  // pinned mirror of the control words
-    // cached task table key
-    int tk_nx = -1, tk_ny = -1, tk_ndir = -1, tk_r = -1;
-    // task tables of earlier launch shapes (a caller that launches the passes of a volume one by one alternates between
-    // eight of them): {nx, ny, key, R} -> device table; `tasks` is the one in use
-    struct TaskTab {
-        int nx, ny, key, R, ntasks;
-        Buf buf;
-        bool one_queue;  // dealt to ONE queue for all XCDs (the plan's simulation preferred it: mgm_plan.hip)
-    };
-    bool tk_one_queue = false;  // ... of the table in use
-    std::vector<TaskTab> ttabs;
+    PlanCache<DenseRequest, DensePlan> dense_plans;  // plans + task tables of the dense kernels' launches, by request
+    PlanCache<RelRequest, RelPlan> rel_plans;        // ... of the range-proportional kernels'
     int force_build = 0;  // 0 auto, 1 first build only (MGM_HIP_PASS_BUILD=1)
-    int ntasks = 0;
     // last aggregate (for mgm_debug_download_lr)
     long long last_nvol = 0;    // floats per volume
     long long last_stride = 0;  // floats between the Lr volumes of consecutive passes (>= last_nvol)
@@ -160,9 +177,10 @@ struct mgm_ctx {
     const mgm_cv *last_cvs[kMaxBatch] = {};  // the volumes of the last aggregation (identity only, never dereferenced) ...
     unsigned long long last_gens[kMaxBatch] = {};  // ... and their generations at that time
     bool pending_check = false;
-    // self-validating hand-off slabs (k_pass2, TAGS): what the region was last cleared for, and the tag of its last launch
-    std::string hand_key;
-    std::string hand_rel_key;      // the range-proportional kernels' slots (same protocol): geometry they were last written for ...
+    // self-validating hand-off slabs (k_pass2, TAGS): the layout the region was last cleared for (npass 0: unknown -- the next
+    // launch clears it), and the tag of its last launch
+    HandLayout hand_key;
+    HandLayout hand_rel_key;       // the range-proportional kernels' slots (same protocol): layout they were last written for ...
     unsigned hand_rel_tag = 0;     // ... and the tag they carry
     unsigned hand_tags[kMaxDirs] = {};  // per pass: the tag its slots carry after its last launch
     int num_cu = 256;  // hipDeviceProp_t::multiProcessorCount
@@ -173,9 +191,7 @@ struct mgm_ctx {
 };
 
 
-constexpr int kR = 16;       // lines per band (waves per workgroup) of the pass kernel
-constexpr int kCtrlWords = 4 + kMaxBatch * kMaxDirs * 4096;  // ticket, err, flag, pad, prog[volume*8 + pass][maxbands]
-constexpr int kMaxBands = 4096;
+constexpr int kCtrlWords = 4 + kMaxBatch * kMaxDirs * kMaxBands;  // ticket, err, flag, pad, prog[volume*8 + pass][maxbands]
 constexpr int kPyrWords = 4;  // behind the control block: the words of mgm_pyramid.hip (minimum / maximum of a coarse map, integer hull)
 
 // Development switches (A/B timing, tests of the fall-back paths), read once per process; everything is on by default.
@@ -242,24 +258,9 @@ struct TimeScope {  // brackets one kernel launch with events when timing is on
     }
 };
 
-// The reference's pass table, mgm_core.cc:463-471, as data.
-struct RefPass {
-    int d[4][2];
-    int inc_x, inc_y, row_major;
-};
-static const RefPass kPasses[8] = {
-    {{{-1, 0}, {0, -1}, {-1, -1}, {1, -1}}, 1, 1, 1}, {{{1, 0}, {0, 1}, {1, 1}, {-1, 1}}, 0, 0, 1},
-    {{{0, 1}, {-1, 0}, {-1, 1}, {-1, -1}}, 1, 0, 0},  {{{0, -1}, {1, 0}, {1, -1}, {1, 1}}, 0, 1, 0},
-    {{{-1, -1}, {1, -1}, {0, -1}, {1, 0}}, 0, 1, 1},  {{{1, -1}, {1, 1}, {1, 0}, {0, 1}}, 0, 0, 0},
-    {{{1, 1}, {-1, 1}, {0, 1}, {-1, 0}}, 1, 0, 1},    {{{-1, 1}, {-1, -1}, {-1, 0}, {0, -1}}, 1, 1, 0},
-};
-static const int kPassToChannel[4][8] = {  // mgm_core.cc:481-484
-    {0, 1, 2, 3, 4, 5, 6, 7}, {3, 2, 0, 1, 5, 6, 7, 4}, {4, 6, 7, 5, 3, 1, 2, 0}, {5, 7, 4, 6, 1, 2, 0, 3}};
-
 int distance_index(const char *n);
 int prefilter_index(const char *n);
 int refinement_index(const char *n);
-bool make_geom(int pass, int nx, int ny, int R, int MGM, bool slope1_ok, PassGeom &g);
 int check_watchdog(mgm_ctx *c, bool block = true);
 
 // pipelined contexts (mgm_ctx_set_pipeline): see mgm_api.hip

@@ -1,0 +1,651 @@
+// mgm_planner.h -- the launch plan of the pass kernels as pure functions: everything a K3 launch is decided by goes in as a
+// request of integers (DenseRequest, RelRequest), everything decided comes out as a plan (the build, the label width, wave
+// sharing, workgroups per CU, deep rings, per-XCD queues, strips, the hand-off layout, the ticket order and the dealt task
+// table).  Plain C++17, standard headers only: no device, no context, no environment -- mgm_plan.hip fills the requests,
+// caches the plans BY the requests and launches; tests/test_planner.py runs the planner on the host.
+#pragma once
+#include <algorithm>
+#include <cstring>
+#include <functional>
+#include <type_traits>
+#include <utility>
+#include <vector>
+
+#include "mgm_geom.h"
+
+namespace mgm {
+
+struct Task {  // ticket -> (volume group * 8 + pass, band + (strip << 16) + (bit 24)); uploaded as int2
+    int x, y;
+};
+
+// Canonical geometry of a pass (see PassGeom).  Returns false if the table
+// entry does not reduce to one of the two canonical neighbour orders.
+inline bool make_geom(int pass, int nx, int ny, int R, int MGM, bool slope1_ok, PassGeom &g)
+{
+    const RefPass &rp = kPasses[pass];
+    const long long sx = rp.inc_x ? 1 : -1, sy = rp.inc_y ? 1 : -1;
+    g.base = (long long)(rp.inc_y ? 0 : ny - 1) * nx + (rp.inc_x ? 0 : nx - 1);
+    if (rp.row_major) {
+        g.NL = ny;
+        g.LL = nx;
+        g.istep = sx;
+        g.jstep = sy * nx;
+    } else {
+        g.NL = nx;
+        g.LL = ny;
+        g.istep = sy * nx;
+        g.jstep = sx;
+    }
+    int kind[4];
+    for (int k = 0; k < 4; k++) {
+        const int dx = rp.d[k][0], dy = rp.d[k][1];
+        const int di = rp.row_major ? dx * (int)sx : dy * (int)sy;
+        const int dj = rp.row_major ? dy * (int)sy : dx * (int)sx;
+        if (di == -1 && dj == 0) kind[k] = 0;        // inline
+        else if (di == 0 && dj == -1) kind[k] = 1;   // same
+        else if (di == -1 && dj == -1) kind[k] = 2;  // back
+        else if (di == 1 && dj == -1) kind[k] = 3;   // fwd
+        else return false;
+        g.wplane[k] = kPassToChannel[k][pass];
+    }
+    if (kind[0] == 0 && kind[1] == 1 && kind[2] == 2 && kind[3] == 3) g.form = 0;
+    else if (kind[0] == 3 && kind[1] == 2 && kind[2] == 1 && kind[3] == 0) g.form = 1;
+    else return false;
+    g.nbands = (g.NL + R - 1) / R;
+    // form 0 sums inline, same, back, fwd: with MGM <= 3 the fwd neighbour (i+1, j-1) is never read,
+    // so a line only has to stay ONE pixel behind the previous one (second K3 build only)
+    g.slope = (slope1_ok && g.form == 0 && MGM <= 3) ? 1 : 2;
+    g.nstrips = 1;
+    g.split = g.LL;
+    g.hand_base = 0;
+    g.diag = 0;
+    g.wmax = 0;
+    g.swap = 0;
+    return true;
+}
+
+// How many per-XCD work queues a launch can use on this device: the XCC ids 0 .. n-1 a 2048-workgroup launch saw
+// (k_xcc_census), if they are exactly that -- 8 on an MI355X in SPX mode, fewer on a partitioned device, 0 = no queues.
+inline int xcc_queues(int mask)
+{
+    int n = 0;
+    while (n < 8 && ((mask >> n) & 1)) n++;
+    return (n >= 2 && mask == (1 << n) - 1) ? n : 0;
+}
+
+// ---- requests: what a plan is a function of, and nothing else ------------------------------------------------------------
+// Integer-only aggregates without padding: two requests are the same plan exactly when their bytes are equal, which is what
+// the contexts' caches compare (mgm_plan.hip).  P1 / P2 are not plan inputs.
+enum { kWeightsNone = 0, kWeightsTwoValued = 1, kWeightsGeneral = 2 };
+struct DenseRequest {
+    int nx, ny, L;             // image, label slots the kernels see (the padded count of a padded launch)
+    int nb, first, count;      // volumes; passes [first, first + count) ...
+    int layout_ndir;           // ... of a hand-off region laid out for the passes [0, layout_ndir)
+    int MGM, fh;               // TSGM neighbours; 1: FH potentials
+    int wmode;                 // kWeights*: none / 1 and one other positive value in every volume / anything else
+    int use_c8, cb;            // compact costs, bytes per cost
+    int first_build, ragged;   // the first build only (forced, or negative penalties); some volume has per-pixel ranges
+    int lines2, lpl, ns;       // what the kernels report: pass2_lines(L * dense_subv(request), use_c8), pass_lpl(L), pass_ns(fh, weighted)
+    int devtools;              // pass2_devtools(): a development build of the pass kernels
+    int num_cu, xcc_mask;      // compute units; XCC ids a launch sees (k_xcc_census; -1: not looked)
+    // development switches and tune values (DevSwitches, MGM_HIP_TUNE)
+    int subv, deep, wg_per_cu, strips, xcdq, xcdq_k, one_queue, w2, oneb;
+};
+struct RelRequest {
+    int nx, ny, NDIR, nb, MGM;
+    int fh, pube, fh2;         // FH potentials; the producer publishes E; update_cost2_trunclinear
+    int slots, cb;             // the volumes' range-proportional format
+    int R, HS;                 // lines per band, floats per hand-off slot (pass_rel_lines, pass_rel_hand_floats)
+    int diag_fits;             // a workgroup with the second hand ring of the anti-diagonal passes fits the LDS (pass_rel_lds_bytes)
+    int num_cu;
+    // tune values: rel_wg 0 = by the launch's shape; rel_prio as resolved by the caller (default 5 for one volume, else 0)
+    int rel_wg, rel_prio, rel_lag, rel_lagd, rel_slots, rel_slope1, rel_swap, rel_diag, rel_strips;
+};
+static_assert(std::has_unique_object_representations_v<DenseRequest>, "DenseRequest: integers only, no padding (compared bytewise)");
+static_assert(std::has_unique_object_representations_v<RelRequest>, "RelRequest: integers only, no padding (compared bytewise)");
+template <class Req>
+inline bool same_request(const Req &a, const Req &b)
+{
+    return memcmp(&a, &b, sizeof(Req)) == 0;
+}
+
+// ---- the hand-off region's layout: what a region of self-validating slots was last cleared for ---------------------------
+// Nothing that differs between launches which share a region: not the passes a launch runs, not its strips, not its weights.
+struct HandLayout {
+    int nx = 0, ny = 0;
+    int npass = 0;        // passes laid out (0: no region known)
+    int groups = 0;       // volume groups
+    int slot_floats = 0;  // floats per slot
+    int slots = 0;        // label slots per pixel of the range-proportional format (0: the dense kernels' region)
+    int R = 0;
+    struct Pass {
+        long long hand_base;
+        int nbands, lines;  // lines: slot lines per band (LL, or 2 * wmax on anti-diagonals)
+        int slope, diag, swap;
+    } pass[kMaxDirs] = {};
+    long long per_group() const { return npass ? pass[npass - 1].hand_base + (long long)pass[npass - 1].nbands * pass[npass - 1].lines : 0; }
+    bool operator==(const HandLayout &o) const
+    {
+        if (nx != o.nx || ny != o.ny || npass != o.npass || groups != o.groups || slot_floats != o.slot_floats || slots != o.slots || R != o.R) return false;
+        for (int q = 0; q < npass; q++) {
+            const Pass &a = pass[q], &b = o.pass[q];
+            if (a.hand_base != b.hand_base || a.nbands != b.nbands || a.lines != b.lines || a.slope != b.slope || a.diag != b.diag || a.swap != b.swap) return false;
+        }
+        return true;
+    }
+    bool operator!=(const HandLayout &o) const { return !(*this == o); }
+};
+// lays the passes [0, npass) out behind each other (sets g[q].hand_base); returns the layout
+inline HandLayout lay_out_hand(PassGeom *g, int npass, int nx, int ny, int groups, int slot_floats, int slots, int R)
+{
+    HandLayout h;
+    h.nx = nx, h.ny = ny, h.npass = npass, h.groups = groups, h.slot_floats = slot_floats, h.slots = slots, h.R = R;
+    long long per_vol = 0;
+    for (int q = 0; q < npass; q++) {
+        g[q].hand_base = per_vol;
+        const int lines = g[q].diag ? 2 * g[q].wmax : g[q].LL;
+        h.pass[q] = HandLayout::Pass{per_vol, g[q].nbands, lines, g[q].slope, g[q].diag, g[q].swap};
+        per_vol += (long long)g[q].nbands * lines;
+    }
+    return h;
+}
+
+// ---- the launch as a list-scheduling problem, simulated ---------------------------------------------------------------
+// A chain = the bands of one pass (or one strip of it) of one volume, band b READY once band b-1 (of both strips) started
+// `skew` steps earlier; `nqueues` queues of `slots` band slots each, band b of chain k belonging to queue
+// (b / QK + k.chain) % nqueues; a free slot starts, among the heads of the chains whose next band belongs to its queue, the
+// ready one with the longest remaining chain (none ready: the one that will be first).  Returns the makespan in steps;
+// `order` = the items by their start in that schedule -- per queue, the order in which the queue hands them out.
+struct SimChain {
+    int x, st, nb, sib, chain;
+    double skew, len;
+    // bands that differ (the anti-diagonal passes of k_pass_rel): band b is ready bskew[b] steps after band b-1 started, runs blen[b]
+    // steps, and brem[b] steps of the chain remain behind its start; empty: skew / len for every band
+    std::vector<double> bskew, blen, brem;
+    double skew_of(int b) const { return bskew.empty() ? skew : bskew[b]; }
+    double len_of(int b) const { return blen.empty() ? len : blen[b]; }
+    double rem_of(int b) const { return brem.empty() ? (double)(nb - 1 - b) * skew + len : brem[b]; }
+    double gap_of(int b) const { return bskew.empty() ? skew : std::min(bskew[b], 4.0); }  // (a band cannot end before its predecessor + this)
+};
+inline double simulate_schedule(const std::vector<SimChain> &chains, int nqueues, int slots, int QK, std::vector<Task> &order)
+{
+    const int n = (int)chains.size();
+    std::vector<std::vector<double>> start(n), end(n);
+    std::vector<int> next(n, 0);
+    size_t total = 0;
+    for (int i = 0; i < n; i++) {
+        start[i].assign(chains[i].nb, 0.0);
+        end[i].assign(chains[i].nb, 0.0);
+        total += (size_t)chains[i].nb;
+    }
+    auto queue_of = [&](int i, int b) { return nqueues <= 1 ? 0 : (b / QK + chains[i].chain) % nqueues; };
+    typedef std::pair<double, int> Slot;  // (free at, queue)
+    std::vector<Slot> heap;
+    for (int q = 0; q < std::max(1, nqueues); q++)
+        for (int k = 0; k < slots; k++) heap.push_back(Slot(0.0, q));
+    std::make_heap(heap.begin(), heap.end(), std::greater<Slot>());
+    order.clear();
+    const double INF = 1e300;
+    double makespan = 0.0;
+    size_t guard = 0;
+    while (order.size() < total && !heap.empty() && guard++ < 64 * total + 4096) {
+        std::pop_heap(heap.begin(), heap.end(), std::greater<Slot>());
+        const Slot sl = heap.back();
+        heap.pop_back();
+        const double t = sl.first;
+        int best = -1;
+        double best_rem = -1, best_ready = INF;
+        bool best_is_ready = false, later = false;
+        for (int i = 0; i < n; i++) {
+            const SimChain &k = chains[i];
+            if (next[i] >= k.nb) continue;
+            const int b = next[i];
+            if (queue_of(i, b) != sl.second) {
+                for (int bb = b + 1; bb < k.nb && !later; bb += std::max(1, QK)) later = queue_of(i, bb) == sl.second;
+                continue;
+            }
+            double ready = 0.0;
+            if (b > 0) {
+                ready = start[i][b - 1] + k.skew_of(b);
+                if (k.sib >= 0) ready = next[k.sib] > b - 1 ? std::max(ready, start[k.sib][b - 1] + k.skew) : INF;
+            }
+            const double rem = k.rem_of(b);
+            const bool is_ready = ready <= t;
+            const bool better = best < 0 || (is_ready != best_is_ready ? is_ready : (is_ready ? rem > best_rem : (ready != best_ready ? ready < best_ready : rem > best_rem)));
+            if (better) best = i, best_rem = rem, best_ready = ready, best_is_ready = is_ready;
+        }
+        if (best < 0 || best_ready >= INF) {
+            // nothing of this queue can start yet (its next bands follow bands of other queues, or the other strip): look again
+            // when the next slot frees; a queue with nothing left retires its slots
+            if (best < 0 && !later) continue;
+            const double again = heap.empty() ? t + 1.0 : std::max(t, heap.front().first) + 1.0;
+            heap.push_back(Slot(again, sl.second));
+            std::push_heap(heap.begin(), heap.end(), std::greater<Slot>());
+            continue;
+        }
+        const SimChain &k = chains[best];
+        const int b = next[best]++;
+        const double st_eff = std::max(t, best_ready);
+        double en = st_eff + k.len_of(b);
+        if (b > 0) en = std::max(en, end[best][b - 1] + k.gap_of(b));  // (it cannot overtake its predecessor)
+        start[best][b] = st_eff;
+        end[best][b] = en;
+        makespan = std::max(makespan, en);
+        heap.push_back(Slot(en, sl.second));
+        std::push_heap(heap.begin(), heap.end(), std::greater<Slot>());
+        order.push_back(Task{k.x, b + (k.st << 16)});
+    }
+    if (order.size() < total) {  // (cannot happen; never lose an item to the model)
+        for (int i = 0; i < n; i++)
+            for (int b = next[i]; b < chains[i].nb; b++) order.push_back(Task{chains[i].x, b + (chains[i].st << 16)});
+        makespan = INF;
+    }
+    return makespan;
+}
+
+// The chains of a launch: every (volume group, pass, strip) of the passes [first, first + count).  What the MODEL assumes per
+// band -- the two planners differ in it, not in the construction: a band trails the one before it by slope x lines + a lag
+// (by the slope of the pass), walks its lines + `len_extra` steps, and on the anti-diagonals of k_pass_rel (g.diag) is ready
+// `diag_lag` steps + the shift of its first line after the band before it.
+struct ChainModel {
+    double lag_slope1, lag_slope2, len_extra, diag_lag;
+};
+inline std::vector<SimChain> make_chains(const PassGeom *geoms, int ngroups, int first, int count, int R, const ChainModel &m)
+{
+    std::vector<SimChain> ch;
+    for (int v = 0; v < ngroups; v++)
+        for (int q = first; q < first + count; q++)
+            for (int st = 0; st < geoms[q].nstrips; st++) {
+                const PassGeom &g = geoms[q];
+                SimChain k;
+                k.x = v * kMaxDirs + q, k.st = st, k.nb = g.nbands, k.chain = v * count + (q - first);
+                k.sib = g.nstrips == 2 ? (int)ch.size() + (st == 0 ? 1 : -1) : -1;  // (a band waits for BOTH strips of the band before it)
+                k.skew = (double)g.slope * R + (g.slope == 1 ? m.lag_slope1 : m.lag_slope2);
+                k.len = (g.nstrips == 2 ? (st == 0 ? g.split : g.LL - g.split) + R - 1 : g.LL) + (double)g.slope * (R - 1) + m.len_extra;
+                if (g.diag) {  // band b walks lines [lo_b, hi_b] of the pass, one step behind band b - 1 (+ the lag)
+                    auto lo = [&](int b) { return std::max(0, b * R - g.LL + 1); };
+                    auto hi = [&](int b) { return std::min(g.NL - 1, b * R + R - 1); };
+                    k.bskew.assign(g.nbands, 0.0), k.blen.assign(g.nbands, 0.0), k.brem.assign(g.nbands, 0.0);
+                    for (int b = 0; b < g.nbands; b++) {
+                        k.bskew[b] = b > 0 ? (double)(lo(b) - lo(b - 1)) + m.diag_lag : 0.0;
+                        k.blen[b] = (double)(hi(b) - lo(b)) + 2.0;
+                    }
+                    for (int b = g.nbands - 1; b >= 0; b--) k.brem[b] = b == g.nbands - 1 ? k.blen[b] : std::max(k.blen[b], k.bskew[b + 1] + k.brem[b + 1]);
+                }
+                ch.push_back(k);
+            }
+    return ch;
+}
+
+// ---- the dense kernels (k_pass / k_pass2) --------------------------------------------------------------------------------
+enum { kPlanOk = 0, kPlanNotCanonical = 1, kPlanTooManyBands = 2, kPlanLostQueues = 3 };
+struct DensePlan {
+    int err = kPlanOk;
+    // the decisions
+    int subv = 1, ngroups = 0, Lk = 0;  // volumes per wave, volume groups, label slots of a wave
+    int R2 = 0, R = 0;                  // lines per band of the second build (0: the first build runs), of the launch
+    int w2 = 0, wk = 0;                 // the two-valued weights' kernels; the general weighted kernels
+    int tags = 0, NS = 1, LPk = 0;      // self-validating hand-off slots; slabs per slot; floats per slot of that protocol
+    int wg_per_cu = 1, deep = 0, oneb = 0;
+    int xcdq = 0, nq = 8, QK = 1 << 20, one_queue = 0;
+    int any_strips = 0;
+    int maxLL = 0;
+    double load_ratio = 0;        // band-steps per CU over the longest chain of the launch
+    double t_one = 0, t_q = 0;    // simulated makespans (steps): one queue, the per-XCD queues
+    PassGeom g[kMaxDirs] = {};
+    long long hand_vstride = 0;
+    HandLayout hand;              // (tags only)
+    std::vector<Task> order;      // the global ticket order
+    std::vector<Task> table;      // as uploaded: the eight queues' (first ticket, count), then the items (bit 24: plain hand-off)
+    int ntasks = 0;
+};
+
+// 128 / 64 labels: 2 / 4 volumes of the launch share every wave of the 256-label kernels (k_pass2<..., SUBV>) -- a
+// step is mostly fixed cost, so it may as well serve several volumes.  Compact costs, no weights, not FH with
+// TSGM = 2 (whose slabs travel with their minimum), and a volume count that divides.
+// Only from two such groups on, though: sharing a wave halves the band-steps but makes every step the longer step of
+// the 256-label kernels, and a launch of one group is bound by its chain of bands, i.e. by the step (round 3,
+// 1920x1080x128 x 2: K3 3.74 ms sharing, 3.11 ms as two plain work items; x 4: the same either way).
+// (reads nothing of the request that depends on it: the caller asks before it fills `lines2`)
+inline int dense_subv(const DenseRequest &q)
+{
+    if (!q.first_build && q.use_c8 && q.cb == 1 && q.wmode == kWeightsNone && !(q.fh && q.MGM == 2) && (q.L == 128 || q.L == 64) && q.nb % (256 / q.L) == 0 &&
+        (q.subv == 2 || (q.subv == 1 && q.nb / (256 / q.L) >= 2)))
+        return 256 / q.L;
+    return 1;
+}
+
+// longest remaining chain first: item (p, b) is followed, band after band, by (nbands - 1 - b) hand-offs of slope * R + lag
+// steps and its own walk.  A valid order by itself (within a pass the remaining chain shrinks with b): what a launch takes
+// when the simulation gives up.
+inline std::vector<Task> order_by_remaining_chain(const PassGeom *geoms, int ngroups, int first, int count, int R, double lag)
+{
+    std::vector<Task> tasks;
+    for (int v = 0; v < ngroups; v++)
+        for (int q = first; q < first + count; q++)
+            for (int b = 0; b < geoms[q].nbands; b++)
+                for (int st = 0; st < geoms[q].nstrips; st++) tasks.push_back(Task{v * kMaxDirs + q, b + (st << 16)});
+    auto rem = [&](const Task &t) {
+        const PassGeom &g = geoms[t.x % kMaxDirs];
+        const int b = t.y & 0xffff, st = (t.y >> 16) & 0xff;
+        const double walk = (g.nstrips == 2 ? (st == 0 ? g.split : g.LL - g.split) + R - 1 : g.LL) + (double)g.slope * R;
+        return (double)(g.nbands - 1 - b) * (g.slope * R + lag) + walk;
+    };
+    std::stable_sort(tasks.begin(), tasks.end(), [&](const Task &a, const Task &b) {
+        const double ra = rem(a), rb = rem(b);
+        return ra != rb ? ra > rb : a.x < b.x;
+    });
+    return tasks;
+}
+
+inline DensePlan plan_dense(const DenseRequest &q)
+{
+    DensePlan p;
+    const int nx = q.nx, ny = q.ny, L = q.L, nb = q.nb, first = q.first, count = q.count, MGM = q.MGM, PEND = first + count;
+    const bool fh = q.fh != 0, weighted = q.wmode != kWeightsNone, use_c8 = q.use_c8 != 0, first_build = q.first_build != 0;
+    const int lpl = q.lpl, LP = lpl * 64;
+    // (768 / 1024 labels with weights that are not two-valued-and-narrow: the weighted kernels of the second build stop at
+    // 512 labels -- two slabs per slot do not fit the LDS beyond -- so those take the first build, which has no compact costs)
+    const bool wide_weighted = weighted && lpl > 8;
+    // second build (LDS-DMA loaders) whenever the slabs are whole DMA pieces
+    const int subv = p.subv = dense_subv(q);
+    const int ngroups = p.ngroups = nb / subv;  // work items address groups of `subv` volumes
+    const int Lk = p.Lk = L * subv;             // label slots of a wave
+    const int R2 = p.R2 = (first_build || wide_weighted) ? 0 : q.lines2;
+    const int R = p.R = R2 ? R2 : (lpl > 8 ? 4 : kR);  // (more than 512 labels: the first build with bands of four lines)
+    int maxLL = 0, maxbands = 0;
+    for (int k = 0; k < std::max(PEND, q.layout_ndir); k++) {
+        if (!make_geom(k, nx, ny, R, MGM, R2 != 0, p.g[k])) return p.err = kPlanNotCanonical, p;
+        maxLL = std::max(maxLL, p.g[k].LL);
+        maxbands = std::max(maxbands, p.g[k].nbands);
+    }
+    p.maxLL = maxLL;
+    if (maxbands > kMaxBands) return p.err = kPlanTooManyBands, p;
+    // Two-valued weights (k_pass2, W2): the compact kernels with deep rings and per-XCD queues, every volume's weights 1 and
+    // one other positive value.  Anything they do not cover -- fp32 costs, more than 256 labels, launches too small for the
+    // queues, a partitioned device, FH on ragged volumes (which borrows the weighted kernels) -- keeps the general
+    // weighted kernels.
+    // (FH on a ragged volume WITH two-valued weights as well: the producer-side transforms of W2 convolve over the SENDING pixel's
+    // slab -- found by the long random campaign of tests/test_gpu_rel.py in round 5, where the range-proportional kernels and the
+    // reference agreed and this path did not)
+    bool w2 = q.wmode == kWeightsTwoValued && q.w2 && R2 && use_c8 && q.cb == 1 && lpl <= 4 && !(fh && q.ragged) && !q.devtools && q.xcdq != 0 && q.deep != 0;
+    if (w2) {
+        int items = 0;
+        for (int k = first; k < PEND; k++) items += nb * p.g[k].nbands;
+        w2 = items >= 32;
+    }
+    w2 = w2 && xcc_queues(q.xcc_mask) > 0;
+    const bool wk = weighted && !w2;  // the general weighted kernels (consumer-side transforms, progress words)
+    p.w2 = w2, p.wk = wk;
+    p.NS = w2 ? 2 : q.ns;
+    const int LPk = p.LPk = (subv > 1 ? Lk : LP) * (w2 ? 2 : 1);  // floats per hand-off slot of the self-validating protocol
+    // The second build's unweighted kernels hand slabs from band to band that validate themselves (mgm_pass2.hip, TAGS):
+    // one slot per (volume, pass, band, pixel), written once per launch OF THAT PASS with the tag in the sign bits.  The
+    // region is laid out for the passes [0, layout_ndir) and is this protocol's alone, so neither a caller that launches
+    // the passes one by one nor one that alternates weighted and unweighted runs makes it be cleared again (mgm_plan.hip).
+    const bool tags = R2 && !wk && (w2 || !(fh && MGM == 2));
+    p.tags = tags;
+    if (tags) {
+        p.hand = lay_out_hand(p.g, q.layout_ndir, nx, ny, ngroups, LPk, 0, R);
+        p.hand_vstride = p.hand.per_group();
+    }
+
+    double load_ratio = 0;  // band-steps per CU over the longest chain of the launch
+    {
+        // Two bands per CU pay when the launch is bound by throughput, not by the longest chain of bands: compare the
+        // band-steps one CU has to run with the critical path of the slowest pass (steps of slope*lines + line length
+        // + the hand-off lag per band: ~3 steps with self-validating slabs, ~10 with progress words).  Measured on
+        // 1920x1080 (round 2, after the hand-off rewrite): the FH kernels -- long dependent instruction chains per step --
+        // gain from the second band from a ratio of ~1.8 on (three cfg3 volumes per launch; 12 volumes: 64 -> 51 ms); the
+        // Hirschmueller kernels only at large batches of 256 labels (+3 % at 12 volumes), and lose 3-10 % at 128 labels
+        // or small batches: their steps are short enough for one band to keep the CU's issue slots busy.
+        double work = 0, chain = 0;
+        const double lag = tags ? 3.0 : 10.0;
+        for (int k = first; k < PEND; k++) {
+            const PassGeom &g = p.g[k];
+            work += (double)ngroups * g.nbands * (g.LL + g.slope * R);
+            chain = std::max(chain, (double)g.slope * g.NL + g.LL + lag * g.nbands);
+        }
+        // (round 3, with the XCD queues: two 256-label FH volumes, ratio 1.66, K3 10.29 -> 9.93 ms with the second band; one
+        // volume -- 0.83 -- loses 20 % with it: the FH threshold moved from 1.8 to 1.5)
+        p.wg_per_cu = (work / (double)q.num_cu > (fh ? 1.5 : 8.0) * chain) ? 2 : 1;
+        load_ratio = work / (double)q.num_cu / chain;
+        // Deep DMA rings (k_pass2, DEEP) for every compact unweighted launch: same-process A/B runs of round 3
+        // (tools/ab_env.sh, shallow -> deep) give -13 % of K3 for one 128-label volume, -15 % at 4096x4096x192, -3 % for
+        // one or two 256-label FH volumes, -3 % for 8 or 16 128-label volumes, and 0..-1 % for twelve 256-label ones.
+        p.deep = (tags && use_c8) ? 1 : 0;
+    }
+    p.load_ratio = load_ratio;
+    if (q.deep >= 0) p.deep = (tags && use_c8 && q.deep) ? 1 : 0;
+    if (q.wg_per_cu) p.wg_per_cu = q.wg_per_cu;
+    // Per-XCD work queues (k_pass2, XCDQ): launches in which the chains of bands matter.  The workgroups stay and work a
+    // queue off (a band that follows another on a CU starts at once instead of waiting for a workgroup to be dispatched),
+    // and most hand-offs stay inside an XCD's L2.  Same-box A/B runs (round 3, 1920x1080, K3 without -> with queues):
+    // 256 labels FH x 1 6.9 -> 6.4 ms, x 2 11.0 -> 10.3, x 3 14.6 -> 13.9, x 4 18.6 -> 17.8, x 6 and x 12 (load/chain 5
+    // and 10) 0 .. +1 %; Hirschmueller x 1 5.4 -> 4.85, x 2 8.6 -> 8.15; 128 labels x 1 2.38 -> 2.07, x 3 4.40 -> 4.24;
+    // 4096x4096x192 x 1 +-0, x 2 (load/chain 5.4) +1 %.  One queue for all XCDs (MGM_HIP_XCDQ=2: the staying workgroups
+    // alone) gives 6.5, 5.2 and 2.08 ms for the three single volumes, 16.3 instead of 15.3 for three 256-label ones.
+    // Needs all eight XCC ids to show up in a launch (a partitioned device shows fewer), and a launch large enough for
+    // the dispatcher's round robin to have put several workgroups on every XCD: a queue is only worked off by
+    // workgroups that find themselves on its XCD -- a small launch keeps the single ticket counter.
+    bool xcdq = false;
+    int nitems = 0;  // work items of the launch (before strips) = its workgroups
+    for (int k = first; k < PEND; k++) nitems += ngroups * p.g[k].nbands;
+    // Hirschmueller potentials (short steps: the second band per CU never gave them more than 3 %): with the queues, ONE band per
+    // CU is the better schedule at every batch size -- same-box A/B runs of 256-label volumes, two bands per CU without
+    // queues -> one with: x 8 0.964 -> 0.985 of the roofline, x 12 0.957 -> 0.981 (K3 46.9 -> 44.9 ms); 4096x4096x192 x 2 +-0 --,
+    // so they take the queues whatever the load; the FH kernels, which need the second band from a load/chain of 1.5 on,
+    // below a load/chain of 4.
+    const bool always_q = !fh;
+    if (tags && p.deep && subv == 1 && R2 && nitems >= 32 && !q.devtools && (w2 || q.xcdq >= 1 || (q.xcdq < 0 && (always_q || load_ratio < 4.0))))
+        xcdq = xcc_queues(q.xcc_mask) > 0;
+    const int nq = p.nq = xcdq ? xcc_queues(q.xcc_mask) : 8;  // queues of the launch (the XCDs of the device)
+    if (xcdq && always_q && !q.wg_per_cu) p.wg_per_cu = 1;
+    if (w2) {
+        if (!xcdq || !p.deep) return p.err = kPlanLostQueues, p;
+        p.wg_per_cu = 1;  // (two slabs per slot: one band per CU)
+    }
+    p.xcdq = xcdq;
+    p.oneb = (xcdq && p.wg_per_cu < 2 && q.oneb) ? 1 : 0;
+    // Two strips per line: the passes without an in-line dependency -- form 1 with 2 or 3 neighbours -- walk their lines
+    // from both image edges inwards (mgm_pass2.hip): half the line length in the critical path of a pass, bands that
+    // live half as long, for twice the work items, each with its own pipeline ramp and hand-off lag (and 1-2 % of the
+    // pixels of such a pass computed twice).  Round 3, same-box A/B runs:
+    //   * with the deep rings alone the strips LOSE on whole volumes (strips -> none, 1920x1080: 256 labels x 1 K3 7.60 ->
+    //     7.21 ms FH, 5.42 -> 5.15 Hirschmueller; 4096x4096x192 27.5 -> 26.2; two or three volumes -2..-5 % too) and win
+    //     where a launch runs only a FEW passes of one volume (a rank of a direction-sharded run; 4096x4096x192,
+    //     tools/time_passes.py, none -> strips: one pass 8.8 -> 7.8-8.0 ms, two 10.7 -> 9.7, four 15.5 -> 14.9-15.2);
+    //   * with the XCD queues -- a finished strip's successor starts at once -- they win wherever the chains dominate
+    //     (none -> strips, 1920x1080x256: FH x 1 6.47 -> 6.18, x 2 10.25 -> 10.0, x 3 14.0 -> 13.5 but x 4 17.7 -> 18.1;
+    //     Hirschmueller x 1 4.85 -> 4.70, x 2 and x 3 +-0; 4096x4096x192 x 1 (load/chain 2.7) 26.5 -> 27.0, x 2 50.9 -> 52.6;
+    //     a rank's four passes of 4096x4096x192 9.6 -> 8.4 with queues and strips together): on below a load/chain of 2.
+    bool any_strips = false;
+    if (tags && !w2 && (q.strips == 1 || (q.strips < 0 && ((ngroups == 1 && count <= 4 && p.wg_per_cu == 1) || (xcdq && load_ratio < 2.0)))))
+        for (int k = first; k < PEND; k++)
+            if (p.g[k].form == 1 && (MGM == 2 || MGM == 3) && p.g[k].LL >= 8 * R) {
+                p.g[k].nstrips = 2;
+                p.g[k].split = p.g[k].LL / 2;
+                any_strips = true;
+            }
+    p.any_strips = any_strips;
+    // bands per queue block: a pass stays on one XCD when the passes of the launch fill the eight queues evenly; otherwise
+    // blocks of two bands, which spread four or twelve passes over all XCDs at the price of every second hand-off
+    // crossing.
+    // Measured (K3, block 0 / 1 / 2, no queues): 1920x1080x256 FH x 2 10.2 / 10.9 / 11.3 (11.4), x 3 14.2 / 15.5 / 15.5 (16.5),
+    // x 4 17.7 / 18.4 / 17.9 (19.1); Hirschmueller x 3 13.0 / 13.35 / 13.4 (13.5); 128 labels x 1 (four passes) 2.85 / 2.08 /
+    // 2.07 (2.35); 4096x4096x192 x 1 27.2 / 27.5 / 26.4 (27.65) -- lines that long keep far more bands in flight than an
+    // XCD has CUs, and a pinned pass that takes longer than the others leaves the other XCDs idle at the end.
+    int QK = ((ngroups * count) % nq == 0 && maxLL <= 3000) ? 0 : 2;
+    if (q.xcdq_k >= 0) QK = q.xcdq_k;
+    if (QK <= 0) QK = 1 << 20;
+    p.QK = QK;
+
+    // task table: ticket -> (pass, band [, strip]); item (p, b, .) always follows the items (p, b-1, .)
+    // LIST SCHEDULING, simulated (simulate_schedule, above): the tickets come out in the order in which a machine of
+    // band slots that always starts, among the items whose predecessor band is far enough ahead (READY), the one with
+    // the longest remaining chain would start them.  The launch then follows that schedule by itself -- every free
+    // workgroup takes the next ticket of its queue -- as far as its step times match the model's (one step = one time
+    // unit for every pass), and an item taken early merely waits, as it always could.  What a plain
+    // longest-remaining-chain order gets wrong is the START of the launch: it hands the first 256 tickets to some sixty
+    // consecutive bands of the two longest chains, of which band k cannot move before k * (slope * R) steps have
+    // passed (timeline, round 5: 43 % of the CUs waiting through the first millisecond; before that, rounds 1-4 dealt by
+    // relative progress b / nbands and left 14-24 % of a single launch's CU-time as tail: docs/experiments.md).
+    // The same simulation DECIDES between the per-XCD queues and one queue for all XCDs (write-through hand-offs
+    // everywhere): a pass pinned to an XCD runs in whole rounds of that XCD's 32 CUs -- 72 row bands of 2.3 ms are three
+    // rounds, the last one a quarter full (1920x1080x256 FH x 1, K3: pinned 6.08 ms, one queue 5.76; two volumes, two
+    // passes per XCD: 10.25 against 11.04) -- so the plan takes the single queue where its simulated makespan is
+    // shorter by more than what the crossing hand-offs cost (4 %).
+    const double lagS = tags ? 5.0 : 12.0;
+    const std::vector<SimChain> ch = make_chains(p.g, ngroups, first, count, R, ChainModel{lagS, lagS, 3.0, 0.0});
+    size_t total = 0;
+    for (const SimChain &k : ch) total += (size_t)k.nb;
+    const int slots = std::max(1, q.num_cu * std::max(1, p.wg_per_cu));
+    std::vector<Task> ord_one, ord_q;
+    const double t_one = simulate_schedule(ch, 1, slots, 1 << 20, ord_one);
+    double t_q = t_one;
+    if (xcdq) t_q = simulate_schedule(ch, nq, std::max(1, slots / nq), QK, ord_q);
+    const int forced = q.one_queue;
+    // (launches that run two bands per CU keep their queues: with the doubled step the pinned dealing measured 5 % FASTER
+    // for two and four 256-label FH volumes although the model says otherwise -- 9.67 against 10.18 ms, 17.7 against 18.3)
+    const bool one_queue = xcdq && (q.xcdq == 2 || forced > 0 || (forced < 0 && p.wg_per_cu < 2 && t_one * 1.04 < t_q));
+    const bool sim_ok = ((xcdq && !one_queue) ? t_q : t_one) < 1e299 && ((xcdq && !one_queue) ? ord_q : ord_one).size() == total;
+    // (never seen: the simulation gave up.  Its leftovers are NOT a valid order -- a strip's band would precede the
+    // other strip's band before it -- so the launch takes the sorted order: longest remaining chain first, which is one)
+    if (sim_ok) p.order = (xcdq && !one_queue) ? ord_q : ord_one;
+    else p.order = order_by_remaining_chain(p.g, ngroups, first, count, R, tags ? 3.0 : 10.0);
+    p.one_queue = one_queue, p.t_one = t_one, p.t_q = t_q;
+    p.ntasks = (int)p.order.size();
+
+    // The table's header: the eight XCD queues (first ticket, count).  xcdq: the sorted items are dealt to the queues
+    // in blocks of QK consecutive bands of a pass, consecutive blocks to consecutive queues, the passes staggered;
+    // every queue keeps the global order (what the progress argument of k_pass2 rests on), and an item whose
+    // successor band sits in the same queue is marked for a plain hand-off (bit 24).
+    p.table.assign(8, Task{0, 0});
+    if (xcdq) {
+        std::vector<Task> qs[8];
+        for (const Task &t : p.order) {
+            const int v = t.x / kMaxDirs, k = t.x % kMaxDirs, b = t.y & 0xffff;
+            const int chain = v * count + (k - first);
+            const bool same = b + 1 < p.g[k].nbands && (b + 1) / QK == b / QK;
+            if (one_queue) qs[0].push_back(t);  // (one queue for all XCDs, write-through hand-offs)
+            else qs[(b / QK + chain) % nq].push_back(Task{t.x, t.y | (same ? 1 << 24 : 0)});
+        }
+        int at = 0;
+        for (int k = 0; k < 8; k++) {
+            p.table[k] = Task{at, (int)qs[k].size()};
+            at += (int)qs[k].size();
+            p.table.insert(p.table.end(), qs[k].begin(), qs[k].end());
+        }
+    } else
+        p.table.insert(p.table.end(), p.order.begin(), p.order.end());
+    return p;
+}
+
+// ---- the range-proportional kernels (k_pass_rel) -------------------------------------------------------------------------
+struct RelPlan {
+    int err = kPlanOk;
+    int rel_wg = 1;    // workgroups (4 compute waves + the loader) per CU
+    int diag_any = 0;  // some pass walks anti-diagonals
+    int swapmask = 0;  // the passes walked with exchanged roles
+    int maxLL = 0;
+    PassGeom g[kMaxDirs] = {};
+    long long hand_vstride = 0;
+    HandLayout hand;
+    std::vector<Task> order;  // the global ticket order
+    std::vector<Task> table;  // as uploaded: the order, bit 24 = issue priority
+    int ntasks = 0;
+};
+
+// the chains of a range-proportional launch as the planner's model has them (`g`: the plan's geometry)
+inline std::vector<SimChain> rel_chains(const RelRequest &q, const PassGeom *g)
+{
+    return make_chains(g, q.nb, 0, q.NDIR, q.R, ChainModel{1.0 + (double)q.rel_lag, 2.0 + (double)q.rel_lag, 1.0, 7.0 + (double)q.rel_lagd});
+}
+
+inline RelPlan plan_rel(const RelRequest &q)
+{
+    RelPlan p;
+    const int nx = q.nx, ny = q.ny, NDIR = q.NDIR, nb = q.nb, MGM = q.MGM, R = q.R;
+    const bool fh = q.fh != 0;
+    int maxLL = 0, maxbands = 0;
+    for (int k = 0; k < NDIR; k++) {
+        // (round 6) form-0 passes with TSGM <= 3 walk slope 1 (make_geom decides; tune rel_slope1=0: slope 2 everywhere, as in round 5)
+        if (!make_geom(k, nx, ny, R, MGM, q.rel_slope1 != 0, p.g[k])) return p.err = kPlanNotCanonical, p;
+        maxLL = std::max(maxLL, p.g[k].LL);
+        maxbands = std::max(maxbands, p.g[k].nbands);
+        // (round 6) two strips per line for the form-1 passes: no pixel of those passes depends on its own line with TSGM <= 3, so the
+        // two halves of a band's lines are two work items (k_pass_rel).  Measured, 1920x1080, windows of 49 labels: FH x 1 8.91 -> 8.12 ms,
+        // x 4 13.33 -> 12.89; Hirschmueller x 1 6.13 -> 5.53 (tune rel_strips=0: none)
+        // (round 6, later) ... and better: those passes ACROSS their lines, bands of anti-diagonals in lock step (k_pass_rel, g.diag) -- the
+        // chain of a pass is NL + bands x lag steps instead of 2 NL + LL / 2 + bands x lag.  Two hand-off lines per band and a second hand
+        // ring in LDS: where that does not fit (the three-slab entries of 128 slots with two-byte costs) the strips stay.  tune rel_diag=0: strips
+        // (round 6, last) form-0 passes with TSGM <= 3 and more lines than pixels per line (the column passes of a landscape image) are walked
+        // with the roles of i and j exchanged: (i - 1, j), (i, j - 1), (i - 1, j - 1) is symmetric in them, the depth NL + LL stays, but a band
+        // trails the band before it by ~2 x 16 steps in practice (the pace of a chain is that of its slowest band), so FEWER bands of longer
+        // lines end sooner: 68 x D + 1920 against 120 x D + 1080.  tune rel_swap=0: none
+        // (FH x 1 5.73 -> 5.27 ms, x 2 7.34 -> 7.04, windows of 101 labels 8.58 -> 7.9, x 4 unchanged; the short steps of the Hirschmueller launches lose
+        // 1-2 % with it -- 4.17 / 5.03 / 8.05 -> 4.19 / 5.16 / 8.16 -- and keep their walks: rel_swap=2 forces it there too)
+        if ((q.rel_swap >= 2 || (q.rel_swap == 1 && fh)) && p.g[k].form == 0 && MGM <= 3 && p.g[k].slope == 1 && p.g[k].NL > p.g[k].LL) {
+            PassGeom &g = p.g[k];
+            std::swap(g.NL, g.LL);
+            std::swap(g.istep, g.jstep);
+            g.swap = 1;
+            p.swapmask |= 1 << k;
+            g.nbands = (g.NL + R - 1) / R;
+            g.split = g.LL;
+            maxLL = std::max(maxLL, g.LL);
+        }
+        const bool diag_ok = q.rel_diag != 0 && p.g[k].form == 1 && MGM <= 3 && q.diag_fits;
+        if (diag_ok) {
+            PassGeom &g = p.g[k];
+            g.diag = 1;
+            g.slope = 0;
+            g.nbands = (g.NL + g.LL - 1 + R - 1) / R;
+            g.wmax = std::min(g.NL, g.LL + R);
+            p.diag_any = 1;
+        } else if (q.rel_strips != 0 && p.g[k].form == 1 && MGM <= 3 && p.g[k].LL >= 8 * R) {
+            p.g[k].nstrips = 2;
+            p.g[k].split = p.g[k].LL / 2;
+        }
+        maxbands = std::max(maxbands, p.g[k].nbands);
+    }
+    p.maxLL = maxLL;
+    if (maxbands > kMaxBands) return p.err = kPlanTooManyBands, p;
+    // self-validating hand-off slots, one per (volume, pass, band, pixel): written once per launch with the launch's tag (see
+    // k_pass_rel); another geometry clears the region (all-ones words) and starts again with tag 0
+    p.hand = lay_out_hand(p.g, NDIR, nx, ny, nb, q.HS, q.slots, R);
+    p.hand_vstride = p.hand.per_group();
+    // workgroups (4 compute waves + the loader) per CU: tune rel_wg forces it
+    // (measured, round 6, 1920x1080 windows of 49 labels, FH with the side-by-side convolutions: x 1 7.87 / 8.20 / 8.53 ms at 1 / 2 / 3 per CU,
+    // x 2 13.0 / 8.6 / 9.6, x 4 24.3 / 14.1 / 12.9; Hirschmueller the same order)
+    // (with the anti-diagonal passes a single launch is no longer one long chain: x 1 6.89 / 6.32 / 6.47 ms at 1 / 2 / 3, x 2 11.5 / 7.82 / 7.76,
+    // x 4 22.0 / 13.0 / 12.3; Hirschmueller x 1 5.45 / 4.62 / 4.36)
+    const int rel_wg = p.rel_wg = q.rel_wg > 0 ? std::min(q.rel_wg, 6) : (nb <= 1 ? (fh ? 2 : 3) : 3);
+    // the task table: the simulated list schedule of the launch (one ticket counter)
+    // (slope of the lock-step diagonal x lines + the lag the MODEL assumes per band.  The tickets are the start order of the
+    // simulated schedule, so these constants decide who holds a band slot while it waits: with the hand-off's real ~4 steps on
+    // every chain, the anti-diagonal bands -- ready every few steps -- took the first 400 of 512 slots and sat in them.  Measured
+    // (tools/ab_rel_lag.sh): 1-2 steps on the line walks, 7 on the anti-diagonals: x 1 6.15 -> 5.72 ms, Hirschmueller x 2 5.42 -> 5.0,
+    // windows of 101 labels 9.09 -> 8.5, four volumes unchanged; tune rel_lag / rel_lagd: added to them)
+    const std::vector<SimChain> ch = rel_chains(q, p.g);
+    (void)simulate_schedule(ch, 1, std::max(1, (int)((long long)(q.num_cu * rel_wg) * q.rel_slots / 100)), 1 << 20, p.order);
+    p.table = p.order;
+    // workgroups that share a CU slow each other down (a step of 1.07 us becomes ~1.5): the bands of the longest chains -- what the
+    // launch ends with -- get the issue priority (bit 24 of the task word; tune rel_prio=0: none, =100: every chain within x % of the longest)
+    {
+        const double pct = (double)q.rel_prio;  // (x 1 6.25 -> 6.03 ms, Hirschmueller 4.36 -> 4.22; x 4 12.3 -> 12.4: not there)
+        double longest = 0.0;
+        for (const SimChain &k : ch) longest = std::max(longest, k.rem_of(0));
+        for (Task &t : p.table)
+            for (const SimChain &k : ch)
+                if (k.x == t.x && k.st == ((t.y >> 16) & 0xff)) {
+                    if (pct > 0.0 && k.rem_of(0) >= longest * (1.0 - pct / 100.0) && rel_wg > 1) t.y |= 1 << 24;
+                    break;
+                }
+    }
+    p.ntasks = (int)p.table.size();
+    return p;
+}
+
+}  // namespace mgm

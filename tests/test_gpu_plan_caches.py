@@ -1,12 +1,15 @@
 """The planner's per-context caches, one fixed A, B, A, B sequence each on ONE context, every step against the oracle.
 
-A context keeps four objects from launch to launch (mgm_amd/csrc/mgm_plan.hip), each behind a key built from some of what
-it was made of:
-  * the dense hand-off region with its per-pass sign-bit tags (run_passes, `hand_key`);
-  * the dense task tables, up to 24 of them (`ttabs`, keyed on shape, `tk_key` and the band height; the oldest is dropped);
-  * the range-proportional hand-off region (run_rel, `hand_rel_key`);
-  * the range-proportional task table (`tasks_rel_key`).
-A and B below share the shape, the batch size and (where the key is complete) every field of the key, but differ in what
+A context keeps four objects from launch to launch (mgm_amd/csrc/mgm_plan.hip), each keyed by the VALUE it was made from
+(mgm_amd/csrc/mgm_planner.h):
+  * the dense hand-off region with its per-pass sign-bit tags (run_passes): cleared whenever the plan's `HandLayout` -- per
+    laid-out pass the base, bands, slot lines and slope, the floats per slot, the volume groups, the band height -- differs from
+    the one the region was last written for;
+  * the dense plans and task tables, up to 24 of them (`dense_plans`: the bytes of the `DenseRequest`, i.e. everything
+    `plan_dense` reads -> the plan and its table on the device; the oldest is dropped);
+  * the range-proportional hand-off region (run_rel, the `HandLayout` of the `RelPlan`);
+  * the range-proportional plans and task tables, up to 24 (`rel_plans`, the bytes of the `RelRequest`).
+A and B below share the shape and the batch size but differ in what
 the cached object is built from -- the update function, FH / Hirschmueller (the exchanged-role walk), TSGM 3 / 4 (slope 1
 or 2), one / two / four bytes per cost (whether the anti-diagonal bands fit the LDS), 64 / 128 slots, weights.  A key that
 missed one of them would hand B the object A left behind; where the key does name everything, the sequence pins it against
@@ -90,6 +93,49 @@ def test_dense_task_table_sequence(ctx, oracle):
         for hs in cvs.values():
             for h in hs:
                 h.free()
+
+
+def test_dense_task_table_tsgm_3_and_4_alternate(ctx, oracle):
+    """TSGM 3 and 4 on one shape, batch and occupancy: the form-0 passes walk slope 1 or 2, which the simulated schedule is made
+    of -- each request has a plan of its own, fetched back on the second round."""
+    nx, ny, L, dmin = 140, 96, 64, -40
+    C = synth.raw_volume(nx, ny, L, seed=71)
+    cv = ctx.upload_volume(C, dmin)
+    threads(oracle)
+    try:
+        for rep in range(2):
+            for MGM in (3, 4):
+                bad = dense_step(ctx, oracle, [cv], [C], dmin, 8.0, 32.0, 8, MGM, 0, names=("k_pass2",))
+                assert not bad, (rep, MGM, bad)
+    finally:
+        oracle.set_threads(1)
+        cv.free()
+
+
+def test_dense_task_table_unweighted_and_general_weights_alternate(ctx, oracle):
+    """The same launch without weights and with a three-valued weight image (the general weighted kernels: progress words, no
+    queues, another hand-off lag in the simulated schedule), alternated."""
+    nx, ny, L, dmin = 140, 96, 64, -40
+    C = synth.raw_volume(nx, ny, L, seed=72)
+    cv = ctx.upload_volume(C, dmin)
+    u = synth.stereo_pair(nx, ny, -30, 0, seed=73)[0]
+    du = ctx.upload_image(u)
+    w3 = ctx.weights_dev(du, 4.0, 12.0)
+    w3h = w3.download()
+    third = 2.5
+    assert third not in np.unique(w3h)
+    w3h[3, 20:50, 30:90] = third  # (1, the weights' other value and a third: not the two-valued kernels)
+    w3.update(w3h)
+    threads(oracle)
+    try:
+        for rep in range(2):
+            for w8, w8h in ((None, None), (w3, w3h)):
+                bad = dense_step(ctx, oracle, [cv], [C], dmin, 8.0, 32.0, 8, 3, 0, w8, w8h, names=("k_pass2",))
+                assert not bad, (rep, w8 is not None, bad)
+    finally:
+        oracle.set_threads(1)
+        for h in (cv, du, w3):
+            h.free()
 
 
 def test_dense_task_table_cache_evicts_and_returns(ctx, oracle):

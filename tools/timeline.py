@@ -4,7 +4,7 @@ single launch": how busy the compute units are, how long bands wait for their pr
 
     python tools/timeline.py dump.txt [--csv out.csv]
 
-The dump (mgm_plan.hip) holds one line per work item:
+The dump (dump_timeline, mgm_plan.hip) holds one line per work item:
     item <ticket> <pass> <band> <strip> <queue> <start_us> <end_us> <wait_us> <waits> <hw_id> <xcc_id> <steps> <spins>
 (<wait_us> is 0 in -DMGM_P2_TIMELINE=1 builds -- this compiler rejects clock reads inside the poll loop of the queue kernels --
 and the time waited is then estimated as spins x the poll period, fitted: duration = a*steps + b*spins over all items)
