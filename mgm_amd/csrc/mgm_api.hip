@@ -1,425 +1,10 @@
-// mgm_api.hip -- the C ABI of libmgm_hip.so (include/mgm_hip.h), compute side: cost volumes, edge weights, the aggregation
-// calls (immediate, batched, deferred), the direction-sharding building blocks and the steps main() applies around the path.
-// Contexts and containers: mgm_ctx.hip; the launch plan: mgm_plan.hip.  No compute happens on the host and there is no CPU
-// fallback.
+// mgm_api.hip -- the C ABI of libmgm_hip.so (include/mgm_hip.h), compute side: edge weights, the aggregation calls (immediate,
+// batched, deferred), the direction-sharding building blocks and the steps main() applies around the path.  Contexts and
+// images: mgm_ctx.hip; cost volumes: mgm_volume.hip; the launch plan: mgm_plan.hip.  No compute happens on the host and there
+// is no CPU fallback.
 #include "mgm_host.h"
 
 extern "C" {
-
-// ---- cost volume ------------------------------------------------------------
-static int costvolume_build(mgm_ctx *c, const mgm_img *u, const mgm_img *v, int dmin, int dmax, const mgm_img *rloI,
-                            const mgm_img *rhiI, const char *prefilter, const char *distance, float truncDist, int census_win,
-                            mgm_cv **out);
-
-int mgm_costvolume_build_dev(mgm_ctx *c, const mgm_img *u, const mgm_img *v, int dmin, int dmax, const char *prefilter,
-                             const char *distance, float truncDist, int census_win, mgm_cv **out)
-{
-    return costvolume_build(c, u, v, dmin, dmax, nullptr, nullptr, prefilter, distance, truncDist, census_win, out);
-}
-
-int mgm_costvolume_build_ranged_dev(mgm_ctx *c, const mgm_img *u, const mgm_img *v, const mgm_img *dminI, const mgm_img *dmaxI,
-                                    int hull_min, int hull_max, const char *prefilter, const char *distance, float truncDist,
-                                    int census_win, mgm_cv **out)
-{
-    if (!c || !u || !dminI || !dmaxI) return fail(c, MGM_ERR_INVALID, "mgm_costvolume_build_ranged: null argument");
-    for (const mgm_img *im : {dminI, dmaxI})
-        if (im->nx != u->nx || im->ny != u->ny || im->nch != 1)
-            return fail(c, MGM_ERR_INVALID, "mgm_costvolume_build_ranged: the range images must have the left image's size");
-    return costvolume_build(c, u, v, hull_min, hull_max, dminI, dmaxI, prefilter, distance, truncDist, census_win, out);
-}
-
-static int costvolume_fill(mgm_ctx *c, const mgm_img *u, const mgm_img *v, int dmin, int dmax, const mgm_img *rloI,
-                           const mgm_img *rhiI, const char *prefilter, const char *distance, float truncDist, int census_win,
-                           mgm_cv **out);
-
-// A volume this call created does not outlive a failure of the call (a caller-provided one stays the caller's).
-static int costvolume_build(mgm_ctx *c, const mgm_img *u, const mgm_img *v, int dmin, int dmax, const mgm_img *rloI,
-                            const mgm_img *rhiI, const char *prefilter, const char *distance, float truncDist, int census_win,
-                            mgm_cv **out)
-{
-    if (!c || !u || !v || !out) return fail(c, MGM_ERR_INVALID, "mgm_costvolume_build: null argument");
-    const bool provided = *out != nullptr;
-    const int r = costvolume_fill(c, u, v, dmin, dmax, rloI, rhiI, prefilter, distance, truncDist, census_win, out);
-    if (*out) {
-        // A provided volume whose refill failed after its state had been touched (a reservation that ran out of memory, a
-        // kernel launch error) must not pass for a filled one: no compact copy, no "NaN-free" verdict, and the mark
-        // that makes mgm_aggregate* refuse it.
-        (*out)->unfilled = r != MGM_OK;
-        if (r != MGM_OK) {
-            (*out)->c8_state = -1;
-            (*out)->p8_state = 0;
-            (*out)->nan_state = 0;
-        }
-    }
-    if (r != MGM_OK && !provided && *out) {
-        const std::string msg = c->err;  // (mgm_cv_free synchronises and may touch the message)
-        mgm_cv_free(c, *out);
-        *out = nullptr;
-        c->err = msg;
-    }
-    return r;
-}
-
-static int costvolume_fill(mgm_ctx *c, const mgm_img *u, const mgm_img *v, int dmin, int dmax, const mgm_img *rloI,
-                           const mgm_img *rhiI, const char *prefilter, const char *distance, float truncDist, int census_win,
-                           mgm_cv **out)
-{
-    if (u->nch != v->nch) return fail(c, MGM_ERR_INVALID, "mgm_costvolume_build: channel counts differ");
-    HIPCHK(c, hipSetDevice(c->device));
-    int dist = distance_index(distance), pre = prefilter_index(prefilter);
-    const int costfn = dist;  // the function is picked BEFORE the consistency fix (mgm_costvolume.h:355)
-    if (dist == 2 || pre == 1) {  // 358-362
-        dist = 2;
-        pre = 1;
-    }
-
-    if (pre == 1) {  // (checked before a provided volume is touched: a bad window leaves it as it was)
-        const int wr0 = census_win / 2, side0 = 2 * wr0 + 1, nbits0 = u->nch * (side0 * side0 - 1);
-        if (wr0 < 1 || nbits0 % 8)  // census_tools.cc:81 asserts this
-            return fail(c, MGM_ERR_INVALID, "census: nch*(win*win-1) must be a positive multiple of 8");
-        if ((nbits0 / 8 + 3) / 4 > kCensusMaxWords) return fail(c, MGM_ERR_UNSUPPORTED, "census descriptor longer than 256 bits");
-    }
-    int r = MGM_OK;
-    if (*out) {  // caller-provided volume to refill (must have the right geometry)
-        if ((*out)->nx != u->nx || (*out)->ny != u->ny || (*out)->dmin != dmin || (*out)->dmax != dmax)
-            return fail(c, MGM_ERR_INVALID, "mgm_costvolume_build: *C is non-NULL but has a different geometry");
-        // (pipelined context: a deferred aggregation still wants the costs this volume holds now)
-        if (pipe_uses(c, *out) && (r = pipe_flush(c))) return r;
-    } else if ((r = cv_create(c, u->nx, u->ny, dmin, dmax, false, out))) {
-        return r;
-    }
-    (*out)->nan_words = false;
-    (*out)->gen = next_cv_generation();
-    CostParams p{};
-    p.C = (*out)->d;
-    p.C8 = nullptr;
-    p.bad8 = (*out)->bad8;
-    HIPCHK(c, hipMemsetAsync((*out)->bad8, 0, 4, c->stream));
-    (*out)->c8_state = 0;
-    (*out)->p8_state = 0;
-    (*out)->nan_state = 1;  // K2 flags NaN costs as it writes them
-    if (rloI) {  // the volume keeps its own copy of the range images: K4-K6 need them again
-        const size_t nb = sizeof(float) * (size_t)u->nx * u->ny;
-        for (float **q : {&(*out)->rlo, &(*out)->rhi})
-            if (!*q && dev_malloc((void **)q, nb) != hipSuccess) {
-                *q = nullptr;
-                return fail(c, MGM_ERR_NOMEM, "mgm_costvolume_build: range images");
-            }
-        HIPCHK(c, hipMemcpyAsync((*out)->rlo, rloI->d, nb, hipMemcpyDeviceToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync((*out)->rhi, rhiI->d, nb, hipMemcpyDeviceToDevice, c->stream));
-    } else if ((*out)->rlo) {  // a refilled volume that used to be ragged
-        (void)hipFree((*out)->rlo);
-        (void)hipFree((*out)->rhi);
-        (*out)->rlo = (*out)->rhi = nullptr;
-    }
-    p.rlo = (*out)->rlo;
-    p.rhi = (*out)->rhi;
-    // (NCC costs are (nch - clipped NCC) * 64 and Birchfield-Tomasi costs are built on half-way interpolants: practically
-    // never whole numbers, so no compact copy is attempted -- one byte store per label of K2, for nothing)
-    // Neither is one attempted for census over several descriptor words (thirds or halves of bit counts), for differences of
-    // blurred images or of descriptor words read as floats, nor for a volume whose last two fillings did not fit: those
-    // write the fp32 volume alone (k_cost_btx).
-    const int census_words = pre == 1 ? (u->nch * ((census_win / 2 * 2 + 1) * (census_win / 2 * 2 + 1) - 1) / 8 + 3) / 4 : 0;
-    const bool may_be_integer = costfn == 2 ? census_words == 1 : (costfn <= 1 && (pre == 0 || pre == 2) && (*out)->diff_fails < 2);
-    // Which compact form: census costs are bit counts (one byte); absolute differences of a one-channel 8-bit pair stay below
-    // 256, of a colour pair below 766, squared differences below 65026 per channel: two bytes (up to 512 labels: the pass
-    // kernels that read them).  The flag word tells afterwards whether every cost really had the form.
-    const int cb = (costfn == 2 || (costfn == 0 && u->nch == 1 && !(*out)->diff_wide) || dmax - dmin + 1 > 512) ? 1 : 2;
-    // (a ragged single-word census volume first tries to be written as its range-proportional copy ALONE, below: no compact hull
-    // is allocated for it unless that fails)
-    const bool rel_direct_candidate = rloI && costfn == 2 && census_words == 1 && rel_enabled() && dev().lazy_f32 && tune_num("rel_direct", 1) != 0 &&
-                                      (truncDist == __builtin_huge_valf() || (truncDist >= 0.0f && !std::signbit(truncDist) && truncDist <= 254.0f && truncDist == rintf(truncDist)));
-    auto setup_c8 = [&]() -> int {
-        if (c8_supported(dmax - dmin + 1) && dev().c8) {
-            if (may_be_integer) {
-                if (int rr = c8_alloc(c, *out, cb)) return rr;
-                p.C8 = (*out)->d8;
-                p.cbytes = cb;
-                (*out)->c8_state = 1;
-            } else
-                (*out)->c8_state = -1;
-        }
-        return MGM_OK;
-    };
-    if (!rel_direct_candidate && (r = setup_c8())) return r;
-    (*out)->f32_state = 1;
-    p.nx = u->nx;
-    p.ny = u->ny;
-    p.vnx = v->nx;
-    p.vny = v->ny;
-    p.dmin = dmin;
-    p.L = dmax - dmin + 1;
-    p.Lreal = p.L;
-    p.costfn = costfn;
-    p.hwin = census_win / 2;  // computeC_clippedNCC: CENSUS_NCC_WIN()/2
-    p.nch = u->nch;
-    p.u = u->d;
-    p.v = v->d;
-    if (pre == 1) {
-        const int wr = census_win / 2, side = 2 * wr + 1;
-        const int nbits = u->nch * (side * side - 1);
-        if (wr < 1 || nbits % 8)  // census_tools.cc:81 asserts this
-            return fail(c, MGM_ERR_INVALID, "census: nch*(win*win-1) must be a positive multiple of 8");
-        const int nwords = (nbits / 8 + 3) / 4;
-        if (nwords > kCensusMaxWords) return fail(c, MGM_ERR_UNSUPPORTED, "census descriptor longer than 256 bits");
-        (*out)->nan_words = costfn != 2 && nbits > 24;
-        if ((r = reserve(c, c->census_u, sizeof(uint32_t) * (size_t)u->nx * u->ny * nwords))) return r;
-        if ((r = reserve(c, c->census_v, sizeof(uint32_t) * (size_t)v->nx * v->ny * nwords))) return r;
-        {
-            TimeScope t(c, "k_census");
-            HIPCHK(c, launch_census(u->d, u->nx, u->ny, u->nch, wr, (uint32_t *)c->census_u.p, c->stream));
-        }
-        {
-            TimeScope t(c, "k_census");
-            HIPCHK(c, launch_census(v->d, v->nx, v->ny, v->nch, wr, (uint32_t *)c->census_v.p, c->stream));
-        }
-        p.cu = (const uint32_t *)c->census_u.p;
-        p.cv = (const uint32_t *)c->census_v.p;
-        p.u = (const float *)c->census_u.p;  // -p census with an ad/sd cost: words read as floats
-        p.v = (const float *)c->census_v.p;
-        p.nch = nwords;
-    }
-    if (pre == 2 || pre == 3) {  // sobelx / gblur of both images (mgm_costvolume.h:366-373), then AD or SD on them
-        const size_t nu = (size_t)u->nx * u->ny * u->nch, nv = (size_t)v->nx * v->ny * v->nch;
-        if ((r = reserve(c, c->census_u, sizeof(float) * nu))) return r;
-        if ((r = reserve(c, c->census_v, sizeof(float) * nv))) return r;
-        TimeScope t(c, "k_filter2d");
-        if (pre == 2) {
-            static const float sob[9] = {-1, 0, 1, -2, 0, 2, -1, 0, 1};  // img_tools.h:129-137
-            HIPCHK(c, launch_filter2d(u->d, u->nx, u->ny, u->nch, sob, 3, 3, (float *)c->census_u.p, c->stream));
-            HIPCHK(c, launch_filter2d(v->d, v->nx, v->ny, v->nch, sob, 3, 3, (float *)c->census_v.p, c->stream));
-        } else {
-            // gblur_gray with sigma = 1 (img_tools.h:140-180): the taps are computed on the host exactly as there
-            const float sigma = 1.0f;
-            const float radius = 3 * fabsf(sigma);
-            int rr = (int)ceil((double)(1 + 2 * radius));
-            rr = rr < 1 ? 1 : (rr > 39 ? 39 : rr);
-            float k[39];
-            const int cw = (rr - 1) / 2;
-            float m = 0;
-            for (int i = 0; i < rr; i++) {
-                const float x = (float)hypot((double)(i - cw), 0.0);
-                const float g = (float)exp((double)(-x * x / (2 * sigma * sigma)));  // (double-precision exp, as compiled there)
-                k[i] = g;
-                m += g;
-            }
-            for (int i = 0; i < rr; i++) k[i] /= m;
-            if ((r = reserve(c, c->stmp, sizeof(float) * std::max(nu, nv)))) return r;
-            HIPCHK(c, launch_filter2d(u->d, u->nx, u->ny, u->nch, k, rr, 1, (float *)c->stmp.p, c->stream));
-            HIPCHK(c, launch_filter2d((const float *)c->stmp.p, u->nx, u->ny, u->nch, k, 1, rr, (float *)c->census_u.p, c->stream));
-            HIPCHK(c, launch_filter2d(v->d, v->nx, v->ny, v->nch, k, rr, 1, (float *)c->stmp.p, c->stream));
-            HIPCHK(c, launch_filter2d((const float *)c->stmp.p, v->nx, v->ny, v->nch, k, 1, rr, (float *)c->census_v.p, c->stream));
-        }
-        p.u = (const float *)c->census_u.p;
-        p.v = (const float *)c->census_v.p;
-    }
-    if (costfn == 3 && pre == 0 && !rloI && u->nch <= 4) {
-        // clipped NCC on the plain images: the per-pixel window statistics are computed once (k_ncc_stats), in the census
-        // buffers, which this combination leaves free
-        if ((r = reserve(c, c->census_u, sizeof(float) * (size_t)u->nx * u->ny * (2 * u->nch + 1)))) return r;
-        if ((r = reserve(c, c->census_v, sizeof(float) * (size_t)v->nx * v->ny * (2 * v->nch + 1)))) return r;
-        p.ncc_u = (float *)c->census_u.p;
-        p.ncc_v = (float *)c->census_v.p;
-    }
-    if (costfn >= 4 && pre == 0 && !rloI) {
-        // Birchfield-Tomasi on the plain images: the interval every sample spans is computed once (k_bt_spans), in the census
-        // buffers, which this combination leaves free
-        if ((r = reserve(c, c->census_u, sizeof(float) * (size_t)u->nx * u->ny * 2 * u->nch))) return r;
-        if ((r = reserve(c, c->census_v, sizeof(float) * (size_t)v->nx * v->ny * 2 * v->nch))) return r;
-        p.ncc_u = (float *)c->census_u.p;
-        p.ncc_v = (float *)c->census_v.p;
-    }
-    p.trunc = truncDist * (float)p.nch;  // mgm_costvolume.h:401,405
-    // A label count that the pass kernels run padded (151 -> 192 slots, ...): the same two families of costs write the PADDED
-    // compact copy themselves (mgm_cv::p8; the slots beyond the real count +INF) instead of an fp32 volume that every
-    // aggregation call would pad and encode again.  The flag word is read back at once; a volume that does not fit takes
-    // the general kernel below, fp32 volume and all, and so do its refills.
-    const int LP = (!c8_supported(p.L) && dev().c8 && dev().pad && dev().lazy_f32 && !p.rlo) ? padded_labels(p.L) : 0;
-    (*out)->rel_only = false;
-    const bool census_fits = costfn == 2 && p.nch == 1 &&
-                             (p.trunc == __builtin_huge_valf() || (p.trunc >= 0.0f && !std::signbit(p.trunc) && p.trunc <= 254.0f && p.trunc == rintf(p.trunc)));
-    const bool diff_may_fit = (costfn == 0 || costfn == 1) && (pre == 0 || pre == 2) && p.trunc >= 0.0f && !std::signbit(p.trunc) &&
-                              (long long)u->nx * u->ny < 0x7fffffffll;  // (what k_cost_diffx takes)
-    // A ragged single-word census volume: the RANGE-PROPORTIONAL copy alone, straight from the descriptor words (mgm_pass_rel.hip,
-    // k_cost_census_rel) -- neither the fp32 hull nor its compact twin is written; whoever wants the hull gets it from
-    // ensure_f32.  The flag word (a window wider than 62 labels) is read back at once: such a volume takes the general path.
-    if (rel_direct_candidate && p.rlo && census_fits) {
-        for (int slots = (*out)->rel_hint_slots == 128 ? 128 : 64; slots <= 128; slots *= 2) {  // (round 6: windows of up to 62 labels in 64 slots per pixel, else up to 126 in 128)
-            if ((r = rel_alloc(c, *out, slots, 1))) return r;
-            if (!(*out)->relbuf) break;
-            unsigned *flag = (*out)->rel_flag();
-            HIPCHK(c, hipMemsetAsync(flag, 0, 4, c->stream));
-            {
-                TimeScope t(c, "k_cost");
-                t.kernel = "k_cost_census_rel";
-                HIPCHK(c, launch_cost_census_rel(p.cu, p.cv, p.nx, p.ny, p.vnx, p.vny, dmin, p.L, p.trunc, p.rlo, p.rhi, slots, (*out)->relbuf, (*out)->rel_records(),
-                                                 flag, c->stream));
-            }
-            if ((r = ensure_words(c))) return r;
-            HIPCHK(c, hipMemcpyAsync(c->h_words + 3, flag, 4, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-            if (c->h_words[3] == 0u) {
-                (*out)->rel_hint_slots = slots;
-                (*out)->rel_state = 2;
-                (*out)->rel_only = true;
-                (*out)->f32_state = 0;
-                (*out)->c8_state = 0;   // (no compact hull either: c8_resolve makes one from the expanded volume if a dense launch wants it)
-                (*out)->nan_state = 2;  // integer costs: NaN-free by construction
-                return MGM_OK;
-            }
-            if (tune_num("rel_wide", 1) == 0) break;
-        }
-        (*out)->rel_state = 0;
-    }
-    if (rel_direct_candidate && (r = setup_c8())) return r;  // (it did not work out: a window wider than 62 labels -- the general path)
-    if (LP && (*out)->diff_fails < 2 && (census_fits || diff_may_fit)) {
-        int pcb = (costfn == 2 || (costfn == 0 && u->nch == 1 && !(*out)->diff_wide) || LP > 512) ? 1 : 2;
-        for (;;) {
-            if ((r = p8_alloc(c, *out, LP, pcb))) return r;
-            CostParams q = p;
-            q.C = nullptr;
-            q.C8 = (*out)->p8;
-            q.cbytes = pcb;
-            q.L = LP;
-            {
-                TimeScope t(c, "k_cost");
-                HIPCHK(c, launch_cost(q, c->stream, &t.kernel));
-            }
-            bool fits = census_fits;  // (min(popcount, trunc) in integers: fits and is NaN-free by construction, nothing to read back)
-            if (!fits) {
-                HIPCHK(c, hipMemcpyAsync(c->h_words + 3, (*out)->bad8, 4, hipMemcpyDeviceToHost, c->stream));
-                HIPCHK(c, hipStreamSynchronize(c->stream));
-                fits = c->h_words[3] == 0u;
-            }
-            if (fits) {
-                (*out)->diff_fails = 0;
-                (*out)->p8_state = 2;
-                (*out)->f32_state = 0;
-                (*out)->nan_state = 2;
-                return MGM_OK;
-            }
-            HIPCHK(c, hipMemsetAsync((*out)->bad8, 0, 4, c->stream));
-            if (pcb == 1 && c->h_words[3] == 1u && LP <= 512) {  // one byte per cost was too narrow, two will do
-                (*out)->diff_wide = true;
-                pcb = 2;
-                continue;
-            }
-            break;
-        }
-        (*out)->diff_fails++;
-    }
-    // A census cost over one descriptor word is a bit count 0..32, clipped to `trunc`: with trunc = +INF
-    // or an integer up to 254 every cost fits the compact form, and the fp32 volume -- which neither K3
-    // nor k_wta reads then -- is only materialised on demand (ensure_f32).
-    if (p.C8 && !p.rlo && costfn == 2 && p.nch == 1 &&
-        (p.trunc == __builtin_huge_valf() || (p.trunc >= 0.0f && !std::signbit(p.trunc) && p.trunc <= 254.0f && p.trunc == rintf(p.trunc))) &&
-        dev().lazy_f32) {
-        p.C = nullptr;
-        (*out)->f32_state = 0;
-        // these kernels (k_cost_census8*) compute min(popcount, trunc) in integers: every cost has a compact form and none
-        // is NaN BY CONSTRUCTION, so there is no flag to read back -- a refilled volume costs no synchronisation
-        (*out)->c8_state = 2;
-        (*out)->nan_state = 2;
-    } else if (p.C8 && !p.rlo && (costfn == 0 || costfn == 1) && (pre == 0 || pre == 2) && dev().lazy_f32 && (*out)->diff_fails < 2) {
-        // Absolute / squared differences of (sobelx-filtered) 8-bit images are whole numbers: write the compact copy alone and
-        // read the flag word back -- the read-back the aggregation would do anyway (c8_resolve).  A volume that does not fit
-        // (float-valued images, a fractional truncDist) is filled again by the general kernel, fp32 volume and all, and so
-        // are its refills.
-        p.C = nullptr;
-        (*out)->f32_state = 0;
-        for (;;) {
-            {
-                TimeScope t(c, "k_cost");
-                HIPCHK(c, launch_cost(p, c->stream, &t.kernel));
-            }
-            HIPCHK(c, hipMemcpyAsync(c->h_words + 3, (*out)->bad8, 4, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-            if (c->h_words[3] == 0u) {
-                (*out)->diff_fails = 0;
-                (*out)->c8_state = 2;
-                (*out)->nan_state = 2;
-                return MGM_OK;
-            }
-            HIPCHK(c, hipMemsetAsync((*out)->bad8, 0, 4, c->stream));
-            // one byte per cost was too narrow (a grey pair with a difference of 255), two would do (k_cost_diffx says so)
-            if (p.cbytes == 1 && c->h_words[3] == 1u && p.L <= 512) {
-                (*out)->diff_wide = true;
-                if ((r = c8_alloc(c, *out, 2))) return r;
-                p.C8 = (*out)->d8;
-                p.cbytes = 2;
-                continue;
-            }
-            break;
-        }
-        (*out)->diff_fails++;
-        if ((r = cv_alloc_f32(c, *out))) return r;
-        p.C = (*out)->d;
-        p.C8 = nullptr;  // (no compact form: the fp32 volume alone)
-        (*out)->c8_state = -1;
-        (*out)->nan_state = 1;
-        (*out)->f32_state = 1;
-    } else {
-        if ((r = cv_alloc_f32(c, *out))) return r;
-        p.C = (*out)->d;
-    }
-    {
-        TimeScope t(c, "k_cost");
-        HIPCHK(c, launch_cost(p, c->stream, &t.kernel));
-    }
-    // A ragged volume also gets its RANGE-PROPORTIONAL copy (mgm_pass_rel.hip): 64 cost bytes per pixel at the pixel's own
-    // window -- what the aggregation then walks instead of the hull, if every window is at most 62 labels wide and every
-    // cost a byte (the flag word is read back by the first aggregation).
-    (*out)->rel_state = 0;
-    if (p.rlo && p.C && rel_enabled()) {
-        // the narrowest form the cost function can have: one byte for single-word census and grey-level absolute differences, two for
-        // the other absolute / squared differences; the flag word (read back by the first aggregation, rel_resolve) widens it
-        // (... and the fp32 cost itself -- four bytes -- for what has no integer form: NCC, Birchfield-Tomasi, census over several words,
-        // differences of filtered images)
-        const int rcb = ((costfn == 2 && census_words == 1) || (costfn == 0 && u->nch == 1 && pre == 0)) ? 1
-                        : (((costfn == 0 || costfn == 1) && (pre == 0 || pre == 2)) ? 2 : 4);
-        if ((r = rel_alloc(c, *out, 64, rcb))) return r;
-        if ((*out)->relbuf) {
-            HIPCHK(c, hipMemsetAsync((*out)->rel_flag(), 0, 4, c->stream));
-            TimeScope t(c, "k_rel_gather");
-            HIPCHK(c, launch_rel_gather(p.C, p.rlo, p.rhi, (long long)u->nx * u->ny, p.L, dmin, 64, rcb, (*out)->relbuf, (*out)->rel_records(), (*out)->rel_flag(),
-                                        c->stream));
-            (*out)->rel_state = 1;
-        }
-    }
-    return MGM_OK;
-}
-
-int mgm_costvolume_build(mgm_ctx *c, const float *u, const float *v, int nx, int ny, int nch, int vnx, int vny,
-                         const float *dminI, const float *dmaxI, const char *prefilter, const char *distance,
-                         float truncDist, int census_win, mgm_cv **out)
-{
-    if (!c || !u || !v || !dminI || !dmaxI || !out) return fail(c, MGM_ERR_INVALID, "mgm_costvolume_build: null argument");
-    // Dvec::init receives the float range values converted to int (dvec.cc:55-60)
-    int dmin = (int)dminI[0], dmax = (int)dmaxI[0];
-    bool ragged = false;
-    for (long long i = 0; i < (long long)nx * ny; i++) {
-        const int lo = (int)dminI[i], hi = (int)dmaxI[i];
-        if (hi < lo) return fail(c, MGM_ERR_INVALID, "mgm_costvolume_build: a pixel's range is empty (dmax < dmin)");
-        ragged |= lo != dmin || hi != dmax;
-    }
-    if (ragged)  // the dense layout spans the hull of all ranges
-        for (long long i = 0; i < (long long)nx * ny; i++) {
-            dmin = std::min(dmin, (int)dminI[i]);
-            dmax = std::max(dmax, (int)dmaxI[i]);
-        }
-    mgm_img *du = nullptr, *dv = nullptr, *dlo = nullptr, *dhi = nullptr;
-    *out = nullptr;
-    int r = mgm_img_upload(c, u, nx, ny, nch, &du);
-    if (!r) r = mgm_img_upload(c, v, vnx, vny, nch, &dv);
-    if (!r && ragged) r = mgm_img_upload(c, dminI, nx, ny, 1, &dlo);
-    if (!r && ragged) r = mgm_img_upload(c, dmaxI, nx, ny, 1, &dhi);
-    if (!r)
-        r = ragged ? mgm_costvolume_build_ranged_dev(c, du, dv, dlo, dhi, dmin, dmax, prefilter, distance, truncDist, census_win, out)
-                   : mgm_costvolume_build_dev(c, du, dv, dmin, dmax, prefilter, distance, truncDist, census_win, out);
-    if (!r) r = mgm_ctx_synchronize(c);
-    for (mgm_img *im : {du, dv, dlo, dhi}) mgm_img_free(c, im);
-    return r;
-}
 
 // ---- weights ------------------------------------------------------------------
 int mgm_weights_dev(mgm_ctx *c, const mgm_img *u, float aP, float aThresh, mgm_img **w8)

@@ -1,12 +1,6 @@
-// mgm_ctx.hip -- contexts, device containers (images, volumes and their compact copies), timing: the part of the C ABI of
-// libmgm_hip.so (include/mgm_hip.h) that owns memory.  See mgm_host.h.
+// mgm_ctx.hip -- contexts, images, development switches, timing: the part of the C ABI of libmgm_hip.so (include/mgm_hip.h)
+// that owns the contexts' memory (the volumes and their copies: mgm_volume.hip).  See mgm_host.h.
 #include "mgm_host.h"
-
-unsigned long long next_cv_generation()
-{
-    static unsigned long long g = 0;
-    return ++g;
-}
 
 // ---- development switches: ONE place, ONE variable -------------------------------------------------------------------------
 // MGM_HIP_TUNE="key=value,key=value,..." -- or, as in rounds 1-3 (tests and tools still use them), the individual variables
@@ -420,251 +414,4 @@ int mgm_img_free(mgm_ctx *c, mgm_img *im)
     return MGM_OK;
 }
 
-// ---- volumes --------------------------------------------------------------
-// The fp32 array of a volume is allocated when somebody needs it: a volume K2 fills in the compact form only (single-word
-// census costs) never does on the hot path.
-extern "C++" int cv_alloc_f32(mgm_ctx *c, mgm_cv *cv)
-{
-    if (cv->d) return MGM_OK;
-    const size_t n = (size_t)cv->nx * cv->ny * (size_t)(cv->dmax - cv->dmin + 1);
-    hipError_t e = dev_malloc((void **)&cv->d, sizeof(float) * n);
-    if (e != hipSuccess) {
-        cv->d = nullptr;
-        return fail(c, MGM_ERR_NOMEM, std::string("cost volume (fp32): ") + hipGetErrorString(e));
-    }
-    return MGM_OK;
-}
-extern "C++" int cv_create(mgm_ctx *c, int nx, int ny, int dmin, int dmax, bool alloc_f32, mgm_cv **out)
-{
-    if (!c || !out || nx <= 0 || ny <= 0 || dmax < dmin) return fail(c, MGM_ERR_INVALID, "mgm_cv_create: bad arguments");
-    const long long L = (long long)dmax - dmin + 1;
-    if (L > kMaxLabels)
-        return fail(c, MGM_ERR_UNSUPPORTED, "more than 4 194 304 disparity labels per pixel are not supported");
-    HIPCHK(c, hipSetDevice(c->device));
-    mgm_cv *cv = new mgm_cv();
-    cv->d = nullptr;
-    cv->nx = nx;
-    cv->ny = ny;
-    cv->dmin = dmin;
-    cv->dmax = dmax;
-    cv->owner = c;
-    if (alloc_f32)
-        if (int r = cv_alloc_f32(c, cv)) {
-            delete cv;
-            return r;
-        }
-    if (dev_malloc((void **)&cv->bad8, 64) != hipSuccess) {
-        if (cv->d) (void)hipFree(cv->d);
-        delete cv;
-        return fail(c, MGM_ERR_NOMEM, "mgm_cv_create: flag word");
-    }
-    cv->gen = next_cv_generation();
-    *out = cv;
-    return MGM_OK;
-}
-int mgm_cv_create(mgm_ctx *c, int nx, int ny, int dmin, int dmax, mgm_cv **out) { return cv_create(c, nx, ny, dmin, dmax, true, out); }
-int mgm_cv_upload(mgm_ctx *c, const float *dense, int nx, int ny, int dmin, int dmax, mgm_cv **out)
-{
-    if (!dense) return fail(c, MGM_ERR_INVALID, "mgm_cv_upload: null host pointer");
-    int r = mgm_cv_create(c, nx, ny, dmin, dmax, out);
-    if (r) return r;
-    const size_t n = (size_t)nx * ny * (size_t)(dmax - dmin + 1);
-    hipError_t e = hipMemcpyAsync((*out)->d, dense, sizeof(float) * n, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) {
-        r = hipfail(c, e, "mgm_cv_upload: copy");
-        mgm_cv_free(c, *out);
-        *out = nullptr;
-        return r;
-    }
-    (*out)->c8_state = 0;
-    (*out)->p8_state = 0;
-    (*out)->nan_state = 0;
-    return MGM_OK;
-}
-// make cv->d current (see mgm_cv::f32_state); enqueued on the context's stream
-extern "C++" int ensure_f32(mgm_ctx *c, const mgm_cv *ccv)
-{
-    mgm_cv *cv = const_cast<mgm_cv *>(ccv);
-    if (cv->f32_state) return MGM_OK;
-    if (cv->rel_only && cv->rel_state == 2 && cv->relbuf) {  // K2 wrote the range-proportional copy alone (ragged census volume)
-        if (int r = cv_alloc_f32(c, cv)) return r;
-        const long long npix = (long long)cv->nx * cv->ny;
-        TimeScope t(c, "k_expand");
-        HIPCHK(c, launch_rel_expand(cv->relbuf, cv->rel_records(), npix, cv->dmax - cv->dmin + 1, cv->dmin, cv->rel_slots, cv->rel_cb, cv->d, c->stream));
-        cv->f32_state = 1;
-        return MGM_OK;
-    }
-    if (cv->p8_state == 2) {  // K2 wrote the padded compact copy alone
-        if (int r = cv_alloc_f32(c, cv)) return r;
-        TimeScope t(c, "k_expand");
-        HIPCHK(c, launch_expand_padded(cv->p8, cv->p8_cb, (long long)cv->nx * cv->ny, cv->dmax - cv->dmin + 1, cv->p8_L, cv->d, c->stream));
-        cv->f32_state = 1;
-        return MGM_OK;
-    }
-    if (!cv->d8 || cv->c8_state < 1) return fail(c, MGM_ERR_INTERNAL, "cost volume has neither an fp32 nor a compact copy");
-    if (int r = cv_alloc_f32(c, cv)) return r;
-    TimeScope t(c, "k_expand");
-    HIPCHK(c, launch_expand(cv->d8, cv->cbytes, (long long)cv->nx * cv->ny * (cv->dmax - cv->dmin + 1), cv->d, c->stream));
-    cv->f32_state = 1;
-    return MGM_OK;
-}
-int mgm_cv_download(mgm_ctx *c, const mgm_cv *cv, float *dense)
-{
-    if (int jr = pipe_join(c)) return jr;  // (pipelined context: run what has been deferred first)
-    if (!c || !cv || !dense) return fail(c, MGM_ERR_INVALID, "mgm_cv_download: bad arguments");
-    HIPCHK(c, hipSetDevice(c->device));
-    if (int r = ensure_f32(c, cv)) return r;
-    const size_t n = (size_t)cv->nx * cv->ny * (size_t)(cv->dmax - cv->dmin + 1);
-    HIPCHK(c, hipMemcpyAsync(dense, cv->d, sizeof(float) * n, hipMemcpyDeviceToHost, c->stream));
-    return mgm_ctx_synchronize(c);
-}
-int mgm_cv_dims(const mgm_cv *cv, int *nx, int *ny, int *dmin, int *dmax)
-{
-    if (!cv) return MGM_ERR_INVALID;
-    if (nx) *nx = cv->nx;
-    if (ny) *ny = cv->ny;
-    if (dmin) *dmin = cv->dmin;
-    if (dmax) *dmax = cv->dmax;
-    return MGM_OK;
-}
-int mgm_cv_device(const mgm_cv *cv) { return (cv && cv->owner) ? cv->owner->device : -1; }
-void *mgm_cv_device_ptr(mgm_cv *cv)
-{
-    if (cv) (void)pipe_join(cv->owner);
-    if (!cv) return nullptr;
-    if (cv->owner && ensure_f32(cv->owner, cv)) return nullptr;
-    cv->c8_state = 0;  // the caller may write through the pointer: re-derive the compact copy at the next use
-    cv->rel_only = false;  // (and the range-proportional copy no longer stands for the volume)
-    cv->rel_state = cv->rel_state == 2 || cv->rel_state == 1 ? 0 : cv->rel_state;
-    cv->p8_state = 0;
-    cv->nan_state = 0;
-    cv->gen = next_cv_generation();
-    return cv->d;
-}
-int mgm_cv_free(mgm_ctx *c, mgm_cv *cv)
-{
-    if (int jr = pipe_join(c)) return jr;  // (pipelined context: run what has been deferred first)
-    if (!cv) return MGM_OK;
-    // (freed through another context, or with none: the context that made the volume may still hold deferred calls on it)
-    if (cv->owner && cv->owner != c && pipe_uses(cv->owner, cv)) (void)pipe_join(cv->owner);
-    if (c) {
-        (void)hipSetDevice(c->device);
-        (void)hipStreamSynchronize(c->stream);
-    }
-    for (mgm_ctx *o : {c, cv->owner})
-        if (o)
-            for (int v = 0; v < kMaxBatch; v++)
-                if (o->last_cvs[v] == cv) o->last_cvs[v] = nullptr;
-    if (cv->d) (void)hipFree(cv->d);
-    if (cv->d8) (void)hipFree(cv->d8);
-    if (cv->p8) (void)hipFree(cv->p8);
-    if (cv->bad8) (void)hipFree(cv->bad8);
-    if (cv->relbuf) (void)hipFree(cv->relbuf);
-    for (mgm_ctx *o : {c, cv->owner})
-        if (o)
-            for (int v = 0; v < kMaxBatch; v++)
-                if (o->rel_last_cvs[v] == cv) o->rel_last_cvs[v] = nullptr;
-    if (cv->rlo) (void)hipFree(cv->rlo);
-    if (cv->rhi) (void)hipFree(cv->rhi);
-    delete cv;
-    return MGM_OK;
-}
-
 }  // extern "C"
-
-// ---- compact costs -----------------------------------------------------------
-int c8_alloc(mgm_ctx *c, mgm_cv *cv, int cb)
-{
-    const size_t n = (size_t)cv->nx * cv->ny * (size_t)(cv->dmax - cv->dmin + 1) * cb + 64;
-    if (cv->d8 && cv->d8_cap < n) {  // (refilled with a cost that takes the wider form)
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        (void)hipFree(cv->d8);
-        cv->d8 = nullptr;
-    }
-    if (!cv->d8) {
-        if (dev_malloc((void **)&cv->d8, n) != hipSuccess) {
-            cv->d8 = nullptr;
-            cv->d8_cap = 0;
-            return fail(c, MGM_ERR_NOMEM, "hipMalloc of the compact cost volume failed");
-        }
-        cv->d8_cap = n;
-    }
-    cv->cbytes = cb;
-    return MGM_OK;
-}
-// room for a padded compact copy of LP label slots, cb bytes each (mgm_cv::p8)
-int p8_alloc(mgm_ctx *c, mgm_cv *cv, int LP, int cb)
-{
-    const size_t n = (size_t)cv->nx * cv->ny * (size_t)LP * cb + 64;
-    if (cv->p8 && cv->p8_cap < n) {
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        (void)hipFree(cv->p8);
-        cv->p8 = nullptr;
-    }
-    if (!cv->p8) {
-        if (dev_malloc((void **)&cv->p8, n) != hipSuccess) {
-            cv->p8 = nullptr;
-            cv->p8_cap = 0;
-            return fail(c, MGM_ERR_NOMEM, "hipMalloc of the padded compact cost volume failed");
-        }
-        cv->p8_cap = n;
-    }
-    cv->p8_L = LP;
-    cv->p8_cb = cb;
-    return MGM_OK;
-}
-// Decide (once per filling of the volume) whether the compact copy can stand in for C, and whether the volume
-// holds NaN costs (mgm_cv::nan_state).  Costs one 4-byte device->host read per filling; MGM_HIP_C8=0 disables the
-// compact path.  An uploaded volume is scanned here: by k_compact where it gets a compact copy, else by k_nanscan.
-int c8_resolve(mgm_ctx *c, const mgm_cv *ccv, bool *use)
-{
-    mgm_cv *cv = const_cast<mgm_cv *>(ccv);
-    *use = false;
-    const int L = cv->dmax - cv->dmin + 1;
-    const bool enabled = dev().c8 && c8_supported(L);
-    const long long n = (long long)cv->nx * cv->ny * L;
-    bool launched = false;
-    if (enabled && cv->c8_state == 0) {  // uploaded / externally written volume: make the compact copy now (one byte per cost)
-        int r = ensure_f32(c, cv);  // (a ragged census volume that only has its range-proportional copy)
-        if (r) return r;
-        r = c8_alloc(c, cv, 1);
-        if (r) return r;
-        HIPCHK(c, hipMemsetAsync(cv->bad8, 0, 4, c->stream));
-        TimeScope t(c, "k_compact");
-        HIPCHK(c, launch_compact(cv->d, n, cv->d8, 1, cv->bad8, c->stream));
-        cv->c8_state = 1;
-        cv->nan_state = 1;
-        launched = true;
-    }
-    if (cv->nan_state == 0) {
-        if (int r = ensure_f32(c, cv)) return r;
-        if (!launched) HIPCHK(c, hipMemsetAsync(cv->bad8, 0, 4, c->stream));
-        TimeScope t(c, "k_nanscan");
-        HIPCHK(c, launch_nanscan(cv->d, n, cv->bad8, c->stream));
-        cv->nan_state = 1;
-    }
-    if (cv->c8_state == 1 || cv->nan_state == 1) {
-        HIPCHK(c, hipMemcpyAsync(c->h_words + 3, cv->bad8, 4, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (cv->c8_state == 1) cv->c8_state = (c->h_words[3] & 1u) ? -1 : 2;
-        if (cv->nan_state == 1) cv->nan_state = (c->h_words[3] & 2u) ? -1 : 2;
-        // an uploaded volume of whole numbers beyond 254 (absolute differences of a colour pair computed elsewhere): the
-        // two-byte form, where the pass kernels read it (up to 512 labels) -- k_compact says whether it would fit
-        if (launched && cv->c8_state < 0 && cv->nan_state == 2 && !(c->h_words[3] & 8u) && L <= 512 && cv->f32_state) {
-            if (int r = c8_alloc(c, cv, 2)) return r;
-            HIPCHK(c, hipMemsetAsync(cv->bad8, 0, 4, c->stream));
-            {
-                TimeScope t(c, "k_compact");
-                HIPCHK(c, launch_compact(cv->d, n, cv->d8, 2, cv->bad8, c->stream));
-            }
-            HIPCHK(c, hipMemcpyAsync(c->h_words + 3, cv->bad8, 4, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-            cv->c8_state = (c->h_words[3] & 1u) ? -1 : 2;
-        }
-        if (cv->c8_state < 0 && !cv->f32_state)
-            return fail(c, MGM_ERR_INTERNAL, "cost volume predicted to fit the compact form does not");
-    }
-    *use = enabled && cv->c8_state == 2;
-    return MGM_OK;
-}

@@ -3,7 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "mgm_geom.h"  // kMaxDirs, kMaxBatch, kMaxBands, PassGeom, the pass table
+#include "mgm_fillplan.h"  // c8_supported, padded_labels
+#include "mgm_geom.h"  // kMaxDirs, kMaxBatch, kMaxBands, kCensusMaxWords, PassGeom, the pass table
 
 namespace mgm {
 
@@ -11,7 +12,6 @@ constexpr int kMaxLPL = 32;          // disparities per lane of the fast kernels
 constexpr int kMaxLabels = 1 << 22;  // (index arithmetic; the reference's Dvec has no limit, dvec.cc:60) beyond 2048 labels: the generic
                                      // kernels (mgm_pass_exact.hip, k_wta_any); FH beyond 8192: convolution arrays in global scratch
 constexpr int kWave = 64;            // CDNA wavefront
-constexpr int kCensusMaxWords = 8;   // 32-bit census words per pixel
 
 struct PassVolume {
     const float *C;     // [npix][L]
@@ -169,8 +169,6 @@ bool pass2_timeline();  // built with -DMGM_P2_TIMELINE=1 (MGM_HIP_TIMELINE is h
 hipError_t launch_pass2(const PassParams &p, int ntasks, bool fh, int wmode, hipStream_t s);
 template <int LPL>
 hipError_t launch_pass2_lpl(const PassParams &p, int ntasks, bool fh, int wmode, hipStream_t s);
-// compact-cost support: labels per lane for which the C8 forms of K3 / k_wta exist
-inline bool c8_supported(int L) { return L == 64 || L == 128 || L == 192 || L == 256 || L == 384 || L == 512 || L == 768 || L == 1024; }
 hipError_t launch_compact(const float *C, long long n, uint8_t *C8, int cbytes, unsigned *bad8, hipStream_t s);
 hipError_t launch_nanscan(const float *C, long long n, unsigned *flag, hipStream_t s);
 hipError_t launch_pad(const float *C, long long npix, int L, int LP, float *Cp, uint8_t *C8p, int cbytes, unsigned *bad8, hipStream_t s);

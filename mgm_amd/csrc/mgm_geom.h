@@ -7,6 +7,7 @@ namespace mgm {
 constexpr int kMaxDirs = 8;
 constexpr int kMaxBands = 4096;
 constexpr int kR = 16;  // lines per band (waves per workgroup) of the pass kernel
+constexpr int kCensusMaxWords = 8;  // 32-bit census words per pixel
 
 // Geometry of one pass in canonical coordinates (i = position along the scan
 // line, j = line index).  Derived on the host from the reference's pass table

@@ -1,8 +1,10 @@
 // mgm_host.h -- host-side internals shared by the translation units behind the C ABI of libmgm_hip.so
-// (mgm_ctx.hip: contexts, device containers, compact cost copies; mgm_planner.h: the launch plan of the pass kernels as pure
-// functions of a request; mgm_plan.hip: the stages of a pass launch around it, the plans' caches and the winner search;
-// mgm_api.hip: cost volumes, aggregation calls, the steps around them).  Nothing here is exported through
-// include/mgm_hip.h; no compute happens on the host and there is no CPU fallback.
+// (mgm_ctx.hip: contexts, images, switches, timing; mgm_fillplan.h: how a cost volume gets filled, as pure functions of a
+// request; mgm_volume.hip: the volumes -- the stages of a filling around that plan and everything that allocates, converts or
+// invalidates one of a volume's copies; mgm_planner.h: the launch plan of the pass kernels as pure functions of a request;
+// mgm_plan.hip: the stages of a pass launch around it, the plans' caches and the winner search; mgm_api.hip: weights,
+// aggregation calls, the steps around them).  Nothing here is exported through include/mgm_hip.h; no compute happens on the
+// host and there is no CPU fallback.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -14,6 +16,7 @@
 
 #include "../../include/mgm_hip.h"
 #include "mgm_device.h"
+#include "mgm_fillplan.h"
 #include "mgm_planner.h"
 
 using namespace mgm;
@@ -33,20 +36,19 @@ struct mgm_cv {
     size_t d8_cap = 0;         // bytes allocated at d8
     mutable int pad_hint = 1;  // a label count that runs padded: the compact form its padded copy took last time (0: none did)
     unsigned *bad8 = nullptr;  // device word: 1 = not representable
-    int c8_state = 0;          // 0 none, 1 written (validity not read back yet), 2 valid, -1 invalid
+    CopyState c8_state = CopyState::None;  // (mgm_fillplan.h: none, written and not checked, valid, invalid)
     // K2 skips the fp32 write when its costs are known to fit the compact form (single-word census):
     // nothing on the hot path reads `d` then, and it is decoded from d8 if somebody asks for it.
     int f32_state = 1;         // 1 current, 0 stale (d8 holds the volume)
-    int diff_fails = 0;        // AD / SD fillings of this volume in a row that did not fit the compact form: after two, refills go straight
-                               // to the fp32 kernel (a filling that fits resets the count)
-    bool diff_wide = false;    // ... did not fit ONE byte per cost but does fit two (a grey pair with a difference of 255): refills start there
+    FillMemory mem;            // what the next filling starts from (mgm_fillplan.h): diff_fails, diff_wide, rel_hint_slots
     // A label count that the pass kernels run PADDED (151 -> 192, ...): K2 may write the padded compact copy itself --
     // [npix][p8_L] costs of p8_cb bytes, the label slots beyond the real count +INF -- instead of an fp32 volume that every
-    // aggregation call pads and encodes again (run_passes).  p8_state 2: valid (and then the ONLY copy until somebody asks
-    // for the fp32 volume: f32_state 0), 0: none.
+    // aggregation call pads and encodes again (run_passes).  p8_state Valid (and then the ONLY copy until somebody asks
+    // for the fp32 volume: f32_state 0), else None.
     uint8_t *p8 = nullptr;
     size_t p8_cap = 0;
-    int p8_L = 0, p8_cb = 1, p8_state = 0;
+    int p8_L = 0, p8_cb = 1;
+    CopyState p8_state = CopyState::None;  // (None or Valid)
     mgm_ctx *owner = nullptr;
     // ragged volume: the per-pixel range images it was built from (device, nx*ny floats each), else nullptr.
     // dmin/dmax are then the hull of all ranges; labels outside a pixel's own range hold +INF.
@@ -59,7 +61,7 @@ struct mgm_cv {
     // reference makes of a NaN cost depends on the operand order of its minima, so such a volume is refused by
     // mgm_aggregate* instead of being aggregated into something unspecified.  0 not scanned (uploaded / written through
     // mgm_cv_device_ptr), 1 flag word on the device is current but not read back, 2 clean, -1 holds NaN.
-    int nan_state = 0;
+    CopyState nan_state = CopyState::None;
     // bumped whenever the contents may have changed: contexts remember (pointer, generation) of the volumes of their
     // last aggregation, so a refilled volume, or a new one at a recycled address, is not mistaken for one of them
     unsigned long long gen = 0;
@@ -71,9 +73,8 @@ struct mgm_cv {
     // narrowest form its cost function allows and is gathered again wider if the flag word asks for it (rel_resolve).
     uint8_t *relbuf = nullptr;
     size_t rel_cap = 0;
-    int rel_state = 0;
+    CopyState rel_state = CopyState::None;
     int rel_slots = 64, rel_cb = 1;
-    int rel_hint_slots = 64;  // the width the last direct filling of this volume needed: a refill starts there (a failed attempt costs ~2.5 ms of flag traffic)
     size_t rel_cost_bytes() const { return (size_t)nx * ny * (size_t)rel_slots * (size_t)rel_cb; }
     int *rel_records() const { return reinterpret_cast<int *>(relbuf + rel_cost_bytes()); }
     unsigned *rel_flag() const { return reinterpret_cast<unsigned *>(relbuf + rel_cost_bytes() + (size_t)nx * ny * 16); }
@@ -268,24 +269,24 @@ int pipe_flush(mgm_ctx *c);
 inline int pipe_join(mgm_ctx *c) { return (c && !c->pend.empty()) ? pipe_flush(c) : MGM_OK; }
 bool pipe_uses(const mgm_ctx *c, const void *obj);
 
-// volumes and their compact copies (mgm_ctx.hip)
+// volumes and their copies (mgm_volume.hip)
 int cv_alloc_f32(mgm_ctx *c, mgm_cv *cv);
 int cv_create(mgm_ctx *c, int nx, int ny, int dmin, int dmax, bool alloc_f32, mgm_cv **out);
 int ensure_f32(mgm_ctx *c, const mgm_cv *ccv);
 int c8_alloc(mgm_ctx *c, mgm_cv *cv, int cb = 1);
 int c8_resolve(mgm_ctx *c, const mgm_cv *ccv, bool *use);
 
-// the launch plan (mgm_plan.hip)
-int padded_labels(int L);
 int p8_alloc(mgm_ctx *c, mgm_cv *cv, int LP, int cb);
+int rel_resolve(mgm_ctx *c, const mgm_cv *cv, bool *usable);
+int rel_alloc(mgm_ctx *c, mgm_cv *cv, int slots, int cb);  // (re)allocates relbuf for the format and sets rel_slots / rel_cb; MGM_OK also when the device has no room (relbuf stays null)
+
+// the launch plan (mgm_plan.hip)
 int run_passes(mgm_ctx *c, const mgm_cv *const *Cs, const mgm_img *const *w8s, int nb, float P1, float P2, int MGM, int use_fh, int first,
                int count, bool allow_pad = false, int slot0 = 0, int nslots = 0, int layout_ndir = 0);
 int run_wta(mgm_ctx *c, const mgm_cv *C, long long pix0, long long npix, const float *lr, long long lr_stride, int NDIR, int fix_overcount,
             int ridx, float *out, float *outcost, float *Sout, const float *wlo = nullptr, const float *whi = nullptr, int slot = -1);
 // the range-proportional path of ragged volumes (mgm_plan.hip): is this call one it takes?  then the passes + the winner search
 bool rel_enabled();
-int rel_resolve(mgm_ctx *c, const mgm_cv *cv, bool *usable);
-int rel_alloc(mgm_ctx *c, mgm_cv *cv, int slots, int cb);  // (re)allocates relbuf for the format and sets rel_slots / rel_cb; MGM_OK also when the device has no room (relbuf stays null)
 int weights_have_odd_values(mgm_ctx *c, const mgm_img *const *w8s, int nb, long long npix, bool *odd, bool *any = nullptr);
 int run_rel(mgm_ctx *c, const mgm_cv *const *Cs, const mgm_img *const *w8s, int nb, float P1, float P2, int MGM, int use_fh, int NDIR,
             int fix_overcount, int ridx, mgm_img *const *outs, mgm_img *const *outcosts, mgm_cv **S = nullptr);

@@ -5,13 +5,6 @@
 
 static_assert(sizeof(Task) == sizeof(int2) && alignof(Task) <= alignof(int2), "task tables are uploaded as the kernels' int2");
 
-int padded_labels(int L)
-{
-    for (int lp : {64, 128, 192, 256, 384, 512, 768, 1024})
-        if (lp >= L) return lp;
-    return 0;
-}
-
 static unsigned long long fnv1a64(const void *data, size_t n)
 {
     unsigned long long h = 1469598103934665603ull;
@@ -428,14 +421,14 @@ static int resolve_dense_operands(mgm_ctx *c, const mgm_cv *const *Cs, const mgm
         bool u = false;
         if ((r = c8_resolve(c, Cs[v], &u))) return r;
         c8ok[v] = u;
-        o.exact |= Cs[v]->nan_state < 0;
+        o.exact |= Cs[v]->nan_state == CopyState::Invalid;
     }
     if (o.exact) return MGM_OK;
     int cb = 1;  // bytes per compact cost of this launch
     // padded launch whose volumes all carry the padded compact copy K2 wrote (mgm_cv::p8): nothing to pad or encode
     bool own_padded = padded && dev().c8;
     for (int v = 0; v < nb && own_padded; v++)
-        own_padded = Cs[v]->p8_state == 2 && Cs[v]->p8_L == L && Cs[v]->p8_cb == Cs[0]->p8_cb;
+        own_padded = Cs[v]->p8_state == CopyState::Valid && Cs[v]->p8_L == L && Cs[v]->p8_cb == Cs[0]->p8_cb;
     if (own_padded) {
         cb = Cs[0]->p8_cb;
     } else if (padded) {
@@ -731,7 +724,7 @@ int run_wta(mgm_ctx *c, const mgm_cv *C, long long pix0, long long npix, const f
     } else {
         // (two-byte costs: the exact k_wta instances and k_wta_q read them -- label counts of the compact pass kernels)
         w.cbytes = C->cbytes;
-        w.C8 = (C->c8_state == 2 && c->force_build != 1) ? C->d8 + pix0 * L * w.cbytes : nullptr;
+        w.C8 = (C->c8_state == CopyState::Valid && c->force_build != 1) ? C->d8 + pix0 * L * w.cbytes : nullptr;
         if (!w.C8)
             if (int r = ensure_f32(c, C)) return r;
         w.C = C->d ? C->d + pix0 * L : nullptr;
@@ -794,65 +787,6 @@ bool rel_enabled()
 {
     const char *e = getenv("MGM_HIP_REL");
     return !(e && atoi(e) == 0) && tune_num("rel", 1) != 0;
-}
-
-int rel_alloc(mgm_ctx *c, mgm_cv *cv, int slots, int cb)
-{
-    const size_t npix = (size_t)cv->nx * cv->ny, need = npix * (size_t)slots * (size_t)cb + npix * 16 + 16;
-    HIPCHK(c, hipSetDevice(c->device));
-    if (cv->rel_cap < need) {
-        if (cv->relbuf) {
-            HIPCHK(c, hipStreamSynchronize(c->stream));  // (a kernel may still be reading the old copy)
-            (void)hipFree(cv->relbuf);
-        }
-        cv->relbuf = nullptr;
-        cv->rel_cap = 0;
-        if (dev_malloc((void **)&cv->relbuf, need) == hipSuccess) cv->rel_cap = need;
-        else (void)hipGetLastError();
-    }
-    cv->rel_slots = slots;
-    cv->rel_cb = cb;
-    return MGM_OK;
-}
-
-int rel_resolve(mgm_ctx *c, const mgm_cv *ccv, bool *usable)
-{
-    mgm_cv *cv = const_cast<mgm_cv *>(ccv);
-    *usable = false;
-    if (!cv->rlo || !cv->relbuf || cv->rel_state == 0 || cv->rel_state == -1) return MGM_OK;
-    if (cv->rel_state == 1) {
-        HIPCHK(c, hipSetDevice(c->device));
-        if (int r = ensure_words(c)) return r;
-        // the flag word of the gathered copy: bit 0 = a window wider than the format's slots - 2, bit 1 = a cost without the format's
-        // code.  (round 6) The copy is then gathered again one step wider -- 64 -> 128 slots, one -> two bytes per cost -- while the
-        // fp32 hull it is gathered from is current; what fits neither keeps the dense hull.
-        for (int round = 0; round < 4; round++) {
-            HIPCHK(c, hipMemcpyAsync(c->h_words + 3, cv->rel_flag(), 4, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-            const unsigned f = c->h_words[3];
-            if (f == 0u) {
-                cv->rel_state = 2;
-                break;
-            }
-            const int slots = (f & 1u) ? cv->rel_slots * 2 : cv->rel_slots, cb = (f & 2u) ? cv->rel_cb * 2 : cv->rel_cb;
-            if (slots > 128 || cb > 4 || !cv->f32_state || !cv->d || tune_num("rel_wide", 1) == 0) {  // (cb 4: the fp32 cost itself)
-                cv->rel_state = -1;
-                break;
-            }
-            if (int r = rel_alloc(c, cv, slots, cb)) return r;
-            if (!cv->relbuf) {
-                cv->rel_state = -1;
-                break;
-            }
-            HIPCHK(c, hipMemsetAsync(cv->rel_flag(), 0, 4, c->stream));
-            TimeScope t(c, "k_rel_gather");
-            HIPCHK(c, launch_rel_gather(cv->d, cv->rlo, cv->rhi, (long long)cv->nx * cv->ny, cv->dmax - cv->dmin + 1, cv->dmin, slots, cb, cv->relbuf,
-                                        cv->rel_records(), cv->rel_flag(), c->stream));
-        }
-        if (cv->rel_state == 1) cv->rel_state = -1;
-    }
-    *usable = cv->rel_state == 2;
-    return MGM_OK;
 }
 
 int run_wta_rel(mgm_ctx *c, const mgm_cv *C, int slot, int NDIR, int fix_overcount, int ridx, const float *wlo, const float *whi, float *out,

@@ -55,11 +55,11 @@ def fill_format(spec, L):
     if spec["kind"] == "ragged":
         w = spec["half"] * 2 + 1
         return "r64" if w <= 56 else ("r128" if w <= 120 else "f32")
-    if not clean or cost in ("ncc", "btad", "census2", "census3c", "adh", "census1h"):
+    if not clean or cost in ("ncc", "btad", "census2", "adh"):  # (census1h: bit counts, whatever the pixels are; census3c: 24 bits, one word)
         return "f32"
     if L == 151:
         return "pad"
-    if cost == "census1":
+    if cost in ("census1", "census1h", "census3c"):
         return "c8"
     return "d2" if cost in ("ad3", "sd") else "d1"
 
@@ -72,12 +72,13 @@ def planner_sig(op, model):
                 passes=op["NDIR"], wantS=op["wantS"])
 
 
-def cost_bytes(cost, trunc):
-    """Bytes per cost of the copy the pass kernels read: one (bit counts, grey differences), two (colour / squared differences), four."""
+def cost_bytes(cost, trunc, ragged=False):
+    """Bytes per cost of the copy the pass kernels read: one (bit counts, grey differences), two (colour / squared differences; the
+    gathered copy of a ragged volume of differences of filtered images), four."""
     clean = trunc == math.inf or (trunc >= 0 and math.copysign(1, trunc) > 0 and float(trunc).is_integer())
-    if not clean or cost not in ("census1", "ad", "sobel", "ad3", "sd"):
+    if not clean or cost not in ("census1", "census1h", "census3c", "ad", "sobel", "ad3", "sd"):
         return 4
-    return 2 if cost in ("ad3", "sd") else 1
+    return 2 if cost in ("ad3", "sd") or (ragged and cost == "sobel") else 1
 
 
 def _new_vol(L, fmt="none"):
@@ -140,7 +141,7 @@ class Generator:
         hist.append(kind)
         if hist[-3:] == ["ragged", "uniform", "ragged"]:
             self.ru_r += 1
-        v.update(alive=True, kind=kind, fmt=fmt, nan=False, cb=cost_bytes(cost, trunc), spec=dict(kind=kind, cost=cost, half=half, trunc=trunc))
+        v.update(alive=True, kind=kind, fmt=fmt, nan=False, cb=cost_bytes(cost, trunc, kind == "ragged"), spec=dict(kind=kind, cost=cost, half=half, trunc=trunc))
         self.bump(name)
 
     def upload(self, name):
