@@ -1,6 +1,7 @@
 // mgm_post.hip -- the steps main() applies to the disparity maps right after the path:
 //
 //   median_filter      img_tools.h:203-238   NaN-aware, window clipped at the border, upper median v[n/2]
+//                                            (of the total order: -0 below +0, in both kernels -- DESIGN section 1)
 //   leftright_test     mgm.cc:68-91          |x - (Lx + R[Lx])| > tau, or Lx outside the other image  =>  NaN
 //   back-projection    mgm.cc:433-443        v sampled at x + d (the reference's float index arithmetic), else u
 //
@@ -22,11 +23,12 @@ __global__ void __launch_bounds__(256) k_median(const float *__restrict__ u, int
     const float *pl = u + (idx / npix) * npix;
     const int x0 = x - radius < 0 ? 0 : x - radius, x1 = x + radius >= nx ? nx - 1 : x + radius;
     const int y0 = y - radius < 0 ? 0 : y - radius, y1 = y + radius >= ny ? ny - 1 : y + radius;
-    int n = 0;
+    int n = 0, below = 0;  // samples; samples that order before +0 (the negative ones and the negative zeros)
     for (int j = y0; j <= y1; j++)
         for (int i = x0; i <= x1; i++) {
             const float s = pl[i + (long long)j * nx];
             n += (s == s);
+            below += (s < 0.0f) || (__builtin_bit_cast(unsigned, s) == 0x80000000u);
         }
     float res = pl[p];  // an all-NaN window leaves the pixel as it is
     if (n > 0) {
@@ -44,6 +46,10 @@ __global__ void __launch_bounds__(256) k_median(const float *__restrict__ u, int
                     }
                 if (less <= k && k < less + equal) res = s;
             }
+        // `t == s` counts both zeros as one value and keeps whichever was met last.  The rule is the total order, -0 below
+        // +0 (what k_median_big's keys give): rank k is a negative zero iff it lies below (#negative samples) + (#negative zeros),
+        // which the sweep that counted the samples has counted too (no further sweep: docs/experiments.md).
+        if (res == 0.0f) res = k < below ? -0.0f : 0.0f;
     }
     out[idx] = res;
 }

@@ -56,6 +56,7 @@ def test_windowed_wta_matches_restatement(ctx, oracle, fix):
 
 
 def test_update_ranges_restatement(ctx):
+    from oracle import post
     nx, ny = 37, 19
     rng = np.random.default_rng(9)
     d = rng.integers(-30, 10, size=(ny, nx)).astype(np.float32) + rng.random((ny, nx)).astype(np.float32)
@@ -64,17 +65,7 @@ def test_update_ranges_restatement(ctx):
     hi = np.full((ny, nx), 20, np.float32)
     dl, dh = ctx.upload_image(lo), ctx.upload_image(hi)
     ctx.update_ranges_dev(ctx.upload_image(d), dl, dh, 3, 2)
-    gmin, gmax = np.nanmin(d), np.nanmax(d)
-    want_lo, want_hi = lo.copy(), hi.copy()
-    for y in range(ny):
-        for x in range(nx):
-            a, b = np.float32(np.inf), np.float32(-np.inf)
-            for dy in range(-2, 3):
-                for dx in range(-2, 3):
-                    v = d[min(max(y + dy, 0), ny - 1), min(max(x + dx, 0), nx - 1)]
-                    a = min(a, (v if np.isfinite(v) else gmin) - np.float32(3))
-                    b = max(b, (v if np.isfinite(v) else gmax) + np.float32(3))
-            want_lo[y, x], want_hi[y, x] = a, b
+    want_lo, want_hi = post.update_ranges(d, lo, hi, 3, 2)  # (mgm.cc:120-158 + 387-388, pinned on the reference by test_post_ref.py)
     assert ndiff(dl.download()[0], want_lo) == 0 and ndiff(dh.download()[0], want_hi) == 0
 
 
