@@ -261,6 +261,12 @@ int mgm_multi_aggregate(mgm_multi *m, const mgm_cv *const *C, const mgm_img *con
  * call on this ctx into `dense` ([ny][nx][L]). */
 int mgm_debug_download_lr(mgm_ctx *ctx, int pass, float *dense);
 
+/* Test/diagnostic aid: what the pruned winner searches of the context's LAST aggregation call did -- pixels searched and
+ * chunks of 32 labels whose Lr values were loaded (a plain search loads L/32 per pixel), summed over the call's volumes.
+ * Counted only while timing (mgm_timing_enable) or MGM_HIP_DEBUG_STATS is on; both 0 when no search of that call was a
+ * pruned one (fall-back cases, MGM_HIP_WTA_PRUNE=0) or nothing was counted. */
+int mgm_debug_wta_stats(mgm_ctx *ctx, unsigned long long *pixels, unsigned long long *chunks);
+
 /* Diagnostic (tools/bimodal_probe.py): the rate, in GB/s, at which the store pattern of the pass kernels -- `nstreams`
  * volumes at the stride of the context's last aggregation, written side by side -- lands on the Lr workspace where the
  * allocator placed it.  MGM_ERR_INVALID before the context's first aggregation. */

@@ -72,6 +72,7 @@ static int aggregate_batch_now(mgm_ctx *c, int n, const mgm_cv *const *C, const 
     const long long npix = (long long)nx * ny;
     if (S)
         for (int v = 0; v < n; v++) S[v] = nullptr;
+    c->wta_stats_n = 0;  // (mgm_debug_wta_stats: the pruned searches of THIS call)
     // Ragged volumes whose range-proportional copies are usable take the kernels that walk the pixels' own windows
     // (mgm_pass_rel.hip): not when S is wanted (a dense volume), with TSGM = 2 (unweighted: other update functions), with
     // P2 = +INF (all-INF slabs: the operand-order-faithful kernel).
@@ -144,16 +145,20 @@ static int aggregate_batch_now(mgm_ctx *c, int n, const mgm_cv *const *C, const 
     // the largest sub-batches that do -- multiples of four / two volumes first, so that volumes keep sharing waves at
     // 64 / 128 labels -- instead of failing with MGM_ERR_NOMEM: same results, the later volumes just wait their turn.
     int chunk = n;
+    // what the winner search behind the launch will be: run_passes decides with it whether the launch writes the chunk minima
+    // the pruned search reads (mgm_planner.h, plan_wta_prune)
+    const bool search_S = S != nullptr;
     if (c->ws_limit) {
         const int Lk = padded_labels(L) ? padded_labels(L) : L;
-        const double per_vol = 4.0 * ((double)npix * Lk + (double)lr_pad_floats()) * NDIR * 1.07;  // (+ the hand-off slots: ~7 %)
+        // (+ the hand-off slots: ~7 %; + the chunk minima where a launch may write them: one float per 32 of Lr)
+        const double per_vol = 4.0 * ((double)npix * Lk + (double)lr_pad_floats()) * NDIR * (1.07 + ((L == 256 && !S && ridx <= 1 && wta_prune_enabled()) ? 1.0 / kChunkLabels : 0.0));
         while (chunk > 1 && per_vol * chunk > (double)c->ws_limit) chunk--;
         if (chunk >= 4) chunk -= chunk % 4;
         else if (chunk == 3) chunk = 2;
     }
     for (int v0 = 0; v0 < n && !r;) {
         int m = std::min(chunk, n - v0);
-        r = run_passes(c, C + v0, (w8 && w8[0]) ? w8 + v0 : nullptr, m, P1, P2, MGM, use_fh, 0, NDIR, /*allow_pad=*/true);
+        r = run_passes(c, C + v0, (w8 && w8[0]) ? w8 + v0 : nullptr, m, P1, P2, MGM, use_fh, 0, NDIR, /*allow_pad=*/true, 0, 0, 0, ridx, search_S);
         // mgm_ctx_set_placement_tries: the workspace has just been (re)allocated -- time this very launch on a few physical
         // placements and keep the fastest (the launch is idempotent: same inputs, same Lr volumes, whichever allocation)
         if (r == MGM_OK && c->place_tries >= 2 && c->lr.p && (c->lr.p != c->placed_ptr || c->lr.cap != c->placed_cap) && c->lr.cap >= (1ull << 28)) {
@@ -165,7 +170,7 @@ static int aggregate_batch_now(mgm_ctx *c, int n, const mgm_cv *const *C, const 
                 HIPCHK(c, hipEventCreate(&a.e));
                 HIPCHK(c, hipEventCreate(&b.e));
                 HIPCHK(c, hipEventRecord(a.e, c->stream));
-                int rr = run_passes(c, C + v0, (w8 && w8[0]) ? w8 + v0 : nullptr, m, P1, P2, MGM, use_fh, 0, NDIR, true);
+                int rr = run_passes(c, C + v0, (w8 && w8[0]) ? w8 + v0 : nullptr, m, P1, P2, MGM, use_fh, 0, NDIR, true, 0, 0, 0, ridx, search_S);
                 if (rr == MGM_OK) {
                     HIPCHK(c, hipEventRecord(b.e, c->stream));
                     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -187,14 +192,14 @@ static int aggregate_batch_now(mgm_ctx *c, int n, const mgm_cv *const *C, const 
                 Buf old = c->lr;
                 c->lr = Buf{};
                 float ms = 0;
-                int rr = run_passes(c, C + v0, (w8 && w8[0]) ? w8 + v0 : nullptr, m, P1, P2, MGM, use_fh, 0, NDIR, true);  // allocates; warm-up
+                int rr = run_passes(c, C + v0, (w8 && w8[0]) ? w8 + v0 : nullptr, m, P1, P2, MGM, use_fh, 0, NDIR, true, 0, 0, 0, ridx, search_S);  // allocates; warm-up
                 if (rr == MGM_OK) rr = timed(&ms);
                 if (rr != MGM_OK) {  // (out of memory after all: back to what we had)
                     if (c->lr.p) (void)hipFree(c->lr.p);
                     c->lr = old;
                     (void)hipGetLastError();
                     c->err.clear();
-                    r = run_passes(c, C + v0, (w8 && w8[0]) ? w8 + v0 : nullptr, m, P1, P2, MGM, use_fh, 0, NDIR, true);
+                    r = run_passes(c, C + v0, (w8 && w8[0]) ? w8 + v0 : nullptr, m, P1, P2, MGM, use_fh, 0, NDIR, true, 0, 0, 0, ridx, search_S);
                     break;
                 }
                 if (tune_num("show_plan", 0)) fprintf(stderr, "[mgm place] try %d: %.3f ms (best so far %.3f)\n", t, ms, best);
@@ -204,7 +209,7 @@ static int aggregate_batch_now(mgm_ctx *c, int n, const mgm_cv *const *C, const 
                 } else {  // keep the old one: hold the new one instead, and run the launch on the old workspace again (its Lr volumes are what k_wta reads)
                     held.push_back(c->lr);
                     c->lr = old;
-                    r = run_passes(c, C + v0, (w8 && w8[0]) ? w8 + v0 : nullptr, m, P1, P2, MGM, use_fh, 0, NDIR, true);
+                    r = run_passes(c, C + v0, (w8 && w8[0]) ? w8 + v0 : nullptr, m, P1, P2, MGM, use_fh, 0, NDIR, true, 0, 0, 0, ridx, search_S);
                 }
             }
             HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -436,6 +441,23 @@ int mgm_debug_download_lr(mgm_ctx *c, int pass, float *dense)
                                sizeof(float) * c->last_Lk, sizeof(float) * c->last_L, (size_t)(c->last_nvol / c->last_Lk),
                                hipMemcpyDeviceToHost, c->stream));
     return mgm_ctx_synchronize(c);
+}
+
+int mgm_debug_wta_stats(mgm_ctx *c, unsigned long long *pixels, unsigned long long *chunks)
+{
+    if (int jr = pipe_join(c)) return jr;  // (pipelined context: run what has been deferred first)
+    if (!c || !pixels || !chunks) return fail(c, MGM_ERR_INVALID, "mgm_debug_wta_stats: null argument");
+    *pixels = *chunks = 0;
+    if (c->wta_stats_n == 0 || !c->wta_stats.p) return MGM_OK;  // no search of the last aggregation call was a counted pruned one
+    HIPCHK(c, hipSetDevice(c->device));
+    std::vector<unsigned long long> w(kWtaStatBytes / sizeof(unsigned long long));
+    HIPCHK(c, hipMemcpyAsync(w.data(), c->wta_stats.p, kWtaStatBytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (int k = 0; k < kWtaStatSlots; k++) {  // (pixels << 32 | chunks per slot)
+        *pixels += w[(size_t)k * 16] >> 32;
+        *chunks += w[(size_t)k * 16] & 0xffffffffull;
+    }
+    return MGM_OK;
 }
 
 // ---- self-tests -------------------------------------------------------------------

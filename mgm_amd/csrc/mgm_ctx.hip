@@ -210,7 +210,7 @@ int mgm_ctx_destroy(mgm_ctx *c)
     (void)pipe_join(c);  // (deferred calls of a pipelined context still write the caller's images)
     (void)hipStreamSynchronize(c->stream);
     std::vector<Buf *> bufs = {&c->lr, &c->hand, &c->hand2, &c->handm, &c->exact_mins, &c->exact_scratch, &c->words, &c->census_u, &c->census_v, &c->dbg, &c->stmp, &c->ones8,
-                               &c->lr_rel, &c->hand_rel};  // (the range-proportional kernels' workspace: round 5 forgot it here)
+                               &c->lr_rel, &c->hand_rel, &c->lmin, &c->wta_stats};  // (the range-proportional kernels' workspace: round 5 forgot it here)
     for (int v = 0; v < kMaxBatch; v++) {
         bufs.push_back(&c->padf[v]);
         bufs.push_back(&c->pad8[v]);
@@ -252,7 +252,9 @@ int mgm_ctx_trim(mgm_ctx *c)
     HIPCHK(c, hipSetDevice(c->device));
     if (int r = mgm_ctx_synchronize(c)) return r;
     std::vector<Buf *> bufs = {&c->lr, &c->hand, &c->hand2, &c->handm, &c->exact_mins, &c->exact_scratch, &c->census_u, &c->census_v, &c->dbg, &c->stmp, &c->ones8,
-                               &c->lr_rel, &c->hand_rel};
+                               &c->lr_rel, &c->hand_rel, &c->lmin, &c->wta_stats};
+    c->last_min = false;
+    c->wta_stats_n = 0;
     c->hand_rel_key = HandLayout{};
     c->rel_last_batch = 0;
     for (int v = 0; v < kMaxBatch; v++) {

@@ -51,6 +51,10 @@ struct PassParams {
     unsigned long long *dbg;  // nullptr, or 8 words per ticket of timing diagnostics (MGM_HIP_DEBUG_STATS)
     unsigned long long tl_addr;  // device address of 8 words per ticket: the queue kernels' timeline (-DMGM_P2_TIMELINE=1 builds; MGM_HIP_TIMELINE)
     int tl_on;                   // ... 1: record it
+    long long min_k;    // 0: no chunk minima.  Else the compute waves of k_pass2 (CHMIN) store, per pass, pixel and chunk of 32 labels, the
+                        // minimum of Lr over the chunk -- one float per 32 of the Lr workspace, at (index of the chunk's first Lr
+                        // float) / 32: the word of the chunk whose LAST 16 bytes start at byte address A is at (A >> 5) + min_k,
+                        // min_k = minima - (workspace >> 5) - 3 for a 32-byte aligned workspace
     long long npix, nvol;
     int L, MGM, NDIR, dmin;
     int fh2_ragged;     // 1: FH, TSGM = 2, no weights, ragged volume: update_cost2_trunclinear with its boundary fix-up
@@ -78,6 +82,10 @@ struct WtaParams {
     // ragged C (CostParams::rlo/rhi): a disparity outside the pixel's own range does not exist in C either
     const float *clo, *chi;
     int num_cu;                      // compute units of the device (grid sizing)
+    // the pruned search (k_wta_pruned): per pass, pixel and chunk of 32 labels the minimum of Lr over the chunk, written by the pass
+    // kernel (PassParams::min_k) -- word (p * nvol + pix * L) / 32 + chunk --, or nullptr: the plain search
+    const float *Lmin;
+    unsigned long long *stats;       // nullptr, or 64 words 128 bytes apart the pruned search's waves add (pixels << 32 | chunks loaded) to
 };
 
 // ---- ragged volumes in the range-proportional layout (mgm_pass_rel.hip, k_wta_rel): 64 label slots per pixel placed at the

@@ -135,6 +135,12 @@ struct mgm_ctx {
     // range-proportional aggregation of ragged volumes (mgm_pass_rel.hip): its Lr volumes [volume][pass][npix][64], hand-off slots,
     // and what the last such aggregation ran on (mgm_wta_windowed_dev searches it again)
     Buf lr_rel, hand_rel;
+    // chunk minima of the dense Lr volumes (k_pass2, CHMIN): one float per 32 of c->lr, written by the last dense launch iff
+    // last_min; the pruned winner search reads them (run_wta).  wta_stats: its two counters' word on the device (timing or
+    // debug statistics on), wta_stats_n: searches counted into it since the last aggregation call began (0: none was pruned)
+    Buf lmin, wta_stats;  // (wta_stats: kWtaStatBytes)
+    bool last_min = false;
+    int wta_stats_n = 0;
     int rel_last_batch = 0, rel_last_ndir = 0;
     int rel_last_slots = 0;  // label slots per pixel of volume 0's copy at that launch (the Lr stride mgm_debug_download_lr reads at)
     long long rel_last_stride = 0;
@@ -192,6 +198,8 @@ struct mgm_ctx {
 };
 
 
+constexpr int kWtaStatSlots = 64;  // the pruned search's counters: one word per 128 bytes, a workgroup adds to slot blockIdx.x % 64
+constexpr size_t kWtaStatBytes = (size_t)kWtaStatSlots * 128;
 constexpr int kCtrlWords = 4 + kMaxBatch * kMaxDirs * kMaxBands;  // ticket, err, flag, pad, prog[volume*8 + pass][maxbands]
 constexpr int kPyrWords = 4;  // behind the control block: the words of mgm_pyramid.hip (minimum / maximum of a coarse map, integer hull)
 
@@ -282,7 +290,8 @@ int rel_alloc(mgm_ctx *c, mgm_cv *cv, int slots, int cb);  // (re)allocates relb
 
 // the launch plan (mgm_plan.hip)
 int run_passes(mgm_ctx *c, const mgm_cv *const *Cs, const mgm_img *const *w8s, int nb, float P1, float P2, int MGM, int use_fh, int first,
-               int count, bool allow_pad = false, int slot0 = 0, int nslots = 0, int layout_ndir = 0);
+               int count, bool allow_pad = false, int slot0 = 0, int nslots = 0, int layout_ndir = 0, int search_refine = -1, bool search_S = false);
+bool wta_prune_enabled();  // MGM_HIP_WTA_PRUNE=0 (read at every call) or tune wta_prune=0: the plain winner search everywhere
 int run_wta(mgm_ctx *c, const mgm_cv *C, long long pix0, long long npix, const float *lr, long long lr_stride, int NDIR, int fix_overcount,
             int ridx, float *out, float *outcost, float *Sout, const float *wlo = nullptr, const float *whi = nullptr, int slot = -1);
 // the range-proportional path of ragged volumes (mgm_plan.hip): is this call one it takes?  then the passes + the winner search

@@ -334,6 +334,9 @@ __device__ __forceinline__ void pass2_item(const PassParams &P, const int ticket
     // have the time -- the FH kernels (cfg3 x 12: K3 50.1 -> 48.9 ms); the Hirschmueller kernels, whose loader is on the
     // critical path of a short step, lose 8-25 % with it (cfg2 x 16, cfg4) and keep decoding every byte.
     constexpr bool CFLAG = C8 && FH;
+    // Chunk minima of Lr for the pruned winner search (PassParams::min_k): the kernels cfg3-like launches run -- 256 labels, one
+    // volume per wave, one-byte costs, unit weights, slabs of E -- at either ring depth, with and without queues.
+    constexpr bool CHMIN = LPL == 4 && SUBV == 1 && C8 == 1 && !WEIGHTED && !W2 && pubE;
     using PL = Plan<LPL, NS, !pubE, C8, DEEP ? MGM_P2_DEEPD : MGM_P2_MAXD, W2 ? 1 : 0>;
     static_assert(!W2 || PL::NL == 1, "two-valued weights: one loader wave");
     constexpr int LP = PL::LP, NC = PL::NC, NCA = PL::NCA, D = PL::D, IPS = PL::IPS;
@@ -886,7 +889,27 @@ __device__ __forceinline__ void pass2_item(const PassParams &P, const int ticket
                     for (int k = 0; k < LPL; k++) q[k] = Lv[k];
                 }
                 float m;
-                if constexpr (SUBV == 1) {
+                if constexpr (CHMIN) {
+                    // slab_min's own reduction, with a look at it half-way: after the row_shr:4 step the last lane of every group
+                    // of eight holds the minimum of that group's 32 labels -- the chunk minima the pruned winner search bounds S
+                    // with (mgm_wta.hip, k_wta_pruned).  A label of +INF enters as +INF.  The minima are one float per 128 bytes of
+                    // the Lr workspace, so the word of the chunk whose last 16 bytes sit at byte address A is at (A >> 5) + min_k:
+                    // the address comes out of the slab pointer the lane holds anyway.  (A wave-uniform running pointer instead --
+                    // scalar adds, no VALU slot -- costs four live SGPRs: 10-20 more scalar spills in every FH instance and vector
+                    // spills in the queue kernels capped at 64 VGPRs.)
+                    m = Lv[0];
+#pragma unroll
+                    for (int k = 1; k < LPL; k++) m = fminf(m, Lv[k]);
+                    m = dpp_min_row_shr1(m, m);
+                    m = dpp_min_row_shr2(m, m);
+                    m = dpp_min_row_shr4(m, m);
+                    if (P.min_k != 0 && (lane & 7) == 7)  // (the first test is wave-uniform)
+                        *reinterpret_cast<float *>((long long)(reinterpret_cast<unsigned long long>(q_here) >> 5) + P.min_k) = m;
+                    m = dpp_min_row_shr8(m, m);
+                    m = dpp_min_bcast15(m, m);
+                    m = dpp_min_bcast31(m, m);
+                    m = readlane_f(m, 63);
+                } else if constexpr (SUBV == 1) {
                     m = slab_min<LPL>(Lv);
                 } else {  // one minimum per lane group
                     m = Lv[0];

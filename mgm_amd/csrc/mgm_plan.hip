@@ -98,6 +98,7 @@ static void remember_dense(mgm_ctx *c, const mgm_cv *const *Cs, int nb, long lon
                            const uint8_t *const *pad8)
 {
     c->rel_last_batch = 0;  // (an earlier range-proportional aggregation of the same volume is no longer the context's last)
+    c->last_min = false;    // (run_passes sets it behind a launch that wrote the chunk minima)
     c->last_nvol = nvol;
     c->last_stride = lr_stride;
     c->last_ndir = nslots;
@@ -117,6 +118,7 @@ static void remember_rel(mgm_ctx *c, const mgm_cv *const *Cs, int nb, int NDIR, 
     // (the dense Lr workspace no longer belongs to these volumes)
     c->last_batch = 0;
     c->last_ndir = 0;
+    c->last_min = false;
     for (int v = 0; v < kMaxBatch; v++) c->last_cvs[v] = nullptr;
     c->rel_last_batch = nb;
     c->rel_last_ndir = NDIR;
@@ -484,7 +486,7 @@ static int resolve_dense_operands(mgm_ctx *c, const mgm_cv *const *Cs, const mgm
 // (see PassVolume); volume v's Lr volumes end up at lr + v*nslots*lr_stride.  Shared by mgm_aggregate_dev and the
 // direction-sharded multi-GPU path.
 int run_passes(mgm_ctx *c, const mgm_cv *const *Cs, const mgm_img *const *w8s, int nb, float P1, float P2, int MGM,
-               int use_fh, int first, int count, bool allow_pad, int slot0, int nslots, int layout_ndir)
+               int use_fh, int first, int count, bool allow_pad, int slot0, int nslots, int layout_ndir, int search_refine, bool search_S)
 {
     if (nslots <= 0) nslots = slot0 + count;
     if (layout_ndir < first + count) layout_ndir = first + count;
@@ -543,6 +545,20 @@ int run_passes(mgm_ctx *c, const mgm_cv *const *Cs, const mgm_img *const *w8s, i
     const long long lr_stride = nvol + lr_pad_floats();
     if ((r = reserve(c, c->lr, sizeof(float) * (size_t)lr_stride * nslots * nb))) return r;
     PassParams p{};
+    // Chunk minima for the pruned winner search (mgm_planner.h, plan_wta_prune): one float per 32 of the Lr workspace, in a
+    // grow-only buffer of their own beside it; a launch that does not write them leaves none behind (remember_dense).
+    // search_refine >= 0: the caller's own search follows this launch (mgm_aggregate*, a pipelined context's flush included: both
+    // run inside one call, so the minima are still there) -- the direction-sharded and multi-device callers pass -1.
+    PruneRequest pq{};
+    pq.enabled = wta_prune_enabled() ? 1 : 0, pq.search_follows = search_refine >= 0 ? 1 : 0, pq.want_S = search_S ? 1 : 0, pq.refine = std::max(search_refine, 0);
+    pq.first = first, pq.count = count, pq.slot0 = slot0, pq.nslots = nslots, pq.L = L, pq.Lreal = Lreal, pq.ragged = o.ragged ? 1 : 0;
+    pq.R2 = R2, pq.subv = subv, pq.tags = tags ? 1 : 0, pq.w2 = w2 ? 1 : 0, pq.wk = wk ? 1 : 0, pq.lpl = q.lpl, pq.use_c8 = o.use_c8 ? 1 : 0, pq.cb = o.cb;
+    pq.stride_mod32 = (int)(lr_stride % 32);
+    const bool minima = plan_wta_prune(pq);
+    if (minima) {
+        if ((r = reserve(c, c->lmin, sizeof(float) * ((size_t)lr_stride * nslots * nb / kChunkLabels + 8)))) return r;
+        p.min_k = (long long)(uintptr_t)c->lmin.p - (long long)((uintptr_t)c->lr.p >> 5) - 3;
+    }
     // The second build's unweighted kernels hand slabs from band to band that validate themselves (mgm_pass2.hip, TAGS):
     // one slot per (volume, pass, band, pixel), written once per launch OF THAT PASS with the tag in the sign bits.  A
     // pass's tag alternates between its consecutive launches over the same slots; a different layout clears the region
@@ -704,7 +720,15 @@ int run_passes(mgm_ctx *c, const mgm_cv *const *Cs, const mgm_img *const *w8s, i
 
     // 7. what the context's last aggregation was: this dense one
     remember_dense(c, Cs, nb, nvol, lr_stride, nslots, Lreal, L, o.cb, (o.padded && o.use_c8) ? pad8 : nullptr);
+    c->last_min = minima;
     return MGM_OK;
+}
+
+// MGM_HIP_WTA_PRUNE=0 (read at every call: tests switch it inside one process): the plain winner search everywhere
+bool wta_prune_enabled()
+{
+    const char *e = getenv("MGM_HIP_WTA_PRUNE");
+    return !(e && atoi(e) == 0) && tune_num("wta_prune", 1) != 0;
 }
 
 // K4-K6 over `npix` pixels starting at pixel `pix0` of C, reading pass p's Lr from lr + p*lr_stride.
@@ -747,6 +771,20 @@ int run_wta(mgm_ctx *c, const mgm_cv *C, long long pix0, long long npix, const f
     w.clo = C->rlo ? C->rlo + pix0 : nullptr;
     w.chi = C->rhi ? C->rhi + pix0 : nullptr;
     w.num_cu = c->num_cu;
+    // The pruned search: the volume was slot `slot` of the context's last dense launch, that launch wrote the chunk minima of
+    // its Lr volumes (c->last_min: decided by plan_wta_prune for exactly this search) and `lr` is that slot's first volume.
+    if (slot >= 0 && c->last_min && c->lmin.p && !Sout && !wlo && !w.clo && ridx <= 1 && !padded && pix0 == 0 && w.C8 && w.cbytes == 1 && L == 256 &&
+        lr == (const float *)c->lr.p + (size_t)slot * NDIR * c->last_stride && lr_stride == c->last_stride && NDIR == c->last_ndir) {
+        w.Lmin = (const float *)c->lmin.p + (size_t)slot * NDIR * (size_t)(c->last_stride / kChunkLabels);
+        // its two counters (mgm_debug_wta_stats) only while somebody is looking: timing or debug statistics on
+        if ((c->timing || c->debug_stats) && npix < (1ll << 24)) {
+            const bool fresh = c->wta_stats.p == nullptr;
+            if (int r = reserve(c, c->wta_stats, kWtaStatBytes)) return r;
+            if (fresh || c->wta_stats_n == 0) HIPCHK(c, hipMemsetAsync(c->wta_stats.p, 0, kWtaStatBytes, c->stream));
+            w.stats = (unsigned long long *)c->wta_stats.p;
+            c->wta_stats_n++;
+        }
+    }
     TimeScope t(c, "k_wta");
     HIPCHK(c, launch_wta(w, c->stream));
     return MGM_OK;

@@ -278,6 +278,36 @@ inline std::vector<SimChain> make_chains(const PassGeom *geoms, int ngroups, int
     return ch;
 }
 
+// ---- the pruned winner search (k_wta_pruned, mgm_wta.hip) ------------------------------------------------------------------
+// Does this launch of the pass kernel write the chunk minima of Lr (PassParams::min_k), and does the winner search behind it
+// read them instead of every Lr slab?  A function of the values below and nothing else; a request of its own because
+// DenseRequest is what the task tables are cached by, and the table does not depend on this.
+//   * the kernels that write minima: the second build's 256-label instances with one volume per wave, one-byte compact
+//     costs, unit weights and slabs of E (k_pass2, CHMIN) -- what cfg3 / cfg3h run at any batch size;
+//   * a search that can use them: the caller's own, right behind the launch, over all passes of the volume (not the
+//     direction-sharded or multi-device building blocks, whose search runs elsewhere or on other slabs), no S volume
+//     wanted, refinement none or vfit, no padded label slots, no per-pixel ranges;
+//   * MGM_HIP_WTA_PRUNE=0 (`enabled` 0) keeps the plain search for A/B runs and tests.
+struct PruneRequest {
+    int enabled;            // the environment switch
+    int search_follows;     // the caller searches all passes of every volume right behind this launch (mgm_aggregate*)
+    int want_S, refine;     // the search writes the corrected volume; refinement index (0 none, 1 vfit, 2.. a second kernel on S)
+    int first, count, slot0, nslots;  // passes of the launch and where their volumes go
+    int L, Lreal, ragged;   // label slots the kernels see, labels that exist, per-pixel ranges
+    int R2, subv, tags, w2, wk, lpl;  // the plan's decisions (DensePlan) and the kernels' labels per lane
+    int use_c8, cb;         // compact costs, bytes per cost
+    int stride_mod32;       // floats between consecutive Lr volumes, modulo 32 (a chunk's word is found by its address)
+};
+static_assert(std::has_unique_object_representations_v<PruneRequest>, "PruneRequest: integers only, no padding");
+constexpr int kChunkLabels = 32;  // labels per chunk minimum: 128 bytes of an Lr slab
+inline bool plan_wta_prune(const PruneRequest &q)
+{
+    const bool kernel_writes = q.R2 != 0 && q.lpl == 4 && q.L == 256 && q.subv == 1 && q.tags != 0 && q.w2 == 0 && q.wk == 0 && q.use_c8 != 0 && q.cb == 1;
+    const bool search_reads = q.search_follows != 0 && q.want_S == 0 && (q.refine == 0 || q.refine == 1) && q.Lreal == q.L && q.ragged == 0 && q.first == 0 &&
+                              q.slot0 == 0 && q.nslots == q.count;
+    return q.enabled != 0 && kernel_writes && search_reads && q.stride_mod32 == 0;
+}
+
 // ---- the dense kernels (k_pass / k_pass2) --------------------------------------------------------------------------------
 enum { kPlanOk = 0, kPlanNotCanonical = 1, kPlanTooManyBands = 2, kPlanLostQueues = 3 };
 struct DensePlan {

@@ -398,8 +398,223 @@ __global__ void __launch_bounds__(256) k_wta_any(const WtaParams P)
     }
 }
 
+// ---- the pruned search (256 labels, one-byte compact costs, no padding / window / ranges, refinement none or vfit) -----------
+// The pass kernel leaves, per pass, pixel and CHUNK of 32 labels (128 bytes of the slab, eight lanes here), the minimum of Lr over
+// the chunk (PassParams::min_k).  Put the chunk minimum in the place of every Lr value of the sum and the same arithmetic gives a
+// lower bound: fp32 addition and s - f*c are monotone in every operand, so
+//     LB(d) = sum_fix(m_0(chunk(d)), ..., m_{N-1}(chunk(d)); C(d)) <= sum_fix(L_0(d), ..., L_{N-1}(d); C(d)) = S(d)
+// bit for bit, no epsilon -- as long as both sides are evaluated by the same operations in the same order (sum_fix, below).  The
+// winner needs the exact S only where it can lie:
+//   (a) costs + N*8 minima of the pixel -> LB of every label; a label with C = +INF is out (its S is never finite);
+//   (b) the chunk with the smallest LB (the lowest one on ties) loads its Lr pieces: best0 = its smallest finite S (+INF: none);
+//   (c) every other chunk with some LB <= best0 loads too, in one round -- best0 can only fall, and `<=` keeps a tie at a lower
+//       label in play; a chunk that stays out has S >= LB > best0 on all its labels;
+//   (d) first strict minimum among the finite S of what was loaded, by rising label; vfit reads S at the winner's neighbours,
+//       from the staged chunks or -- the neighbour lies in a chunk that stayed out -- recomputed from memory;
+//   (e) nothing finite: NaN label, +INF cost, as in k_wta.
+// On census volumes 1.8-2 of the 8 chunks of a pixel are loaded: 2.4 KB per pixel instead of 8.4.
+template <int MAXD>
+__device__ __forceinline__ void sum_fix(const float (&l)[MAXD][4], const float (&c)[4], int ndir, int fix, float (&S)[4])
+{
+    // S = ((0 + L0) + L1) + ... in pass order, then the over-count term (mgm_core.cc:582-599): k_wta's operations, in its order
+#pragma unroll
+    for (int k = 0; k < 4; k++) S[k] = 0.0f;
+#pragma unroll
+    for (int p = 0; p < MAXD; p++)
+        if (p < ndir) {
+#pragma unroll
+            for (int k = 0; k < 4; k++) S[k] = S[k] + l[p][k];
+        }
+    if (fix == 1) {
+        const float f = (float)(ndir - 1);
+#pragma unroll
+        for (int k = 0; k < 4; k++) S[k] = S[k] - f * c[k];
+    }
+}
+template <int CTRL>
+__device__ __forceinline__ float dpp_fmin(float v)  // min with the lane CTRL names (every lane has one)
+{
+    return __builtin_fminf(v, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, false)));
+}
+// PPW: pixels per wave and iteration (their loads go out together).  MAXD: upper bound of NDIR; ALLD: NDIR == MAXD, known at
+// compile time (4 and 8 directions: no test per pass around the loads).
+template <int PPW, int MAXD, bool ALLD>
+__global__ void __launch_bounds__(256) k_wta_pruned(const WtaParams P)
+{
+    constexpr int L = 256;
+    __shared__ float sS[4][PPW][L];
+    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int ch = lane >> 3;   // this lane's chunk
+    const int o0 = lane * 4;    // its first label
+    const int ndir = ALLD ? MAXD : P.NDIR, fix = P.FIX;
+    const long long mstride = P.nvol / 32;  // chunk minima per pass
+    unsigned nloaded = 0, npx = 0;          // (mgm_debug_wta_stats) of this wave
+    for (long long g0 = ((long long)blockIdx.x * 4 + wv) * PPW; g0 < P.npix; g0 += (long long)gridDim.x * 4 * PPW) {
+        // (a) costs and minima
+        unsigned cw[PPW];
+        float mn[PPW][MAXD];
+#pragma unroll
+        for (int u = 0; u < PPW; u++) {
+            const long long pix = g0 + u < P.npix ? g0 + u : P.npix - 1;
+            cw[u] = *reinterpret_cast<const unsigned *>(P.C8 + pix * L + o0);
+#pragma unroll
+            for (int p = 0; p < MAXD; p++)
+                if (p < ndir) mn[u][p] = P.Lmin[(long long)p * mstride + pix * (L / 32) + ch];
+        }
+        float c[PPW][4], clb[PPW];
+        int seed[PPW];  // the seed chunk, -1: no label can hold a finite S
+#pragma unroll
+        for (int u = 0; u < PPW; u++) {
+            float lm[MAXD][4], LB[4];
+#pragma unroll
+            for (int k = 0; k < 4; k++) c[u][k] = c8_decode((cw[u] >> (8 * k)) & 255u);
+#pragma unroll
+            for (int p = 0; p < MAXD; p++)
+#pragma unroll
+                for (int k = 0; k < 4; k++) lm[p][k] = p < ndir ? mn[u][p] : 0.0f;
+            sum_fix<MAXD>(lm, c[u], ndir, fix, LB);
+            float lb = f_inf();
+#pragma unroll
+            for (int k = 0; k < 4; k++) lb = c[u][k] < f_inf() ? __builtin_fminf(lb, LB[k]) : lb;
+            lb = lb == lb ? lb : -f_inf();  // (a NaN bound bounds nothing: such a chunk always loads.  The pass kernels are NaN-free)
+            lb = dpp_fmin<0xB1>(lb);   // quad_perm [1,0,3,2]
+            lb = dpp_fmin<0x4E>(lb);   // quad_perm [2,3,0,1]
+            lb = dpp_fmin<0x141>(lb);  // row_half_mirror: all eight lanes hold the chunk's smallest bound
+            clb[u] = lb;
+            const float gmin = wave_min(lb);
+            const unsigned long long at = __builtin_amdgcn_ballot_w64(lb == gmin);
+            seed[u] = gmin < f_inf() ? (int)(__builtin_ctzll(at) >> 3) : -1;
+        }
+        // (b) the seed chunks.  No lane sits a load out: the lanes of the other chunks fetch the seed chunk's pieces as well (the
+        // same 128 bytes eight times over: one line from memory) and drop them -- straight-line code, no exec-masked branches
+        // around the loads, so the requests of all passes (and pixels) go out back to back
+        float S[PPW][4];
+        bool act[PPW];
+        float best0[PPW];
+        {
+            float l[PPW][MAXD][4];
+#pragma unroll
+            for (int u = 0; u < PPW; u++) {
+                const long long pix = g0 + u < P.npix ? g0 + u : P.npix - 1;
+                act[u] = ch == seed[u];
+                const float *q0 = P.Lr + pix * L + (seed[u] > 0 ? seed[u] : 0) * 32 + (lane & 7) * 4;
+#pragma unroll
+                for (int p = 0; p < MAXD; p++)
+                    if (p < ndir) {
+                        const float4 q = *reinterpret_cast<const float4 *>(q0 + (long long)p * P.nvol);
+                        l[u][p][0] = q.x, l[u][p][1] = q.y, l[u][p][2] = q.z, l[u][p][3] = q.w;
+                    }
+            }
+#pragma unroll
+            for (int u = 0; u < PPW; u++) {
+                sum_fix<MAXD>(l[u], c[u], ndir, fix, S[u]);  // (means something in the seed chunk's lanes only)
+                float b = f_inf();
+#pragma unroll
+                for (int k = 0; k < 4; k++) b = (act[u] && finite_bits(S[u][k]) && S[u][k] < b) ? S[u][k] : b;
+                best0[u] = wave_min(b);
+            }
+        }
+        // (c) every other chunk that can still hold the winner loads its own pieces; the rest fetch the seed chunk's again (cached)
+        bool act2[PPW];
+        {
+            float l[PPW][MAXD][4];
+#pragma unroll
+            for (int u = 0; u < PPW; u++) {
+                const long long pix = g0 + u < P.npix ? g0 + u : P.npix - 1;
+                act2[u] = !act[u] && seed[u] >= 0 && clb[u] <= best0[u];
+                const float *q0 = P.Lr + pix * L + (act2[u] ? ch : (seed[u] > 0 ? seed[u] : 0)) * 32 + (lane & 7) * 4;
+#pragma unroll
+                for (int p = 0; p < MAXD; p++)
+                    if (p < ndir) {
+                        const float4 q = *reinterpret_cast<const float4 *>(q0 + (long long)p * P.nvol);
+                        l[u][p][0] = q.x, l[u][p][1] = q.y, l[u][p][2] = q.z, l[u][p][3] = q.w;
+                    }
+            }
+#pragma unroll
+            for (int u = 0; u < PPW; u++) {
+                float S2[4];
+                sum_fix<MAXD>(l[u], c[u], ndir, fix, S2);
+#pragma unroll
+                for (int k = 0; k < 4; k++) S[u][k] = act[u] ? S[u][k] : S2[k];
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < PPW; u++) {
+            if (g0 + u >= P.npix) break;
+            const long long pix = g0 + u;
+            const bool have = act[u] || act2[u];
+            const unsigned long long lmask = __builtin_amdgcn_ballot_w64(have);  // bit 8*c: chunk c was loaded
+            nloaded += (unsigned)__builtin_popcountll(lmask & 0x0101010101010101ull);
+            npx++;
+            // (d) first strict minimum among the finite entries, ascending label
+            float best = f_inf();
+            int bi = 0x7fffffff;
+            if (have) {
+#pragma unroll
+                for (int k = 0; k < 4; k++)
+                    if (finite_bits(S[u][k]) && best > S[u][k]) {
+                        best = S[u][k];
+                        bi = o0 + k;
+                    }
+            }
+            const float gbest = wave_min(best);
+            const unsigned long long who = __builtin_amdgcn_ballot_w64(bi != 0x7fffffff && best == gbest);
+            best = gbest;
+            bi = who ? __builtin_amdgcn_readlane(bi, (int)__builtin_ctzll(who)) : 0x7fffffff;  // (lanes hold rising labels)
+            float outv, outc = best;
+            if (bi == 0x7fffffff) outv = __builtin_nanf("");  // the reference leaves minP uninitialised here
+            else outv = (float)(bi + P.dmin);
+            if (P.refine == 1) {  // (wave-uniform)
+                if (have) {
+#pragma unroll
+                    for (int k = 0; k < 4; k++) sS[wv][u][o0 + k] = S[u][k];
+                }
+                if (bi != 0x7fffffff && bi - 1 >= 0 && bi + 2 <= L - 1) {  // mgm_refine.h:58
+                    auto S_at = [&](int o) -> float {  // (o is wave-uniform)
+                        if ((lmask >> ((o >> 5) * 8)) & 1ull) return sS[wv][u][o];
+                        float a = 0.0f;
+                        for (int p = 0; p < ndir; p++) a = a + P.Lr[(long long)p * P.nvol + pix * L + o];
+                        if (fix == 1) a = a - (float)(ndir - 1) * c8_decode(P.C8[pix * L + o]);
+                        return a;
+                    };
+                    const float v0 = S_at(bi - 1), v1 = S_at(bi), v2 = S_at(bi + 1);
+                    float vmin, dx;
+                    vfit(v0, v1, v2, vmin, dx);
+                    outv = (float)(bi + P.dmin) + dx;
+                    outc = vmin;
+                }
+            }
+            if (lane == 0) {
+                P.out[pix] = outv;
+                P.outcost[pix] = outc;
+            }
+        }
+    }
+    // one atomic per wave, spread over 64 words 128 bytes apart: one per wave ITERATION on one word (the first version) serialised
+    // a million atomics on one address and took the kernel from 1.x to 12 ms
+    if (P.stats && lane == 0) atomicAdd(P.stats + (blockIdx.x & 63) * 16, ((unsigned long long)npx << 32) | nloaded);
+}
+
 hipError_t launch_wta(const WtaParams &p, hipStream_t s)
 {
+    if (p.Lmin) {  // the pruned search (run_wta has checked what it needs: 256 labels, no padding, one-byte compact costs, ...)
+        if (p.L != 256 || p.Lreal != 256 || !p.C8 || p.cbytes != 1 || p.S || p.wlo || p.clo || p.refine > 1 || p.nvol % 32 != 0) return hipErrorInvalidValue;
+        static int ppw = -1, wgs = -1;  // MGM_HIP_TUNE=wta_prune_ppw=1|2, wta_prune_wg=<workgroups per CU> (A/B timing)
+        if (ppw < 0) ppw = (int)tune_num("wta_prune_ppw", 2);
+        if (wgs < 0) wgs = (int)tune_num("wta_prune_wg", 0);
+        const int pw = (ppw == 1 || (p.NDIR != 4 && p.NDIR != 8)) ? 1 : 2;
+        long long nb = (p.npix + 4 * pw - 1) / (4 * pw);
+        const long long cap = (long long)(p.num_cu > 0 ? p.num_cu : 256) * (wgs > 0 ? wgs : 64);
+        if (nb > cap) nb = cap;
+        const dim3 grid((unsigned)nb), block(256);
+        if (p.NDIR == 8 && pw == 2) hipLaunchKernelGGL((k_wta_pruned<2, 8, true>), grid, block, 0, s, p);
+        else if (p.NDIR == 8) hipLaunchKernelGGL((k_wta_pruned<1, 8, true>), grid, block, 0, s, p);
+        else if (p.NDIR == 4 && pw == 2) hipLaunchKernelGGL((k_wta_pruned<2, 4, true>), grid, block, 0, s, p);
+        else if (p.NDIR == 4) hipLaunchKernelGGL((k_wta_pruned<1, 4, true>), grid, block, 0, s, p);
+        else if (p.NDIR < 4) hipLaunchKernelGGL((k_wta_pruned<1, 4, false>), grid, block, 0, s, p);
+        else hipLaunchKernelGGL((k_wta_pruned<1, 8, false>), grid, block, 0, s, p);
+        return hipGetLastError();
+    }
     long long nb = (p.npix + 3) / 4;  // (an upper bound: waves take several pixels per iteration)
     static int per_cu = -1;  // MGM_HIP_WTA_WG_PER_CU=n overrides the grid bound (A/B timing)
     if (per_cu < 0) {
