@@ -295,6 +295,16 @@ int mgm_refine(mgm_ctx *ctx, const mgm_cv *S, const char *method, float *out, fl
  * without the over-count fix.  Any refinement name. */
 int mgm_wta_windowed_dev(mgm_ctx *ctx, const mgm_cv *C, int NDIR, int fix_overcount, const char *refine,
                          const mgm_img *dminI, const mgm_img *dmaxI, mgm_img *out, mgm_img *outcost);
+/* The right view's disparity map read out of the LEFT run: searches, for every pixel of a vnx-wide right image, the
+ * diagonal of the corrected aggregated volume of the context's last aggregation of C (DESIGN.md "right from left").
+ * Right pixel xr with disparity e = -dmax..-dmin names the match of left pixel xr + e with disparity -e; a match
+ * outside the left image is +INF.  The winner is the first strict minimum among the finite entries by rising e
+ * (mgm_core.cc:592-609 on that diagonal); refine is "none"/NULL or "vfit" (the gate of mgm_refine.h:58 in the right
+ * index), the other methods return MGM_ERR_UNSUPPORTED.  outR / outcostR are vnx x ny x 1 images: vnx is taken from
+ * them, ny must be C's.  C must be a dense volume (not built from range images: MGM_ERR_UNSUPPORTED) of the context's
+ * last aggregation with NDIR passes, in any slot of a batch (else MGM_ERR_INVALID).  No synchronisation. */
+int mgm_wta_right_dev(mgm_ctx *ctx, const mgm_cv *C, int NDIR, int fix_overcount, const char *refine,
+                      mgm_img *outR, mgm_img *outcostR);
 /* update_dmin_dmax (mgm.cc:120-158; main() uses slack 3, radius 2) followed by the two
  * remove_nonfinite_values_Img calls (mgm.cc:387-388): dminI/dmaxI are updated in place from the disparity map. */
 int mgm_update_ranges_dev(mgm_ctx *ctx, const mgm_img *outoff, mgm_img *dminI, mgm_img *dmaxI, int slack, int radius);

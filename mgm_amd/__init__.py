@@ -27,7 +27,7 @@ ABI_SYMBOLS = [
     "mgm_aggregate_dev", "mgm_aggregate", "mgm_debug_download_lr", "mgm_refine_dev", "mgm_refine",
     "mgm_selftest_div3", "mgm_aggregate_passes_dev", "mgm_lr_device_ptr", "mgm_wta_rows_dev",
     "mgm_aggregate_batch_dev", "mgm_median_dev", "mgm_leftright_dev", "mgm_backproject_dev",
-    "mgm_wta_windowed_dev", "mgm_update_ranges_dev", "mgm_costvolume_build_ranged_dev",
+    "mgm_wta_windowed_dev", "mgm_wta_right_dev", "mgm_update_ranges_dev", "mgm_costvolume_build_ranged_dev",
     "mgm_multi_create", "mgm_multi_destroy", "mgm_multi_size", "mgm_multi_ctx", "mgm_multi_last_error", "mgm_multi_plan",
     "mgm_multi_aggregate", "mgm_multi_transport", "mgm_img_device", "mgm_cv_device", "mgm_aggregate_passes_at_dev",
     "mgm_ctx_set_workspace_limit", "mgm_ctx_mem_info", "mgm_ctx_set_pipeline", "mgm_img_update", "mgm_debug_probe_workspace", "mgm_ctx_set_placement_tries",
@@ -112,6 +112,7 @@ def load_library():
     L.mgm_median_dev.argtypes = [vp, vp, i, vp]
     L.mgm_costvolume_build_ranged_dev.argtypes = [vp, vp, vp, vp, vp, i, i, cp, cp, f, i, pp]
     L.mgm_wta_windowed_dev.argtypes = [vp, vp, i, i, cp, vp, vp, vp, vp]
+    L.mgm_wta_right_dev.argtypes = [vp, vp, i, i, cp, vp, vp]
     L.mgm_update_ranges_dev.argtypes = [vp, vp, vp, vp, i, i]
     L.mgm_leftright_dev.argtypes = [vp, vp, vp, f, vp]
     L.mgm_backproject_dev.argtypes = [vp, vp, vp, vp, vp]
@@ -344,6 +345,50 @@ class Context:
         self._chk(self.lib.mgm_wta_windowed_dev(self.h, Cv.h, NDIR, fix_overcount, refine.encode() if refine else None,
                                                 dminI.h, dmaxI.h, out.h, outcost.h))
         return out, outcost
+
+    def wta_right_dev(self, Cv, NDIR, fix_overcount, refine, vnx, out=None, outcost=None):
+        """The right view's map (vnx wide) read out of the context's last aggregation of the LEFT volume Cv: (out, outcost)
+        as device images; refine None / "none" / "vfit" (mgm_wta_right_dev)."""
+        _, ny, _, _ = Cv.dims
+        out = out or self.new_image(vnx, ny)
+        outcost = outcost or self.new_image(vnx, ny)
+        self._chk(self.lib.mgm_wta_right_dev(self.h, Cv.h, NDIR, fix_overcount, refine.encode() if refine else None, out.h, outcost.h))
+        return out, outcost
+
+    def pair_right_from_left(self, u, v, dmin, dmax, P1=8.0, P2=32.0, NDIR=4, TSGM=4, use_fh=0, fix_overcount=1, aP2=1.0, aThresh=5.0,
+                             prefilter="none", distance="ad", truncDist=float("inf"), census_win=3, refine="none", tau=1.0, median=0):
+        """A stereo pair with ONE run: the left->right cost volume and aggregation, the right map read out of that run
+        (wta_right_dev), the optional medians and the left-right test both ways.  u, v: device images of one height (P1 / P2 as
+        given: multiply by the channel count yourself).  Returns device images (left map, right map, left cost), the maps checked."""
+        _, ny, nx = u.shape
+        _, vny, vnx = v.shape
+        if vny != ny:
+            raise ValueError("pair_right_from_left: the two images must have one height")
+        refine = refine if refine and refine != "none" else None
+        cv = self.costvolume_dev(u, v, dmin, dmax, prefilter, distance, truncDist, census_win)
+        w8 = self.weights_dev(u, aP2, aThresh) if aP2 != 1 else None
+        mine = [cv, w8]
+        try:
+            _, outL, costL = self.aggregate_dev(cv, P1, P2, NDIR, TSGM, use_fh, fix_overcount, w8=w8, refine=refine)
+            mine += [outL, costL]
+            outR, costR = self.wta_right_dev(cv, NDIR, fix_overcount, refine, vnx)
+            mine += [outR, costR]
+            if median:
+                mL, mR = self.median_dev(outL, median), self.median_dev(outR, median)
+                mine += [mL, mR]
+                outL, outR = mL, mR
+            chkR = self.leftright_dev(outR, outL, tau)
+            mine.append(chkR)
+            chkL = self.leftright_dev(outL, outR, tau)
+        except Exception:
+            for o in mine:
+                if o is not None:
+                    o.free()
+            raise
+        for o in mine:
+            if o is not None and o is not chkR and o is not costL:
+                o.free()
+        return chkL, chkR, costL
 
     def update_ranges_dev(self, outoff, dminI, dmaxI, slack=3, radius=2):
         self._chk(self.lib.mgm_update_ranges_dev(self.h, outoff.h, dminI.h, dmaxI.h, slack, radius))

@@ -544,6 +544,28 @@ int mgm_wta_windowed_dev(mgm_ctx *c, const mgm_cv *C, int NDIR, int fix_overcoun
                           refinement_index(refine), out->d, outcost->d, nullptr, dminI->d, dmaxI->d, slot);
 }
 
+int mgm_wta_right_dev(mgm_ctx *c, const mgm_cv *C, int NDIR, int fix_overcount, const char *refine, mgm_img *outR, mgm_img *outcostR)
+{
+    if (int jr = pipe_join(c)) return jr;  // (pipelined context: run what has been deferred first)
+    if (!c || !C || !outR || !outcostR) return fail(c, MGM_ERR_INVALID, "mgm_wta_right: null argument");
+    const int L = C->dmax - C->dmin + 1, vnx = outR->nx;
+    if (vnx < 1 || outR->ny != C->ny || outR->nch != 1 || outcostR->nx != vnx || outcostR->ny != C->ny || outcostR->nch != 1)
+        return fail(c, MGM_ERR_INVALID, "mgm_wta_right: image size mismatch (the two outputs are vnx x ny x 1, ny the volume's)");
+    const int ridx = refinement_index(refine);
+    if (ridx > 1) return fail(c, MGM_ERR_UNSUPPORTED, "mgm_wta_right: refinement none or vfit only");
+    if (C->rlo) return fail(c, MGM_ERR_UNSUPPORTED, "mgm_wta_right: a ragged volume (built from range images) has no right view here");
+    for (int v = 0; v < c->rel_last_batch; v++)
+        if (c->rel_last_cvs[v] == C && c->rel_last_gens[v] == C->gen)
+            return fail(c, MGM_ERR_UNSUPPORTED, "mgm_wta_right: the last aggregation of this volume ran on its range-proportional copy");
+    int slot = -1;
+    for (int v = 0; v < c->last_batch; v++)
+        if (c->last_cvs[v] == C && c->last_gens[v] == C->gen) slot = v;
+    if (!c->lr.p || slot < 0 || c->last_ndir != NDIR || c->last_L != L)
+        return fail(c, MGM_ERR_INVALID, "mgm_wta_right: this volume was not part of the context's last aggregation with NDIR passes");
+    HIPCHK(c, hipSetDevice(c->device));
+    return run_wta_right(c, C, slot, NDIR, fix_overcount, ridx, vnx, outR->d, outcostR->d);
+}
+
 int mgm_update_ranges_dev(mgm_ctx *c, const mgm_img *outoff, mgm_img *dminI, mgm_img *dmaxI, int slack, int radius)
 {
     if (int jr = pipe_join(c)) return jr;  // (pipelined context: run what has been deferred first)

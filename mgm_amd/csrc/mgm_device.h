@@ -88,6 +88,22 @@ struct WtaParams {
     unsigned long long *stats;       // nullptr, or 64 words 128 bytes apart the pruned search's waves add (pixels << 32 | chunks loaded) to
 };
 
+// the right view's winner search over the left run's Lr volumes (k_wta_right, mgm_wta.hip)
+struct WtaRightParams {
+    const float *C;      // costs of the left volume, label stride Lk (read with the over-count fix only) ...
+    const uint8_t *C8;   // ... or their compact copy, cbytes bytes per cost
+    int cbytes;
+    const float *Lr;     // NDIR volumes [ny*nx][Lk], pass p at Lr + p*nvol
+    float *out, *outcost;  // [ny][vnx]
+    long long nvol;
+    int nx, ny, vnx;
+    int L, Lk;           // labels that exist, label stride (>= L)
+    int NDIR, FIX, dmin, dmax, refine;  // refine: 0 none, 1 vfit
+    int num_cu;
+    int seg, ring;       // set by the launcher: right pixels per workgroup, entries of the LDS ring
+};
+hipError_t launch_wta_right(const WtaRightParams &p, hipStream_t s);
+
 // ---- ragged volumes in the range-proportional layout (mgm_pass_rel.hip, k_wta_rel): 64 label slots per pixel placed at the
 // pixel's own window, slot k <-> disparity base + k
 struct RelVolume {

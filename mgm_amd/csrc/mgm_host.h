@@ -294,6 +294,7 @@ int run_passes(mgm_ctx *c, const mgm_cv *const *Cs, const mgm_img *const *w8s, i
 bool wta_prune_enabled();  // MGM_HIP_WTA_PRUNE=0 (read at every call) or tune wta_prune=0: the plain winner search everywhere
 int run_wta(mgm_ctx *c, const mgm_cv *C, long long pix0, long long npix, const float *lr, long long lr_stride, int NDIR, int fix_overcount,
             int ridx, float *out, float *outcost, float *Sout, const float *wlo = nullptr, const float *whi = nullptr, int slot = -1);
+int run_wta_right(mgm_ctx *c, const mgm_cv *C, int slot, int NDIR, int fix_overcount, int ridx, int vnx, float *out, float *outcost);
 // the range-proportional path of ragged volumes (mgm_plan.hip): is this call one it takes?  then the passes + the winner search
 bool rel_enabled();
 int weights_have_odd_values(mgm_ctx *c, const mgm_img *const *w8s, int nb, long long npix, bool *odd, bool *any = nullptr);

@@ -790,6 +790,46 @@ int run_wta(mgm_ctx *c, const mgm_cv *C, long long pix0, long long npix, const f
     return MGM_OK;
 }
 
+// The right view's winners (vnx x C->ny) out of the Lr volumes of slot `slot` of the context's last dense aggregation
+// (mgm_wta_right_dev has checked that C is that volume).  Costs and label stride as run_wta takes them for such a slot.
+int run_wta_right(mgm_ctx *c, const mgm_cv *C, int slot, int NDIR, int fix_overcount, int ridx, int vnx, float *out, float *outcost)
+{
+    const int Lreal = C->dmax - C->dmin + 1;
+    const bool padded = c->last_Lk > c->last_L;
+    WtaRightParams w{};
+    if (fix_overcount != 1) {
+        w.cbytes = 1;  // (the costs are not read)
+    } else if (padded) {
+        w.C = c->last_pad_c8 ? nullptr : (const float *)c->padf[slot].p;
+        w.cbytes = c->last_pad_c8 ? c->last_pad_cb : 1;
+        w.C8 = c->last_pad_c8 ? c->last_pad_ptr[slot] : nullptr;
+    } else {
+        w.cbytes = C->cbytes;
+        w.C8 = (C->c8_state == CopyState::Valid && c->force_build != 1) ? C->d8 : nullptr;
+        if (!w.C8)
+            if (int r = ensure_f32(c, C)) return r;
+        w.C = C->d;
+    }
+    w.Lr = (const float *)c->lr.p + (size_t)slot * NDIR * c->last_stride;
+    w.out = out;
+    w.outcost = outcost;
+    w.nvol = c->last_stride;
+    w.nx = C->nx;
+    w.ny = C->ny;
+    w.vnx = vnx;
+    w.L = Lreal;
+    w.Lk = c->last_Lk;
+    w.NDIR = NDIR;
+    w.FIX = fix_overcount;
+    w.dmin = C->dmin;
+    w.dmax = C->dmax;
+    w.refine = ridx;
+    w.num_cu = c->num_cu;
+    TimeScope t(c, "k_wta_right");
+    HIPCHK(c, launch_wta_right(w, c->stream));
+    return MGM_OK;
+}
+
 // K4-K6 with any refinement of the reference's table: none/vfit are fused into k_wta; parabola, cubic and
 // parabolaOCV (refine.h:6-145) run as a second kernel on the corrected S (the caller's, or a scratch volume).
 int run_wta_refine(mgm_ctx *c, const mgm_cv *C, long long pix0, long long npix, const float *lr, long long lr_stride,

@@ -1070,4 +1070,232 @@ hipError_t launch_update_ranges(const float *outoff, int nx, int ny, int slack, 
     return hipGetLastError();
 }
 
+// ---- the right view's winners out of the LEFT run ("right from left") ----------------------------------------
+// Right pixel xr with label e = -dmax..-dmin (index oR = e + dmax) names the match of left pixel x = xr + e with label index
+// o = L-1-oR:  S_R(y, xr, oR) = S(y, xr + oR - dmax, L-1-oR), +INF where that left pixel lies outside the image.  The winner is the
+// first strict minimum among the finite entries by rising oR (mgm_core.cc:592-609), vfit (refine.h:70-92) on the three entries
+// around it under the gate of mgm_refine.h:58 in the right index.
+__device__ __forceinline__ float right_cost_at(const WtaRightParams &P, long long i)
+{
+    if (!P.C8) return P.C[i];
+    return P.cbytes == 2 ? c16_decode(reinterpret_cast<const unsigned short *>(P.C8)[i]) : c8_decode(P.C8[i]);
+}
+// one entry of S_R from memory: the pass volumes summed in pass order, then the over-count term -- k_wta's operations, in its order
+__device__ __forceinline__ float right_S_at(const WtaRightParams &P, int y, int xr, int oR)
+{
+    const int x = xr + oR - P.dmax;
+    if (x < 0 || x >= P.nx) return f_inf();
+    const long long i = ((long long)y * P.nx + x) * P.Lk + (P.L - 1 - oR);
+    float a = 0.0f;
+    for (int p = 0; p < P.NDIR; p++) a = a + P.Lr[(long long)p * P.nvol + i];
+    if (P.FIX == 1) a = a - (float)(P.NDIR - 1) * right_cost_at(P, i);
+    return a;
+}
+// the two outputs of a right pixel whose winner is entry oR with value v1 (oR < 0: no finite entry)
+__device__ __forceinline__ void right_emit(const WtaRightParams &P, int y, int xr, int oR, float v1)
+{
+    float outv = __builtin_nanf(""), outc = f_inf();  // as k_wta leaves a pixel without a finite entry
+    if (oR >= 0) {
+        outv = (float)(oR - P.dmax);
+        outc = v1;
+        if (P.refine == 1 && oR - 1 >= 0 && oR + 2 <= P.L - 1) {  // mgm_refine.h:58
+            float vmin, dx;
+            vfit(right_S_at(P, y, xr, oR - 1), v1, right_S_at(P, y, xr, oR + 1), vmin, dx);
+            outv = (float)(oR - P.dmax) + dx;
+            outc = vmin;
+        }
+    }
+    const long long i = (long long)y * P.vnx + xr;
+    P.out[i] = outv;
+    P.outcost[i] = outc;
+}
+
+// STREAMING: the volume is read exactly as k_wta reads it -- a wave takes a left pixel, its 64*LPL label slots in registers, every
+// stream a coalesced kilobyte -- and label o of left pixel x is handed to right pixel xr = x + dmin + o.  The running winners of the
+// right pixels in flight live in an LDS ring of packed keys (ordered float bits << 32 | oR) combined with a 64-bit atomic minimum:
+// the smallest key is the smallest value and, among equal values, the smallest oR -- the first strict minimum, whatever order the
+// waves arrive in.  (S is never -0: a sum that starts from +0 cannot be, and neither can x - y; +0 and -0 would order apart.)
+// One workgroup walks the left pixels xlo..xhi-1 that reach its segment [xr0, xr1) of one row in chunks of CH = 4*PPW; after the
+// chunk that ends before xb, right pixels below xb + dmin are final.  One barrier per chunk: the ring holds L-1 + 2*CH entries, so
+// finalising (and clearing) the entries of chunk i never meets the atomics of chunk i+1, and the barrier of chunk i+1 orders the
+// clearing before chunk i+2 reuses the slots.  Label stride Lk == 64*LPL; labels L..Lk-1 are padding.
+template <int LPL, int PPW>
+__global__ void __launch_bounds__(256) k_wta_right(const WtaRightParams P)
+{
+    constexpr int CH = 4 * PPW;
+    extern __shared__ unsigned long long ring[];  // P.ring entries (a power of two >= L-1 + 2*CH)
+    const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;
+    const int nseg = (P.vnx + P.seg - 1) / P.seg;
+    const int y = blockIdx.x / nseg;
+    const int xr0 = (blockIdx.x % nseg) * P.seg, xr1 = min(xr0 + P.seg, P.vnx);
+    const int xlo = max(0, xr0 - P.dmax), xhi = min(P.nx, xr1 - P.dmin);  // the left pixels that reach the segment
+    const unsigned mask = (unsigned)P.ring - 1u;
+    const int o0 = lane * LPL;
+    const bool c8 = P.C8 != nullptr;
+    for (int i = tid; i < P.ring; i += 256) ring[i] = ~0ull;
+    int fin = xr0;  // right pixels below it are written
+    if (xlo < xhi) {
+        // right pixels left of every match: no entry
+        const int first = max(xr0, xlo + P.dmin);
+        for (int xr = xr0 + tid; xr < first; xr += 256) right_emit(P, y, xr, -1, 0.0f);
+        fin = first;
+        __syncthreads();
+        for (int xa = xlo; xa < xhi; xa += CH) {
+            const int xb = min(xa + CH, xhi);
+            float c[PPW][LPL], l[kMaxDirs][PPW][LPL];
+#pragma unroll
+            for (int u = 0; u < PPW; u++) {
+                const int x = min(xa + wv * PPW + u, xhi - 1);
+                const long long g = ((long long)y * P.nx + x) * (64 * LPL) + o0;
+                if (P.FIX != 1) {
+#pragma unroll
+                    for (int k = 0; k < LPL; k++) c[u][k] = 0.0f;
+                } else if (c8 && P.cbytes == 2) {
+                    const unsigned short *q = reinterpret_cast<const unsigned short *>(P.C8) + g;
+#pragma unroll
+                    for (int k = 0; k < LPL; k++) c[u][k] = c16_decode(q[k]);
+                } else if (c8) {
+                    const uint8_t *q = P.C8 + g;
+#pragma unroll
+                    for (int k = 0; k < LPL; k++) c[u][k] = c8_decode(q[k]);
+                } else {
+                    const float *q = P.C + g;
+#pragma unroll
+                    for (int k = 0; k < LPL; k++) c[u][k] = q[k];
+                }
+            }
+#pragma unroll
+            for (int p = 0; p < kMaxDirs; p++) {
+                if (p < P.NDIR) {
+#pragma unroll
+                    for (int u = 0; u < PPW; u++) {
+                        const int x = min(xa + wv * PPW + u, xhi - 1);
+                        const float *q = P.Lr + (long long)p * P.nvol + ((long long)y * P.nx + x) * (64 * LPL) + o0;
+#pragma unroll
+                        for (int k = 0; k < LPL; k++) l[p][u][k] = q[k];
+                    }
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < PPW; u++) {
+                const int x = xa + wv * PPW + u;
+                if (x >= xhi) break;
+                // S = ((0 + L0) + L1) + ... in pass order, then the over-count term (mgm_core.cc:582-599)
+                float S[LPL];
+#pragma unroll
+                for (int k = 0; k < LPL; k++) S[k] = 0.0f;
+#pragma unroll
+                for (int p = 0; p < kMaxDirs; p++) {
+                    if (p < P.NDIR) {
+#pragma unroll
+                        for (int k = 0; k < LPL; k++) S[k] = S[k] + l[p][u][k];
+                    }
+                }
+                if (P.FIX == 1) {
+                    const float f = (float)(P.NDIR - 1);
+#pragma unroll
+                    for (int k = 0; k < LPL; k++) S[k] = S[k] - f * c[u][k];
+                }
+#pragma unroll
+                for (int k = 0; k < LPL; k++) {
+                    const int o = o0 + k, xr = x + P.dmin + o;
+                    if (o < P.L && xr >= xr0 && xr < xr1 && finite_bits(S[k])) {
+                        const unsigned long long key = ((unsigned long long)f2ord(S[k]) << 32) | (unsigned)(P.L - 1 - o);
+                        atomicMin(&ring[(unsigned)xr & mask], key);
+                    }
+                }
+            }
+            __syncthreads();
+            // final now: every right pixel whose last left pixel, xr - dmin, has passed; after the last chunk all that were reached
+            const int fe = min(xr1, xb == xhi ? xhi + P.dmax : xb + P.dmin);
+            for (int i = lane * 4 + wv; fin + i < fe; i += 256) {  // (spread over the waves: vfit fetches from memory)
+                const int xr = fin + i;
+                const unsigned long long key = ring[(unsigned)xr & mask];
+                ring[(unsigned)xr & mask] = ~0ull;
+                if (key == ~0ull) right_emit(P, y, xr, -1, 0.0f);
+                else right_emit(P, y, xr, (int)(unsigned)key, ord2f((unsigned)(key >> 32)));
+            }
+            fin = max(fin, fe);
+        }
+    }
+    // right pixels right of every match (or a segment no left pixel reaches)
+    for (int xr = fin + tid; xr < xr1; xr += 256) right_emit(P, y, xr, -1, 0.0f);
+}
+
+// Any label count and label stride: one wavefront per right pixel walks its diagonal in memory, the entries strided over the lanes.
+// The same arithmetic and rules; nothing here is tuned (a wave touches one line per entry).
+__global__ void __launch_bounds__(256) k_wta_right_any(const WtaRightParams P)
+{
+    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const long long npix = (long long)P.vnx * P.ny;
+    for (long long pix = (long long)blockIdx.x * 4 + wv; pix < npix; pix += (long long)gridDim.x * 4) {
+        const int y = (int)(pix / P.vnx), xr = (int)(pix % P.vnx);
+        float best = f_inf();
+        int bi = 0x7fffffff;
+        for (int oR = lane; oR < P.L; oR += 64) {
+            const float v = right_S_at(P, y, xr, oR);
+            if (finite_bits(v) && best > v) {
+                best = v;
+                bi = oR;
+            }
+        }
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) {
+            const float ov = __shfl_xor(best, d);
+            const int oi = __shfl_xor(bi, d);
+            if (ov < best || (ov == best && oi < bi)) {
+                best = ov;
+                bi = oi;
+            }
+        }
+        if (lane == 0) right_emit(P, y, xr, bi == 0x7fffffff ? -1 : bi, best);
+    }
+}
+
+hipError_t launch_wta_right(const WtaRightParams &p0, hipStream_t s)
+{
+    WtaRightParams p = p0;
+    if (p.L < 1 || p.Lk < p.L || p.nx < 1 || p.ny < 1 || p.vnx < 1 || p.dmax - p.dmin + 1 != p.L) return hipErrorInvalidValue;
+    const int cus = p.num_cu > 0 ? p.num_cu : 256;
+    const int lpl = p.Lk % 64 == 0 ? p.Lk / 64 : 0;
+    // MGM_HIP_WTA_RIGHT_ANY=1 (read at every call: tests switch it inside one process): the diagonal walk everywhere
+    const char *ea = getenv("MGM_HIP_WTA_RIGHT_ANY");
+    const bool force_any = ea && atoi(ea) != 0;
+    const bool stream = !force_any && (lpl == 1 || lpl == 2 || lpl == 3 || lpl == 4 || lpl == 6 || lpl == 8 || lpl == 12 || lpl == 16);
+    if (!stream) {
+        long long nb = ((long long)p.vnx * p.ny + 3) / 4;
+        nb = std::min(nb, (long long)cus * 64);
+        hipLaunchKernelGGL(k_wta_right_any, dim3((unsigned)nb), dim3(256), 0, s, p);
+        return hipGetLastError();
+    }
+    // Segments of a row: a workgroup re-reads the L-1 left pixels ahead of its segment, so a row is split only as far as the
+    // device needs workgroups (about four per compute unit), and never below max(64, L) right pixels.
+    static int seg_tune = -1;  // MGM_HIP_TUNE=wta_right_seg=<right pixels per workgroup> (A/B timing)
+    if (seg_tune < 0) seg_tune = (int)tune_num("wta_right_seg", 0);
+    const int want = (4 * cus + p.ny - 1) / p.ny;  // segments per row
+    int seg = (p.vnx + want - 1) / want;
+    seg = std::max(seg, std::max(64, p.L));
+    if (seg_tune > 0) seg = seg_tune;
+    p.seg = std::min(seg, p.vnx);
+    const long long nb = (long long)p.ny * ((p.vnx + p.seg - 1) / p.seg);
+    if (nb > 0x7fffffffll) return hipErrorInvalidValue;
+    const int ppw = lpl <= 4 ? 2 : 1;
+    int ring = 64;
+    while (ring < p.L - 1 + 2 * 4 * ppw) ring *= 2;
+    p.ring = ring;
+    const dim3 grid((unsigned)nb), block(256);
+    const size_t lds = sizeof(unsigned long long) * (size_t)ring;
+    switch (lpl) {
+        case 1: hipLaunchKernelGGL((k_wta_right<1, 2>), grid, block, lds, s, p); break;
+        case 2: hipLaunchKernelGGL((k_wta_right<2, 2>), grid, block, lds, s, p); break;
+        case 3: hipLaunchKernelGGL((k_wta_right<3, 2>), grid, block, lds, s, p); break;
+        case 4: hipLaunchKernelGGL((k_wta_right<4, 2>), grid, block, lds, s, p); break;
+        case 6: hipLaunchKernelGGL((k_wta_right<6, 1>), grid, block, lds, s, p); break;
+        case 8: hipLaunchKernelGGL((k_wta_right<8, 1>), grid, block, lds, s, p); break;
+        case 12: hipLaunchKernelGGL((k_wta_right<12, 1>), grid, block, lds, s, p); break;
+        default: hipLaunchKernelGGL((k_wta_right<16, 1>), grid, block, lds, s, p); break;
+    }
+    return hipGetLastError();
+}
+
 }  // namespace mgm

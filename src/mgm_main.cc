@@ -400,6 +400,9 @@ static void parse_job(Job &j)
                         "environment: CENSUS_NCC_WIN=3 TESTLRRL=1 TESTLRRL_TAU=1.0 MEDIAN=0 TSGM=4 TSGM_ITER=1\n"
                         "             TSGM_FIX_OVERCOUNT=1 USE_TRUNCATED_LINEAR_POTENTIALS=0 MGM_DEVICE=0 MGM_DEVICES=0,1,...\n"
                         "             MGM_MS_SLACK=3 MGM_MS_RADIUS=2 (-S: window around the coarser level's disparities)\n"
+                        "             MGM_RIGHT_FROM_LEFT=0 (1, with TESTLRRL != 0: no right->left run; the right map is read out of the left run's\n"
+                        "              aggregated volume along its diagonals, and stdout has the line `right from left` in place of that run's\n"
+                        "              lines; not with -m/-M, -S > 1, TSGM_ITER != 1, several MGM_DEVICES, -s parabola|cubic|parabolaOCV: exit code 2)\n"
                         "             (with several MGM_DEVICES, -S / -m -M / TSGM_ITER > 1 run on the first device; in --batch mode a FIRST line\n"
                         "              of that kind brings up one device for the whole batch, a later one leaves the other lines their devices)\n"
                         "resident mode: mgm --batch FILE|-   (one such command line per line of FILE, one device context for all)");
@@ -600,6 +603,21 @@ static int device_job(Session &S, Job &j, const std::function<void()> &decoded, 
     // all for TSGM_ITER <= 0 -- the maps then stay the zero images they were allocated as (mgm.cc:360-365)
     const int ITER = TSGM_ITER > 0 ? (int)std::ceil(TSGM_ITER) : 0;
     const bool ranged = !j.min_file.empty();
+    // MGM_RIGHT_FROM_LEFT=1 (this program's own mode): the right map of the left-right test comes out of the left
+    // run's aggregated volume (mgm_wta_right_dev) instead of a second run
+    const bool rfl = env_param("MGM_RIGHT_FROM_LEFT", 0) != 0 && TESTLRRL != 0;
+    if (rfl) {
+        const char *why = nullptr;
+        if (ranged) why = "range images (-m/-M)";
+        else if (j.nscales > 1) why = "-S > 1";
+        else if (ITER != 1) why = "TSGM_ITER != 1";
+        else if (o.refine == "parabola" || o.refine == "cubic" || o.refine == "parabolaOCV") why = "a refinement other than none or vfit";
+        else if (getenv("MGM_DEVICES") && strchr(getenv("MGM_DEVICES"), ',')) why = "several MGM_DEVICES";
+        if (why) {
+            fprintf(stderr, "mgm: MGM_RIGHT_FROM_LEFT=1 does not combine with %s\n", why);
+            return 2;
+        }
+    }
     try {
         bring_up(S, ITER, ranged, j.nscales > 1);
         sw.mark("context");
@@ -625,6 +643,14 @@ static int device_job(Session &S, Job &j, const std::function<void()> &decoded, 
             return 1;
         }
         const HostImg &u = j.u, &v = j.v;
+        if (rfl && multi) {  // (resident mode: an earlier line brought several devices up)
+            fprintf(stderr, "mgm: MGM_RIGHT_FROM_LEFT=1 does not combine with several MGM_DEVICES\n");
+            return 2;
+        }
+        if (rfl && u.ny != v.ny) {
+            fprintf(stderr, "mgm: MGM_RIGHT_FROM_LEFT=1 needs two images of one height\n");
+            return 2;
+        }
         HostImg &rlo = j.rlo, &rhi = j.rhi;  // -m / -M range images of the left->right run (mgm.cc:342-353); the right->left run keeps -r/-R
         if (ranged) {
             if (rlo.nx != u.nx || rlo.ny != u.ny || rhi.nx != u.nx || rhi.ny != u.ny || rlo.nch != 1 || rhi.nch != 1) {
@@ -666,7 +692,7 @@ static int device_job(Session &S, Job &j, const std::function<void()> &decoded, 
             zero_run(L);
             together = true;  // (nothing to aggregate)
         }
-        if (ITER > 0 && !multi && both && !plo && u.nx == v.nx && u.ny == v.ny && env_param("MGM_BATCH_LR", 1) != 0) {
+        if (ITER > 0 && !multi && both && !rfl && !plo && u.nx == v.nx && u.ny == v.ny && env_param("MGM_BATCH_LR", 1) != 0) {
             // both runs of the pair (mgm.cc:376-385 and 405-414) through ONE launch of the pass kernel
             prepare_R();
             const mgm_cv *Cs[2] = {L.C, R.C};
@@ -689,7 +715,17 @@ static int device_job(Session &S, Job &j, const std::function<void()> &decoded, 
         }
         if (MEDIAN != 0) median_run(ctx, L, (int)MEDIAN);
         if (!j.nolr_file.empty()) j.nolr = download(ctx, L.dout, L.nx, L.ny, 1);
-        if (both) {
+        if (rfl) {
+            // the right map out of the left run: no volume, no passes (R keeps only its two maps)
+            if (R.C || R.nx != v.nx || R.ny != v.ny) free_run(ctx, R);
+            R.nx = v.nx, R.ny = v.ny, R.nch = v.nch;
+            image_like(ctx, v.nx, v.ny, 1, &R.dout);
+            image_like(ctx, v.nx, v.ny, 1, &R.dcost);
+            if ((rc = mgm_wta_right_dev(ctx, L.C, o.NDIR, o.FIX, o.refine.c_str(), R.dout, R.dcost))) die(ctx, rc, "mgm_wta_right");
+            printf("right from left\n");
+            fflush(stdout);
+            if (MEDIAN != 0) median_run(ctx, R, (int)MEDIAN);
+        } else if (both) {
             if (!r_ready) prepare_R();
             if (ITER == 0) {
                 zero_run(R);
@@ -700,6 +736,8 @@ static int device_job(Session &S, Job &j, const std::function<void()> &decoded, 
                 iterate_run(ctx, o, R, ITER, -o.dmax, -o.dmin);
             }
             if (MEDIAN != 0) median_run(ctx, R, (int)MEDIAN);
+        }
+        if (both) {
             // leftright_test both ways on copies of the unchecked maps (mgm.cc:420-423)
             image_like(ctx, L.nx, L.ny, 1, &L.dspare);
             image_like(ctx, R.nx, R.ny, 1, &R.dspare);
