@@ -261,6 +261,12 @@ int mgm_multi_aggregate(mgm_multi *m, const mgm_cv *const *C, const mgm_img *con
  * call on this ctx into `dense` ([ny][nx][L]). */
 int mgm_debug_download_lr(mgm_ctx *ctx, int pass, float *dense);
 
+/* Test/diagnostic aid: the chunk minima (one float per pixel and chunk of 32 labels: [ny][nx][L/32]) that the pass kernel
+ * left beside pass `pass`'s Lr volume of volume `slot` of the LAST aggregation call on this ctx, read where the pruned winner
+ * search reads them.  MGM_ERR_INVALID when that launch wrote no minima (any launch the pruned search does not follow), when
+ * the volume has been refilled since, or when `slot` / `pass` is out of range. */
+int mgm_debug_download_lmin(mgm_ctx *ctx, int slot, int pass, float *out);
+
 /* Test/diagnostic aid: what the pruned winner searches of the context's LAST aggregation call did -- pixels searched and
  * chunks of 32 labels whose Lr values were loaded (a plain search loads L/32 per pixel), summed over the call's volumes.
  * Counted only while timing (mgm_timing_enable) or MGM_HIP_DEBUG_STATS is on; both 0 when no search of that call was a

@@ -31,7 +31,7 @@ ABI_SYMBOLS = [
     "mgm_multi_create", "mgm_multi_destroy", "mgm_multi_size", "mgm_multi_ctx", "mgm_multi_last_error", "mgm_multi_plan",
     "mgm_multi_aggregate", "mgm_multi_transport", "mgm_img_device", "mgm_cv_device", "mgm_aggregate_passes_at_dev",
     "mgm_ctx_set_workspace_limit", "mgm_ctx_mem_info", "mgm_ctx_set_pipeline", "mgm_img_update", "mgm_debug_probe_workspace", "mgm_ctx_set_placement_tries",
-    "mgm_debug_wta_stats",
+    "mgm_debug_wta_stats", "mgm_debug_download_lmin",
     "mgm_multiscale_levels", "mgm_zoom_out_dev", "mgm_ranges_zoom_out_dev", "mgm_ranges_from_coarse_dev", "mgm_multiscale_pair_dev",
 ]
 
@@ -118,6 +118,7 @@ def load_library():
     L.mgm_backproject_dev.argtypes = [vp, vp, vp, vp, vp]
     L.mgm_aggregate_batch_dev.argtypes = [vp, i, pp, pp, f, f, i, i, i, i, cp, pp, pp, pp]
     L.mgm_debug_download_lr.argtypes = [vp, i, fp]
+    L.mgm_debug_download_lmin.argtypes = [vp, i, i, fp]
     L.mgm_refine_dev.argtypes = [vp, vp, cp, vp, vp]
     L.mgm_refine.argtypes = [vp, vp, cp, fp, fp]
     L.mgm_selftest_div3.argtypes = [vp, C.POINTER(C.c_ulonglong)]
@@ -494,6 +495,13 @@ class Context:
         nx, ny, dmin, dmax = Cv.dims
         out = np.empty((ny, nx, dmax - dmin + 1), np.float32)
         self._chk(self.lib.mgm_debug_download_lr(self.h, p, _ptr(out)))
+        return out
+
+    def debug_lmin(self, Cv, slot, p):
+        """The chunk minima of pass p of volume `slot` of the last aggregation call: (ny, nx, L/32), as the pruned search reads them."""
+        nx, ny, dmin, dmax = Cv.dims
+        out = np.empty((ny, nx, (dmax - dmin + 1) // 32), np.float32)
+        self._chk(self.lib.mgm_debug_download_lmin(self.h, slot, p, _ptr(out)))
         return out
 
     def refine(self, S, method, out, outcost):

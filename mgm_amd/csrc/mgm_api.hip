@@ -443,6 +443,25 @@ int mgm_debug_download_lr(mgm_ctx *c, int pass, float *dense)
     return mgm_ctx_synchronize(c);
 }
 
+int mgm_debug_download_lmin(mgm_ctx *c, int slot, int pass, float *out)
+{
+    if (int jr = pipe_join(c)) return jr;  // (pipelined context: run what has been deferred first)
+    if (!c || !out) return fail(c, MGM_ERR_INVALID, "mgm_debug_download_lmin: null argument");
+    if (!c->last_min || !c->lmin.p || !c->lr.p || c->last_stride % kChunkLabels != 0)
+        return fail(c, MGM_ERR_INVALID, "mgm_debug_download_lmin: the context's last aggregation wrote no chunk minima");
+    if (slot < 0 || slot >= c->last_batch || pass < 0 || pass >= c->last_ndir)
+        return fail(c, MGM_ERR_INVALID, "mgm_debug_download_lmin: no such slot or pass");
+    const mgm_cv *C = c->last_cvs[slot];
+    if (!C || C->gen != c->last_gens[slot])
+        return fail(c, MGM_ERR_INVALID, "mgm_debug_download_lmin: the volume of the last aggregation has been refilled since");
+    HIPCHK(c, hipSetDevice(c->device));
+    // where the search finds them (run_wta): slot k's passes behind each other, one word per 32 floats of the Lr workspace
+    const size_t nchunk = (size_t)(c->last_nvol / kChunkLabels);  // (pixels x L / 32)
+    const float *src = (const float *)c->lmin.p + ((size_t)slot * c->last_ndir + pass) * (size_t)(c->last_stride / kChunkLabels);
+    HIPCHK(c, hipMemcpyAsync(out, src, sizeof(float) * nchunk, hipMemcpyDeviceToHost, c->stream));
+    return mgm_ctx_synchronize(c);
+}
+
 int mgm_debug_wta_stats(mgm_ctx *c, unsigned long long *pixels, unsigned long long *chunks)
 {
     if (int jr = pipe_join(c)) return jr;  // (pipelined context: run what has been deferred first)

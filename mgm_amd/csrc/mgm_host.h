@@ -181,7 +181,7 @@ struct mgm_ctx {
     bool last_pad_c8 = false;
     const uint8_t *last_pad_ptr[kMaxBatch] = {};  // ... where they are: the context's pad8 buffers, or the volumes' own padded copies (mgm_cv::p8)
     int last_pad_cb = 1;  // ... bytes per compact cost of those padded copies
-    const mgm_cv *last_cvs[kMaxBatch] = {};  // the volumes of the last aggregation (identity only, never dereferenced) ...
+    const mgm_cv *last_cvs[kMaxBatch] = {};  // the volumes of the last aggregation (identities; mgm_cv_free clears the entry of a freed volume) ...
     unsigned long long last_gens[kMaxBatch] = {};  // ... and their generations at that time
     bool pending_check = false;
     // self-validating hand-off slabs (k_pass2, TAGS): the layout the region was last cleared for (npass 0: unknown -- the next

@@ -476,7 +476,7 @@ __global__ void __launch_bounds__(256) k_wta_pruned(const WtaParams P)
             float lb = f_inf();
 #pragma unroll
             for (int k = 0; k < 4; k++) lb = c[u][k] < f_inf() ? __builtin_fminf(lb, LB[k]) : lb;
-            lb = lb == lb ? lb : -f_inf();  // (a NaN bound bounds nothing: such a chunk always loads.  The pass kernels are NaN-free)
+            lb = lb == lb ? lb : -f_inf();  // (never taken: fminf above returns its other operand, so a NaN bound drops out -- S is NaN on that label too)
             lb = dpp_fmin<0xB1>(lb);   // quad_perm [1,0,3,2]
             lb = dpp_fmin<0x4E>(lb);   // quad_perm [2,3,0,1]
             lb = dpp_fmin<0x141>(lb);  // row_half_mirror: all eight lanes hold the chunk's smallest bound
