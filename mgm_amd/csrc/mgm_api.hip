@@ -229,8 +229,7 @@ static int aggregate_batch_now(mgm_ctx *c, int n, const mgm_cv *const *C, const 
                 if ((r = mgm_cv_create(c, nx, ny, C[v0 + v]->dmin, C[v0 + v]->dmax, &S[v0 + v]))) break;
                 Sout = S[v0 + v]->d;
             }
-            const float *lr = (const float *)c->lr.p + (size_t)v * NDIR * c->last_stride;
-            r = run_wta_refine(c, C[v0 + v], 0, npix, lr, c->last_stride, NDIR, fix_overcount, ridx, out[v0 + v]->d, outcost[v0 + v]->d,
+            r = run_wta_refine(c, C[v0 + v], 0, npix, c->last.lr(c->lr, v, 0), c->last.stride, NDIR, fix_overcount, ridx, out[v0 + v]->d, outcost[v0 + v]->d,
                                Sout, nullptr, nullptr, v);
         }
         v0 += m;
@@ -367,8 +366,8 @@ int mgm_aggregate_passes_at_dev(mgm_ctx *c, const mgm_cv *C, const mgm_img *w8, 
 void *mgm_lr_device_ptr(mgm_ctx *c, int slot)
 {
     (void)pipe_join(c);
-    if (!c || !c->lr.p || slot < 0 || slot >= c->last_ndir || c->last_Lk != c->last_L) return nullptr;
-    return (float *)c->lr.p + (size_t)slot * c->last_stride;
+    if (!c || !c->lr.p || slot < 0 || slot >= c->last.ndir || c->last.Lk != c->last.L) return nullptr;
+    return const_cast<float *>(c->last.lr(c->lr, 0, slot));  // (the volumes of a single-volume launch: its passes)
 }
 
 int mgm_wta_rows_dev(mgm_ctx *c, const mgm_cv *C, int row0, int nrows, const void *lr_slabs, int NDIR, int fix_overcount,
@@ -406,13 +405,13 @@ int mgm_aggregate(mgm_ctx *c, const mgm_cv *C, const float *w8, float P1, float 
 int mgm_debug_download_lr(mgm_ctx *c, int pass, float *dense)
 {
     if (int jr = pipe_join(c)) return jr;  // (pipelined context: run what has been deferred first)
-    if (c && dense && c->rel_last_batch > 0 && c->last_ndir == 0 && c->rel_last_cvs[0] && c->lr_rel.p) {
+    if (c && dense && c->rel_last.batch > 0 && c->last.ndir == 0 && c->rel_last.cvs[0] && c->lr_rel.p) {
         // the last aggregation ran on the range-proportional copy (k_pass_rel): volume 0's pass, expanded on the host to the dense
         // hull -- label o <-> slot o + dmin - base(p) of the pixel's 64, +INF where the pixel has no such label (test aid only)
-        if (pass < 0 || pass >= c->rel_last_ndir) return fail(c, MGM_ERR_INVALID, "mgm_debug_download_lr: no such pass");
-        const mgm_cv *C = c->rel_last_cvs[0];
+        if (pass < 0 || pass >= c->rel_last.ndir) return fail(c, MGM_ERR_INVALID, "mgm_debug_download_lr: no such pass");
+        const mgm_cv *C = c->rel_last.cvs[0];
         // (a volume refilled since -- another slot count, other records -- no longer describes the Lr volumes of that launch)
-        if (C->gen != c->rel_last_gens[0] || C->rel_slots != c->rel_last_slots)
+        if (c->rel_last.slot_of(C) != 0 || C->rel_slots != c->rel_last.slots)
             return fail(c, MGM_ERR_INVALID, "mgm_debug_download_lr: the volume of the last aggregation has been refilled since");
         const size_t npix = (size_t)C->nx * C->ny;
         const int L = C->dmax - C->dmin + 1;
@@ -420,7 +419,7 @@ int mgm_debug_download_lr(mgm_ctx *c, int pass, float *dense)
         const size_t slots = (size_t)C->rel_slots;
         std::vector<float> slabs(npix * slots);
         std::vector<int> rec(npix * 4);
-        HIPCHK(c, hipMemcpyAsync(slabs.data(), (const float *)c->lr_rel.p + (size_t)pass * c->rel_last_stride, sizeof(float) * npix * slots,
+        HIPCHK(c, hipMemcpyAsync(slabs.data(), c->rel_last.lr(c->lr_rel, 0, pass), sizeof(float) * npix * slots,
                                  hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipMemcpyAsync(rec.data(), C->rel_records(), sizeof(int) * npix * 4, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -433,12 +432,12 @@ int mgm_debug_download_lr(mgm_ctx *c, int pass, float *dense)
         }
         return MGM_OK;
     }
-    if (!c || !dense || pass < 0 || pass >= c->last_ndir || !c->lr.p)
+    if (!c || !dense || pass < 0 || pass >= c->last.ndir || !c->lr.p)
         return fail(c, MGM_ERR_INVALID, "mgm_debug_download_lr: nothing to download");
     HIPCHK(c, hipSetDevice(c->device));
-    // (a launch with a padded label count keeps last_Lk floats per pixel, of which the first last_L exist)
-    HIPCHK(c, hipMemcpy2DAsync(dense, sizeof(float) * c->last_L, (const float *)c->lr.p + (size_t)pass * c->last_stride,
-                               sizeof(float) * c->last_Lk, sizeof(float) * c->last_L, (size_t)(c->last_nvol / c->last_Lk),
+    // (a launch with a padded label count keeps Lk floats per pixel, of which the first L exist)
+    const DenseRun &d = c->last;
+    HIPCHK(c, hipMemcpy2DAsync(dense, sizeof(float) * d.L, d.lr(c->lr, 0, pass), sizeof(float) * d.Lk, sizeof(float) * d.L, (size_t)(d.nvol / d.Lk),
                                hipMemcpyDeviceToHost, c->stream));
     return mgm_ctx_synchronize(c);
 }
@@ -447,18 +446,17 @@ int mgm_debug_download_lmin(mgm_ctx *c, int slot, int pass, float *out)
 {
     if (int jr = pipe_join(c)) return jr;  // (pipelined context: run what has been deferred first)
     if (!c || !out) return fail(c, MGM_ERR_INVALID, "mgm_debug_download_lmin: null argument");
-    if (!c->last_min || !c->lmin.p || !c->lr.p || c->last_stride % kChunkLabels != 0)
+    const DenseRun &d = c->last;
+    if (!d.wrote_min || !c->lmin.p || !c->lr.p || d.stride % kChunkLabels != 0)
         return fail(c, MGM_ERR_INVALID, "mgm_debug_download_lmin: the context's last aggregation wrote no chunk minima");
-    if (slot < 0 || slot >= c->last_batch || pass < 0 || pass >= c->last_ndir)
+    if (slot < 0 || slot >= d.batch || pass < 0 || pass >= d.ndir)
         return fail(c, MGM_ERR_INVALID, "mgm_debug_download_lmin: no such slot or pass");
-    const mgm_cv *C = c->last_cvs[slot];
-    if (!C || C->gen != c->last_gens[slot])
+    if (!d.current(slot))
         return fail(c, MGM_ERR_INVALID, "mgm_debug_download_lmin: the volume of the last aggregation has been refilled since");
     HIPCHK(c, hipSetDevice(c->device));
     // where the search finds them (run_wta): slot k's passes behind each other, one word per 32 floats of the Lr workspace
-    const size_t nchunk = (size_t)(c->last_nvol / kChunkLabels);  // (pixels x L / 32)
-    const float *src = (const float *)c->lmin.p + ((size_t)slot * c->last_ndir + pass) * (size_t)(c->last_stride / kChunkLabels);
-    HIPCHK(c, hipMemcpyAsync(out, src, sizeof(float) * nchunk, hipMemcpyDeviceToHost, c->stream));
+    const size_t nchunk = (size_t)(d.nvol / kChunkLabels);  // (pixels x L / 32)
+    HIPCHK(c, hipMemcpyAsync(out, d.lmin(c->lmin, slot, pass), sizeof(float) * nchunk, hipMemcpyDeviceToHost, c->stream));
     return mgm_ctx_synchronize(c);
 }
 
@@ -486,9 +484,9 @@ int mgm_debug_probe_workspace(mgm_ctx *c, int nstreams, float *gbps)
 {
     if (int jr = pipe_join(c)) return jr;
     if (!c || !gbps || nstreams < 1 || nstreams > 64) return fail(c, MGM_ERR_INVALID, "mgm_debug_probe_workspace: bad arguments");
-    if (!c->lr.p || c->last_stride <= 0) return fail(c, MGM_ERR_INVALID, "mgm_debug_probe_workspace: no aggregation has run on this context");
+    if (!c->lr.p || c->last.stride <= 0) return fail(c, MGM_ERR_INVALID, "mgm_debug_probe_workspace: no aggregation has run on this context");
     HIPCHK(c, hipSetDevice(c->device));
-    const long long stride = c->last_stride;
+    const long long stride = c->last.stride;
     const long long have = (long long)(c->lr.cap / sizeof(float));
     if ((long long)nstreams * stride > have) nstreams = (int)(have / stride);
     if (nstreams < 1) return fail(c, MGM_ERR_INVALID, "mgm_debug_probe_workspace: workspace smaller than one volume");
@@ -548,18 +546,15 @@ int mgm_wta_windowed_dev(mgm_ctx *c, const mgm_cv *C, int NDIR, int fix_overcoun
     const int nx = C->nx, ny = C->ny, L = C->dmax - C->dmin + 1;
     for (const mgm_img *im : {dminI, dmaxI, (const mgm_img *)out, (const mgm_img *)outcost})
         if (im->nx != nx || im->ny != ny || im->nch != 1) return fail(c, MGM_ERR_INVALID, "mgm_wta_windowed: image size mismatch");
-    for (int v = 0; v < c->rel_last_batch; v++)  // the context's last aggregation of this volume ran on its range-proportional copy
-        if (c->rel_last_cvs[v] == C && c->rel_last_gens[v] == C->gen && c->rel_last_ndir == NDIR) {
-            HIPCHK(c, hipSetDevice(c->device));
-            return run_wta_rel(c, C, v, NDIR, fix_overcount, refinement_index(refine), dminI->d, dmaxI->d, out->d, outcost->d);
-        }
-    int slot = -1;
-    for (int v = 0; v < c->last_batch; v++)
-        if (c->last_cvs[v] == C && c->last_gens[v] == C->gen) slot = v;
-    if (!c->lr.p || slot < 0 || c->last_ndir != NDIR || c->last_L != L)
+    if (const int v = c->rel_last.slot_of(C); v >= 0 && c->rel_last.ndir == NDIR) {  // the context's last aggregation of this volume ran on its range-proportional copy
+        HIPCHK(c, hipSetDevice(c->device));
+        return run_wta_rel(c, C, v, NDIR, fix_overcount, refinement_index(refine), dminI->d, dmaxI->d, out->d, outcost->d);
+    }
+    const int slot = c->last.slot_of(C);
+    if (!c->lr.p || slot < 0 || c->last.ndir != NDIR || c->last.L != L)
         return fail(c, MGM_ERR_INVALID, "mgm_wta_windowed: this volume was not part of the context's last aggregation with NDIR passes");
     HIPCHK(c, hipSetDevice(c->device));
-    return run_wta_refine(c, C, 0, (long long)nx * ny, (const float *)c->lr.p + (size_t)slot * NDIR * c->last_stride, c->last_stride, NDIR, fix_overcount,
+    return run_wta_refine(c, C, 0, (long long)nx * ny, c->last.lr(c->lr, slot, 0), c->last.stride, NDIR, fix_overcount,
                           refinement_index(refine), out->d, outcost->d, nullptr, dminI->d, dmaxI->d, slot);
 }
 
@@ -573,13 +568,10 @@ int mgm_wta_right_dev(mgm_ctx *c, const mgm_cv *C, int NDIR, int fix_overcount, 
     const int ridx = refinement_index(refine);
     if (ridx > 1) return fail(c, MGM_ERR_UNSUPPORTED, "mgm_wta_right: refinement none or vfit only");
     if (C->rlo) return fail(c, MGM_ERR_UNSUPPORTED, "mgm_wta_right: a ragged volume (built from range images) has no right view here");
-    for (int v = 0; v < c->rel_last_batch; v++)
-        if (c->rel_last_cvs[v] == C && c->rel_last_gens[v] == C->gen)
-            return fail(c, MGM_ERR_UNSUPPORTED, "mgm_wta_right: the last aggregation of this volume ran on its range-proportional copy");
-    int slot = -1;
-    for (int v = 0; v < c->last_batch; v++)
-        if (c->last_cvs[v] == C && c->last_gens[v] == C->gen) slot = v;
-    if (!c->lr.p || slot < 0 || c->last_ndir != NDIR || c->last_L != L)
+    if (c->rel_last.slot_of(C) >= 0)
+        return fail(c, MGM_ERR_UNSUPPORTED, "mgm_wta_right: the last aggregation of this volume ran on its range-proportional copy");
+    const int slot = c->last.slot_of(C);
+    if (!c->lr.p || slot < 0 || c->last.ndir != NDIR || c->last.L != L)
         return fail(c, MGM_ERR_INVALID, "mgm_wta_right: this volume was not part of the context's last aggregation with NDIR passes");
     HIPCHK(c, hipSetDevice(c->device));
     return run_wta_right(c, C, slot, NDIR, fix_overcount, ridx, vnx, outR->d, outcostR->d);

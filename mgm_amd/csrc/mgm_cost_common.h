@@ -5,11 +5,6 @@
 
 namespace mgm {
 
-__device__ __forceinline__ bool finite_bits(float x)
-{
-    return (__builtin_bit_cast(unsigned, x) & 0x7f800000u) != 0x7f800000u;
-}
-
 // ---- the costs that look at more than one sample per image ------------------------
 // Birchfield-Tomasi dissimilarity of one channel (mgm_costvolume.h:82-110).  Each sample spans the closed interval
 // between itself and its two half-way interpolants along x (at the image border the interpolant is the sample; the

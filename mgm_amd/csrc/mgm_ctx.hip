@@ -47,6 +47,13 @@ const DevSwitches &dev()
     return d;
 }
 long long lr_pad_floats() { return dev().lr_pad; }
+const WtaSwitches &wta_switches()
+{
+    static const WtaSwitches w{(int)tune_num("wta_prune_ppw", 2), (int)tune_num("wta_prune_wg", 0), (int)tune_num("wta_wg_per_cu", 0),
+                               tune_num("wta_packed", 1) != 0, tune_num("wta_wide4", 1) != 0, tune_num("wta_quad", 1) != 0,
+                               (int)tune_num("wta_right_seg", 0)};
+    return w;
+}
 
 int fail(mgm_ctx *c, int code, const std::string &msg)
 {
@@ -253,10 +260,10 @@ int mgm_ctx_trim(mgm_ctx *c)
     if (int r = mgm_ctx_synchronize(c)) return r;
     std::vector<Buf *> bufs = {&c->lr, &c->hand, &c->hand2, &c->handm, &c->exact_mins, &c->exact_scratch, &c->census_u, &c->census_v, &c->dbg, &c->stmp, &c->ones8,
                                &c->lr_rel, &c->hand_rel, &c->lmin, &c->wta_stats};
-    c->last_min = false;
+    c->last.clear();
+    c->rel_last.clear();
     c->wta_stats_n = 0;
     c->hand_rel_key = HandLayout{};
-    c->rel_last_batch = 0;
     for (int v = 0; v < kMaxBatch; v++) {
         bufs.push_back(&c->padf[v]);
         bufs.push_back(&c->pad8[v]);
@@ -271,8 +278,6 @@ int mgm_ctx_trim(mgm_ctx *c)
     c->hand_key = HandLayout{};
     c->dense_plans.free_all();
     c->rel_plans.free_all();
-    c->last_ndir = c->last_batch = 0;
-    for (int v = 0; v < kMaxBatch; v++) c->last_cvs[v] = nullptr;
     return MGM_OK;
 }
 

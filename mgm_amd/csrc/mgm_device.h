@@ -102,7 +102,9 @@ struct WtaRightParams {
     int num_cu;
     int seg, ring;       // set by the launcher: right pixels per workgroup, entries of the LDS ring
 };
-hipError_t launch_wta_right(const WtaRightParams &p, hipStream_t s);
+struct WtaChoice;  // (mgm_planner.h: what plan_wta / plan_wta_right decided)
+struct WtaRightChoice;
+hipError_t launch_wta_right(const WtaRightParams &p, const WtaRightChoice &c, hipStream_t s);
 
 // ---- ragged volumes in the range-proportional layout (mgm_pass_rel.hip, k_wta_rel): 64 label slots per pixel placed at the
 // pixel's own window, slot k <-> disparity base + k
@@ -198,7 +200,7 @@ hipError_t launch_nanscan(const float *C, long long n, unsigned *flag, hipStream
 hipError_t launch_pad(const float *C, long long npix, int L, int LP, float *Cp, uint8_t *C8p, int cbytes, unsigned *bad8, hipStream_t s);
 hipError_t launch_expand(const uint8_t *C8, int cbytes, long long n, float *C, hipStream_t s);
 hipError_t launch_expand_padded(const uint8_t *C8, int cbytes, long long npix, int L, int LP, float *C, hipStream_t s);
-hipError_t launch_wta(const WtaParams &p, hipStream_t s);
+hipError_t launch_wta(const WtaParams &p, const WtaChoice &c, hipStream_t s);
 long long tune_num(const char *key, long long dflt);  // development switches (MGM_HIP_TUNE; mgm_ctx.hip)
 hipError_t launch_median(const float *u, int nx, int ny, int nch, int radius, float *out, hipStream_t s);
 hipError_t launch_leftright(const float *dx, int nc, int nr, const float *Rdx, int Rnc, float threshold, float *out,
@@ -267,6 +269,20 @@ hipError_t launch_xcc_census(unsigned *mask, hipStream_t s);
 // ---------------------------------------------------------------------------
 #ifdef __HIPCC__
 __device__ __forceinline__ float f_inf() { return __builtin_huge_valf(); }
+__device__ __forceinline__ bool finite_bits(float x)
+{
+    return (__builtin_bit_cast(unsigned, x) & 0x7f800000u) != 0x7f800000u;
+}
+// floats ordered through their bit patterns, so that integer atomics can reduce them (k_minmax, k_wta_right's keys)
+__device__ __forceinline__ unsigned f2ord(float f)
+{
+    const unsigned u = __builtin_bit_cast(unsigned, f);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float ord2f(unsigned o)
+{
+    return __builtin_bit_cast(float, (o & 0x80000000u) ? (o & 0x7fffffffu) : ~o);
+}
 
 // Compact cost: an fp32 cost that is an integer in [0, 254] or +INF is stored as one byte
 // (255 = +INF).  Census costs with one descriptor word and AD costs of 8-bit images qualify; the

@@ -2,7 +2,7 @@
 // (mgm_ctx.hip: contexts, images, switches, timing; mgm_fillplan.h: how a cost volume gets filled, as pure functions of a
 // request; mgm_volume.hip: the volumes -- the stages of a filling around that plan and everything that allocates, converts or
 // invalidates one of a volume's copies; mgm_planner.h: the launch plan of the pass kernels as pure functions of a request;
-// mgm_plan.hip: the stages of a pass launch around it, the plans' caches and the winner search; mgm_api.hip: weights,
+// mgm_plan.hip: the stages of a pass launch around it, the plans' caches and the winner search, planned there too; mgm_api.hip: weights,
 // aggregation calls, the steps around them).  Nothing here is exported through include/mgm_hip.h; no compute happens on the
 // host and there is no CPU fallback.
 #pragma once
@@ -119,6 +119,72 @@ struct PlanCache {
     }
 };
 
+// What the context's last DENSE aggregation left behind, for whoever searches or downloads it later (the winner search of the same
+// call, mgm_wta_windowed_dev, mgm_wta_right_dev, mgm_lr_device_ptr, mgm_debug_download_*).  Written by the remember stage of
+// run_passes (mgm_plan.hip) and by nobody else.
+struct DenseRun {
+    long long nvol = 0;    // floats per Lr volume
+    long long stride = 0;  // floats between the Lr volumes of consecutive passes (>= nvol)
+    int ndir = 0;          // Lr volumes per slot
+    int batch = 0;         // slots: the volumes of the launch
+    int L = 0, Lk = 0;     // labels of that aggregation, and the label stride its kernels ran with (>= L)
+    bool wrote_min = false;  // the launch wrote the chunk minima of its Lr volumes (mgm_ctx::lmin)
+    bool pad_c8 = false;   // a padded launch (Lk > L) read compact padded copies of its volumes ...
+    int pad_cb = 1;        // ... of this many bytes per cost ...
+    const uint8_t *pad_ptr[kMaxBatch] = {};  // ... here: the context's pad8 buffers, or the volumes' own padded copies (mgm_cv::p8)
+    const mgm_cv *cvs[kMaxBatch] = {};       // the volumes (identities) ...
+    unsigned long long gens[kMaxBatch] = {};  // ... and their generations at that time
+    // "no dense aggregation to search": after a trim, or once a range-proportional aggregation has become the context's last.
+    // (`stride` stays: mgm_debug_probe_workspace probes the workspace, which a range-proportional aggregation leaves alone, at
+    // the stride of the last dense launch.)
+    void clear()
+    {
+        const long long keep = stride;
+        *this = DenseRun{};
+        stride = keep;
+    }
+    void forget(const mgm_cv *cv)  // (mgm_cv_free: the address may be handed out again)
+    {
+        for (int v = 0; v < kMaxBatch; v++)
+            if (cvs[v] == cv) cvs[v] = nullptr;
+    }
+    // is slot v still the volume it was, with the contents it had?
+    bool current(int v) const { return v >= 0 && v < batch && cvs[v] && cvs[v]->gen == gens[v]; }
+    int slot_of(const mgm_cv *C) const  // the slot of C, or -1 (a volume given twice: its last slot)
+    {
+        int slot = -1;
+        for (int v = 0; v < batch; v++)
+            if (cvs[v] == C && current(v)) slot = v;
+        return slot;
+    }
+    bool padded() const { return Lk > L; }
+    // pass `pass` of slot `slot` in the Lr workspace (mgm_ctx::lr), and its chunk minima in mgm_ctx::lmin (one float per 32 of
+    // the workspace)
+    const float *lr(const Buf &ws, int slot, int pass) const { return (const float *)ws.p + ((size_t)slot * ndir + pass) * stride; }
+    const float *lmin(const Buf &mins, int slot, int pass) const { return (const float *)mins.p + ((size_t)slot * ndir + pass) * (size_t)(stride / kChunkLabels); }
+};
+// ... and its last aggregation on the range-proportional copies of ragged volumes (mgm_pass_rel.hip; Lr volumes in mgm_ctx::lr_rel)
+struct RelRun {
+    int batch = 0, ndir = 0;
+    int slots = 0;  // label slots per pixel of volume 0's copy at that launch (the Lr stride mgm_debug_download_lr reads at)
+    long long stride = 0;
+    const mgm_cv *cvs[kMaxBatch] = {};
+    unsigned long long gens[kMaxBatch] = {};
+    void clear() { *this = RelRun{}; }
+    void forget(const mgm_cv *cv)
+    {
+        for (int v = 0; v < kMaxBatch; v++)
+            if (cvs[v] == cv) cvs[v] = nullptr;
+    }
+    int slot_of(const mgm_cv *C) const  // the slot of C with the contents it had, or -1
+    {
+        for (int v = 0; v < batch; v++)
+            if (cvs[v] == C && gens[v] == C->gen) return v;
+        return -1;
+    }
+    const float *lr(const Buf &ws, int slot, int pass) const { return (const float *)ws.p + ((size_t)slot * ndir + pass) * stride; }
+};
+
 struct Timing {
     const char *name;
     hipEvent_t a, b;
@@ -136,16 +202,12 @@ struct mgm_ctx {
     // and what the last such aggregation ran on (mgm_wta_windowed_dev searches it again)
     Buf lr_rel, hand_rel;
     // chunk minima of the dense Lr volumes (k_pass2, CHMIN): one float per 32 of c->lr, written by the last dense launch iff
-    // last_min; the pruned winner search reads them (run_wta).  wta_stats: its two counters' word on the device (timing or
+    // last.wrote_min; the pruned winner search reads them (run_wta).  wta_stats: its two counters' word on the device (timing or
     // debug statistics on), wta_stats_n: searches counted into it since the last aggregation call began (0: none was pruned)
     Buf lmin, wta_stats;  // (wta_stats: kWtaStatBytes)
-    bool last_min = false;
     int wta_stats_n = 0;
-    int rel_last_batch = 0, rel_last_ndir = 0;
-    int rel_last_slots = 0;  // label slots per pixel of volume 0's copy at that launch (the Lr stride mgm_debug_download_lr reads at)
-    long long rel_last_stride = 0;
-    const mgm_cv *rel_last_cvs[kMaxBatch] = {};
-    unsigned long long rel_last_gens[kMaxBatch] = {};
+    DenseRun last;    // the last aggregation, if it was a dense one ...
+    RelRun rel_last;  // ... or a range-proportional one (each remember stage clears the other)
     // Pipelined contexts (mgm_ctx_set_pipeline, depth >= 2): aggregation calls are DEFERRED and gathered -- up to `depth`
     // calls of the same geometry and settings become ONE launch of the pass kernel (see PendingAgg, pipe_flush)
     struct PendingAgg {
@@ -170,19 +232,8 @@ struct mgm_ctx {
     PlanCache<DenseRequest, DensePlan> dense_plans;  // plans + task tables of the dense kernels' launches, by request
     PlanCache<RelRequest, RelPlan> rel_plans;        // ... of the range-proportional kernels'
     int force_build = 0;  // 0 auto, 1 first build only (MGM_HIP_PASS_BUILD=1)
-    // last aggregate (for mgm_debug_download_lr)
-    long long last_nvol = 0;    // floats per volume
-    long long last_stride = 0;  // floats between the Lr volumes of consecutive passes (>= last_nvol)
-    int last_ndir = 0;
-    int last_batch = 0;
-    int last_L = 0, last_Lk = 0;          // labels of the last aggregation, and the label stride its kernels ran with (>= last_L)
     Buf padf[kMaxBatch], pad8[kMaxBatch];  // padded copies of the cost volumes of a launch whose label count was padded
     Buf wsel[kMaxBatch], wvals;            // two-valued weights (k_pass2, W2): selector words per volume; the value scan's words
-    bool last_pad_c8 = false;
-    const uint8_t *last_pad_ptr[kMaxBatch] = {};  // ... where they are: the context's pad8 buffers, or the volumes' own padded copies (mgm_cv::p8)
-    int last_pad_cb = 1;  // ... bytes per compact cost of those padded copies
-    const mgm_cv *last_cvs[kMaxBatch] = {};  // the volumes of the last aggregation (identities; mgm_cv_free clears the entry of a freed volume) ...
-    unsigned long long last_gens[kMaxBatch] = {};  // ... and their generations at that time
     bool pending_check = false;
     // self-validating hand-off slabs (k_pass2, TAGS): the layout the region was last cleared for (npass 0: unknown -- the next
     // launch clears it), and the tag of its last launch
@@ -221,6 +272,17 @@ struct DevSwitches {
 };
 const DevSwitches &dev();
 long long lr_pad_floats();
+// ... and the winner search's (MGM_HIP_TUNE=wta_*; A/B timing), copied into every request of its planner (plan_wta, plan_wta_right)
+struct WtaSwitches {
+    int prune_ppw;  // wta_prune_ppw=1|2: pixels per wave of the pruned search
+    int prune_wg;   // wta_prune_wg=<workgroups per CU> of the pruned search (0: 64)
+    int wg_per_cu;  // wta_wg_per_cu=<workgroups per CU> of the plain search (0: by the instance)
+    int packed;     // wta_packed=0: one pixel per slab also at 128 / 64 labels
+    int wide4;      // wta_wide4=0: the 8-direction instance also for NDIR <= 4
+    int quad;       // wta_quad=0: 192 / 384 labels on k_wta<3> / <6>
+    int right_seg;  // wta_right_seg=<right pixels per workgroup> of the right view's search (0: by the device)
+};
+const WtaSwitches &wta_switches();
 
 // Development switches live behind ONE variable: MGM_HIP_TUNE="key=value,key=value" (keys are the lower-case names of
 // DevSwitches' comments: deep, xcdq, xcdq_k, strips, wg_per_cu, subv, c8, pad, lazy_f32, w2, oneb, lr_pad, xflags, pass_build,

@@ -93,41 +93,26 @@ static int plan_error(mgm_ctx *c, int err)
 }
 
 // "this was the context's last aggregation": what mgm_wta_windowed_dev / mgm_debug_download_lr / the winner search of a later
-// call find.  pad8: the padded compact copies of a padded launch (per volume), or nullptr.
+// call find (DenseRun, RelRun: mgm_host.h).  pad8: the padded compact copies of a padded launch (per volume), or nullptr;
+// minima: the launch wrote the chunk minima of its Lr volumes.
 static void remember_dense(mgm_ctx *c, const mgm_cv *const *Cs, int nb, long long nvol, long long lr_stride, int nslots, int Lreal, int Lk, int pad_cb,
-                           const uint8_t *const *pad8)
+                           const uint8_t *const *pad8, bool minima)
 {
-    c->rel_last_batch = 0;  // (an earlier range-proportional aggregation of the same volume is no longer the context's last)
-    c->last_min = false;    // (run_passes sets it behind a launch that wrote the chunk minima)
-    c->last_nvol = nvol;
-    c->last_stride = lr_stride;
-    c->last_ndir = nslots;
-    c->last_batch = nb;
-    c->last_L = Lreal;
-    c->last_Lk = Lk;
-    c->last_pad_c8 = pad8 != nullptr;
-    c->last_pad_cb = pad_cb;
-    for (int v = 0; v < nb; v++) c->last_pad_ptr[v] = pad8 ? pad8[v] : nullptr;
-    for (int v = 0; v < kMaxBatch; v++) {
-        c->last_cvs[v] = v < nb ? Cs[v] : nullptr;
-        c->last_gens[v] = v < nb ? Cs[v]->gen : 0;
-    }
+    c->rel_last.clear();  // (an earlier range-proportional aggregation of the same volume is no longer the context's last)
+    DenseRun &d = c->last;
+    d = DenseRun{};
+    d.nvol = nvol, d.stride = lr_stride, d.ndir = nslots, d.batch = nb, d.L = Lreal, d.Lk = Lk;
+    d.wrote_min = minima;
+    d.pad_c8 = pad8 != nullptr, d.pad_cb = pad_cb;
+    for (int v = 0; v < nb; v++) d.pad_ptr[v] = pad8 ? pad8[v] : nullptr, d.cvs[v] = Cs[v], d.gens[v] = Cs[v]->gen;
 }
 static void remember_rel(mgm_ctx *c, const mgm_cv *const *Cs, int nb, int NDIR, long long stride)
 {
-    // (the dense Lr workspace no longer belongs to these volumes)
-    c->last_batch = 0;
-    c->last_ndir = 0;
-    c->last_min = false;
-    for (int v = 0; v < kMaxBatch; v++) c->last_cvs[v] = nullptr;
-    c->rel_last_batch = nb;
-    c->rel_last_ndir = NDIR;
-    c->rel_last_stride = stride;
-    c->rel_last_slots = Cs[0]->rel_slots;
-    for (int v = 0; v < kMaxBatch; v++) {
-        c->rel_last_cvs[v] = v < nb ? Cs[v] : nullptr;
-        c->rel_last_gens[v] = v < nb ? Cs[v]->gen : 0;
-    }
+    c->last.clear();  // (the dense Lr workspace no longer belongs to these volumes)
+    RelRun &d = c->rel_last;
+    d = RelRun{};
+    d.batch = nb, d.ndir = NDIR, d.stride = stride, d.slots = Cs[0]->rel_slots;
+    for (int v = 0; v < nb; v++) d.cvs[v] = Cs[v], d.gens[v] = Cs[v]->gen;
 }
 
 // MGM_HIP_TIMELINE=<file>: one line per work item of the launch (tools/timeline.py reads them) -- where the compute units'
@@ -290,7 +275,7 @@ static int run_passes_exact(mgm_ctx *c, const mgm_cv *const *Cs, const mgm_img *
         TimeScope t(c, "k_pass_exact");
         HIPCHK(c, launch_pass_exact(p, c->stream));
     }
-    remember_dense(c, Cs, nb, nvol, lr_stride, nslots, L, L, 1, nullptr);
+    remember_dense(c, Cs, nb, nvol, lr_stride, nslots, L, L, 1, nullptr, false);
     return MGM_OK;
 }
 
@@ -719,8 +704,7 @@ int run_passes(mgm_ctx *c, const mgm_cv *const *Cs, const mgm_img *const *w8s, i
     if (p.dbg && (r = print_pass_stats(c, p.dbg, (const int2 *)e->buf.p + 8, ntasks, first, PEND))) return r;
 
     // 7. what the context's last aggregation was: this dense one
-    remember_dense(c, Cs, nb, nvol, lr_stride, nslots, Lreal, L, o.cb, (o.padded && o.use_c8) ? pad8 : nullptr);
-    c->last_min = minima;
+    remember_dense(c, Cs, nb, nvol, lr_stride, nslots, Lreal, L, o.cb, (o.padded && o.use_c8) ? pad8 : nullptr, minima);
     return MGM_OK;
 }
 
@@ -731,28 +715,74 @@ bool wta_prune_enabled()
     return !(e && atoi(e) == 0) && tune_num("wta_prune", 1) != 0;
 }
 
+// The costs a search of C reads: the padded copies of the context's last dense launch if C ran as slot `slot` of it with a padded
+// label count (compact, else fp32), else the volume's own compact copy, else its fp32 volume (brought up to date here).
+// "Padded" is ONE rule: the caller names a slot, the launch padded, and the volume has the label count of that launch.
+// run_wta_right used to ask `Lk > L` alone: its only caller, mgm_wta_right_dev, finds the slot with DenseRun::slot_of and
+// refuses a volume whose label count is not the launch's, so both other terms held at every call.
+struct CostSource {
+    const float *C;
+    const uint8_t *C8;
+    int cbytes, L;  // bytes per compact cost; label stride of the copy
+    bool padded;
+};
+static int cost_source(mgm_ctx *c, const mgm_cv *C, int slot, CostSource *out)
+{
+    const DenseRun &d = c->last;
+    const int Lreal = C->dmax - C->dmin + 1;
+    CostSource s{};
+    s.padded = slot >= 0 && d.padded() && d.L == Lreal;
+    s.L = s.padded ? d.Lk : Lreal;
+    if (s.padded) {
+        s.C = d.pad_c8 ? nullptr : (const float *)c->padf[slot].p;
+        s.cbytes = d.pad_c8 ? d.pad_cb : 1;
+        s.C8 = d.pad_c8 ? d.pad_ptr[slot] : nullptr;
+    } else {
+        // (two-byte costs: the exact k_wta instances and k_wta_q read them -- label counts of the compact pass kernels)
+        s.cbytes = C->cbytes;
+        s.C8 = (C->c8_state == CopyState::Valid && c->force_build != 1) ? C->d8 : nullptr;
+        if (!s.C8)
+            if (int r = ensure_f32(c, C)) return r;
+        s.C = C->d;
+    }
+    *out = s;
+    return MGM_OK;
+}
+
 // K4-K6 over `npix` pixels starting at pixel `pix0` of C, reading pass p's Lr from lr + p*lr_stride.
 // `slot` >= 0: the volume was slot `slot` of the context's last aggregation; if that launch ran with a padded label
-// count, its padded cost copies and label stride are used (see run_passes).  slot < 0: plain [pix][L] layout.
+// count, its padded cost copies and label stride are used (cost_source).  slot < 0: plain [pix][L] layout.
 int run_wta(mgm_ctx *c, const mgm_cv *C, long long pix0, long long npix, const float *lr, long long lr_stride, int NDIR,
             int fix_overcount, int ridx, float *out, float *outcost, float *Sout, const float *wlo, const float *whi, int slot)
 {
-    const int Lreal = C->dmax - C->dmin + 1;
-    const bool padded = slot >= 0 && c->last_Lk > c->last_L && c->last_L == Lreal;
-    const int L = padded ? c->last_Lk : Lreal;
+    const DenseRun &d = c->last;
+    // 1. the costs
+    CostSource src;
+    if (int r = cost_source(c, C, slot, &src)) return r;
+    const int L = src.L;
+
+    // 2. the request: the call, what the last dense launch left for it, the switches
+    const WtaSwitches &sw = wta_switches();
+    WtaRequest q{};
+    q.npix = npix;
+    q.L = L, q.Lreal = C->dmax - C->dmin + 1, q.NDIR = NDIR, q.lpl = pass_lpl(L);
+    q.cbytes = src.cbytes, q.compact = src.C8 ? 1 : 0;
+    q.refine = ridx, q.want_S = Sout ? 1 : 0;
+    q.window = wlo ? 1 : 0, q.ragged = C->rlo ? 1 : 0;
+    q.in_last_run = slot >= 0 ? 1 : 0, q.last_min = (d.wrote_min && c->lmin.p) ? 1 : 0;
+    q.lr_is_last = (slot >= 0 && NDIR == d.ndir && lr == d.lr(c->lr, slot, 0) && lr_stride == d.stride) ? 1 : 0;
+    q.pix0_zero = pix0 == 0 ? 1 : 0, q.padded = src.padded ? 1 : 0, q.nvol_mod32 = (int)(lr_stride % 32), q.num_cu = c->num_cu;
+    q.sw_prune = wta_prune_enabled() ? 1 : 0, q.sw_prune_ppw = sw.prune_ppw, q.sw_prune_wg = sw.prune_wg, q.sw_wg_per_cu = sw.wg_per_cu;
+    q.sw_packed = sw.packed, q.sw_wide4 = sw.wide4, q.sw_quad = sw.quad;
+
+    // 3. the plan: family, instance, grid, pruned or not
+    const WtaChoice choice = plan_wta(q);
+
+    // 4. the kernel's parameters
     WtaParams w{};
-    if (padded) {
-        w.C = c->last_pad_c8 ? nullptr : (const float *)c->padf[slot].p + pix0 * L;
-        w.cbytes = c->last_pad_c8 ? c->last_pad_cb : 1;
-        w.C8 = c->last_pad_c8 ? c->last_pad_ptr[slot] + pix0 * L * w.cbytes : nullptr;
-    } else {
-        // (two-byte costs: the exact k_wta instances and k_wta_q read them -- label counts of the compact pass kernels)
-        w.cbytes = C->cbytes;
-        w.C8 = (C->c8_state == CopyState::Valid && c->force_build != 1) ? C->d8 + pix0 * L * w.cbytes : nullptr;
-        if (!w.C8)
-            if (int r = ensure_f32(c, C)) return r;
-        w.C = C->d ? C->d + pix0 * L : nullptr;
-    }
+    w.C = src.C ? src.C + pix0 * L : nullptr;
+    w.cbytes = src.cbytes;
+    w.C8 = src.C8 ? src.C8 + pix0 * L * src.cbytes : nullptr;
     w.Lr = lr;
     w.S = Sout;
     w.out = out;
@@ -760,7 +790,7 @@ int run_wta(mgm_ctx *c, const mgm_cv *C, long long pix0, long long npix, const f
     w.npix = npix;
     w.nvol = lr_stride;
     w.L = L;
-    w.Lreal = Lreal;
+    w.Lreal = q.Lreal;
     w.NDIR = NDIR;
     w.FIX = fix_overcount;
     w.dmin = C->dmin;
@@ -771,12 +801,11 @@ int run_wta(mgm_ctx *c, const mgm_cv *C, long long pix0, long long npix, const f
     w.clo = C->rlo ? C->rlo + pix0 : nullptr;
     w.chi = C->rhi ? C->rhi + pix0 : nullptr;
     w.num_cu = c->num_cu;
-    // The pruned search: the volume was slot `slot` of the context's last dense launch, that launch wrote the chunk minima of
-    // its Lr volumes (c->last_min: decided by plan_wta_prune for exactly this search) and `lr` is that slot's first volume.
-    if (slot >= 0 && c->last_min && c->lmin.p && !Sout && !wlo && !w.clo && ridx <= 1 && !padded && pix0 == 0 && w.C8 && w.cbytes == 1 && L == 256 &&
-        lr == (const float *)c->lr.p + (size_t)slot * NDIR * c->last_stride && lr_stride == c->last_stride && NDIR == c->last_ndir) {
-        w.Lmin = (const float *)c->lmin.p + (size_t)slot * NDIR * (size_t)(c->last_stride / kChunkLabels);
-        // its two counters (mgm_debug_wta_stats) only while somebody is looking: timing or debug statistics on
+
+    // 5. the pruned search reads the slot's chunk minima; its two counters (mgm_debug_wta_stats) only while somebody is looking:
+    // timing or debug statistics on
+    if (choice.prune) {
+        w.Lmin = d.lmin(c->lmin, slot, 0);
         if ((c->timing || c->debug_stats) && npix < (1ll << 24)) {
             const bool fresh = c->wta_stats.p == nullptr;
             if (int r = reserve(c, c->wta_stats, kWtaStatBytes)) return r;
@@ -785,8 +814,10 @@ int run_wta(mgm_ctx *c, const mgm_cv *C, long long pix0, long long npix, const f
             c->wta_stats_n++;
         }
     }
+
+    // 6. the launch
     TimeScope t(c, "k_wta");
-    HIPCHK(c, launch_wta(w, c->stream));
+    if (hipError_t e = launch_wta(w, choice, c->stream)) return hipfail(c, e, "launch_wta(w, c->stream)");  // (the message names the call as it always has)
     return MGM_OK;
 }
 
@@ -794,39 +825,35 @@ int run_wta(mgm_ctx *c, const mgm_cv *C, long long pix0, long long npix, const f
 // (mgm_wta_right_dev has checked that C is that volume).  Costs and label stride as run_wta takes them for such a slot.
 int run_wta_right(mgm_ctx *c, const mgm_cv *C, int slot, int NDIR, int fix_overcount, int ridx, int vnx, float *out, float *outcost)
 {
-    const int Lreal = C->dmax - C->dmin + 1;
-    const bool padded = c->last_Lk > c->last_L;
+    const DenseRun &d = c->last;
+    CostSource src{};
+    src.cbytes = 1;
+    if (fix_overcount == 1)  // (else the costs are not read)
+        if (int r = cost_source(c, C, slot, &src)) return r;
     WtaRightParams w{};
-    if (fix_overcount != 1) {
-        w.cbytes = 1;  // (the costs are not read)
-    } else if (padded) {
-        w.C = c->last_pad_c8 ? nullptr : (const float *)c->padf[slot].p;
-        w.cbytes = c->last_pad_c8 ? c->last_pad_cb : 1;
-        w.C8 = c->last_pad_c8 ? c->last_pad_ptr[slot] : nullptr;
-    } else {
-        w.cbytes = C->cbytes;
-        w.C8 = (C->c8_state == CopyState::Valid && c->force_build != 1) ? C->d8 : nullptr;
-        if (!w.C8)
-            if (int r = ensure_f32(c, C)) return r;
-        w.C = C->d;
-    }
-    w.Lr = (const float *)c->lr.p + (size_t)slot * NDIR * c->last_stride;
+    w.C = src.C;
+    w.C8 = src.C8;
+    w.cbytes = src.cbytes;
+    w.Lr = d.lr(c->lr, slot, 0);
     w.out = out;
     w.outcost = outcost;
-    w.nvol = c->last_stride;
+    w.nvol = d.stride;
     w.nx = C->nx;
     w.ny = C->ny;
     w.vnx = vnx;
-    w.L = Lreal;
-    w.Lk = c->last_Lk;
+    w.L = C->dmax - C->dmin + 1;
+    w.Lk = d.Lk;
     w.NDIR = NDIR;
     w.FIX = fix_overcount;
     w.dmin = C->dmin;
     w.dmax = C->dmax;
     w.refine = ridx;
     w.num_cu = c->num_cu;
+    // MGM_HIP_WTA_RIGHT_ANY=1 (read at every call: tests switch it inside one process): the diagonal walk everywhere
+    const char *ea = getenv("MGM_HIP_WTA_RIGHT_ANY");
+    const WtaRightChoice choice = plan_wta_right(WtaRightRequest{w.L, w.Lk, w.nx, w.ny, w.vnx, w.dmin, w.dmax, w.num_cu, wta_switches().right_seg, (ea && atoi(ea) != 0) ? 1 : 0});
     TimeScope t(c, "k_wta_right");
-    HIPCHK(c, launch_wta_right(w, c->stream));
+    if (hipError_t e = launch_wta_right(w, choice, c->stream)) return hipfail(c, e, "launch_wta_right(w, c->stream)");  // (as above)
     return MGM_OK;
 }
 
@@ -878,13 +905,13 @@ int run_wta_rel(mgm_ctx *c, const mgm_cv *C, int slot, int NDIR, int fix_overcou
     w.cb = C->rel_cb;
     w.rlo = C->rlo;
     w.rhi = C->rhi;
-    w.Lr = (const float *)c->lr_rel.p + (size_t)slot * NDIR * c->rel_last_stride;
+    w.Lr = c->rel_last.lr(c->lr_rel, slot, 0);
     w.wlo = wlo;
     w.whi = whi;
     w.out = out;
     w.outcost = outcost;
     w.npix = (long long)npix;
-    w.nvol = c->rel_last_stride;
+    w.nvol = c->rel_last.stride;
     w.NDIR = NDIR;
     w.FIX = fix_overcount;
     w.refine = ridx;

@@ -3,6 +3,8 @@
 // sharing, workgroups per CU, deep rings, per-XCD queues, strips, the hand-off layout, the ticket order and the dealt task
 // table).  Plain C++17, standard headers only: no device, no context, no environment -- mgm_plan.hip fills the requests,
 // caches the plans BY the requests and launches; tests/test_planner.py runs the planner on the host.
+// The winner search is planned here as well (plan_wta, plan_wta_right, plan_wta_rel at the end: which instance, which grid,
+// pruned or not); tests/test_wta_plan.py.
 #pragma once
 #include <algorithm>
 #include <cstring>
@@ -676,6 +678,148 @@ inline RelPlan plan_rel(const RelRequest &q)
     }
     p.ntasks = (int)p.table.size();
     return p;
+}
+
+// ---- the winner search (mgm_wta.hip) ---------------------------------------------------------------------------------------
+// Which kernel instance a search runs on, and on how many workgroups: a function of the request and nothing else.  mgm_plan.hip
+// fills the requests (run_wta, run_wta_right), the launchers of mgm_wta.hip are tables from a choice to its instance, and
+// tests/test_wta_plan.py holds the planner against a restatement of the launchers it replaced.
+struct WtaRequest {
+    long long npix;           // pixels of the call
+    int L, Lreal, NDIR, lpl;  // label stride, labels that exist, passes; what the kernels report: pass_lpl(L)
+    int cbytes, compact;      // bytes per cost of the compact copy; the search reads a compact copy (WtaParams::C8)
+    int refine, want_S;       // refinement index; the search writes the corrected volume
+    int window, ragged;       // range images given (WtaParams::wlo); the volume has ranges of its own (WtaParams::clo)
+    // the volume was a slot of the context's last dense launch; that launch wrote its chunk minima and they are still there; the Lr
+    // pointer, its stride and NDIR are that launch's own (the slot's first volume, every pass of it)
+    int in_last_run, last_min, lr_is_last;
+    int pix0_zero, padded, nvol_mod32, num_cu;  // the call starts at pixel 0; the launch ran with padded labels; Lr stride % 32; CUs
+    // the switches (WtaSwitches, mgm_host.h): MGM_HIP_WTA_PRUNE / wta_prune, then MGM_HIP_TUNE=wta_prune_ppw=1|2,
+    // wta_prune_wg=<workgroups per CU>, wta_wg_per_cu=<the same for the plain search>, wta_packed=0, wta_wide4=0, wta_quad=0
+    int sw_prune, sw_prune_ppw, sw_prune_wg, sw_wg_per_cu, sw_packed, sw_wide4, sw_quad;
+};
+static_assert(std::has_unique_object_representations_v<WtaRequest>, "WtaRequest: integers only, no padding");
+enum WtaFamily { kWtaRefuse = 0, kWtaPlain, kWtaPacked, kWtaQuad, kWtaAny, kWtaPruned };
+struct WtaChoice {
+    long long grid;  // workgroups of 256 threads
+    int family;      // kWtaRefuse: hipErrorInvalidValue
+    // the instance's template arguments: k_wta<LPL, PPW, EXACT, MAXD, SUB> (plain and packed), k_wta_q<64 * LPL, MAXD>,
+    // k_wta_pruned<PPW, MAXD, ALLD>, k_wta_any (none); those an instance does not have are 0
+    int LPL, PPW, EXACT, MAXD, SUB, ALLD;
+    int prune;       // the search reads the chunk minima: WtaParams::Lmin is to be passed
+};
+static_assert(std::has_unique_object_representations_v<WtaChoice>, "WtaChoice: integers only, no padding");
+constexpr int kWtaWidestLabels = 2048;  // the widest k_wta instance (64 * kMaxLPL; mgm_wta.hip asserts it)
+
+inline WtaChoice plan_wta(const WtaRequest &q)
+{
+    WtaChoice c{};
+    const long long cus = q.num_cu > 0 ? q.num_cu : 256;
+    const int maxd = q.NDIR <= 4 ? 4 : kMaxDirs;
+    // The pruned search: the volume was a slot of the context's last dense launch, that launch wrote the chunk minima of its Lr
+    // volumes (decided by plan_wta_prune for exactly this search) and the call reads that slot's volumes whole.  (sw_prune: what
+    // plan_wta_prune was asked with -- a search of a slot runs in the call that launched it, or has a window.)
+    c.prune = q.sw_prune != 0 && q.in_last_run != 0 && q.last_min != 0 && q.want_S == 0 && q.window == 0 && q.ragged == 0 && q.refine <= 1 && q.padded == 0 &&
+              q.pix0_zero != 0 && q.compact != 0 && q.cbytes == 1 && q.L == 256 && q.lr_is_last != 0;
+    if (c.prune) {
+        // (what k_wta_pruned is built for, checked where it is launched from: 256 labels, no padding, one-byte compact costs, ...)
+        if (q.Lreal != 256 || q.nvol_mod32 != 0) return c;
+        const int pw = (q.sw_prune_ppw == 1 || (q.NDIR != 4 && q.NDIR != 8)) ? 1 : 2;
+        c.grid = std::min((q.npix + 4 * pw - 1) / (4 * pw), cus * (q.sw_prune_wg > 0 ? q.sw_prune_wg : 64));
+        c.family = kWtaPruned, c.PPW = pw, c.MAXD = maxd, c.ALLD = (q.NDIR == 4 || q.NDIR == 8) ? 1 : 0;
+        return c;
+    }
+    const int per_cu = q.sw_wg_per_cu > 0 ? q.sw_wg_per_cu : 0;
+    const int exact = q.Lreal == q.L ? 1 : 0;
+    const bool packed = q.sw_packed != 0 && exact && (q.L == 128 || q.L == 64) && q.npix % (256 / q.L) == 0;
+    // A bounded grid (workgroups of 4 waves), grid-stride beyond it.  Measured at 1920x1080 (8 / 4 directions): one pixel per
+    // slab is fastest at ~768 workgroups per CU (2.99 ms at 16 -> 2.73 ms: 6.4 TB/s, the read ceiling of the part), several
+    // pixels per slab at ~128 (0.83 -> 0.80 ms); far larger grids lose again.
+    c.grid = std::min((q.npix + 3) / 4, cus * (per_cu ? per_cu : (packed ? 128 : 768)));  // (an upper bound: waves take several pixels per iteration)
+    if (q.L > kWtaWidestLabels) {
+        c.family = kWtaAny;
+        return c;
+    }
+    // 192 / 384 labels: four / two pixels per three 256-float slabs
+    if (q.sw_quad != 0 && exact && (q.L == 192 || q.L == 384) && q.npix % (768 / q.L) == 0 && q.window == 0 && q.ragged == 0 && q.refine <= 1) {
+        c.grid = std::min((q.npix / (768 / q.L) + 3) / 4, cus * (per_cu ? per_cu : 256));
+        c.family = kWtaQuad, c.LPL = q.L / 64, c.MAXD = maxd;
+        return c;
+    }
+    // 128 and 64 labels: two / four pixels per 256-float slab (16-byte loads, one butterfly for all of them)
+    if (packed) {
+        c.family = kWtaPacked, c.LPL = 4, c.PPW = q.NDIR <= 4 ? 4 : 2, c.EXACT = 1, c.MAXD = maxd, c.SUB = 256 / q.L;
+        return c;
+    }
+    // pixels per wave and iteration of the instances without a padding lane (up to 512 labels; 768 and 1024: one)
+    int ppw = 0;
+    switch (q.lpl) {
+        case 1: case 2: ppw = 4; break;
+        case 3: ppw = 2; break;
+        case 4: ppw = 3; break;
+        case 6: case 8: case 12: case 16: case 24: case 32: ppw = 1; break;
+        default: return c;
+    }
+    c.family = kWtaPlain, c.LPL = q.lpl, c.PPW = 1, c.MAXD = kMaxDirs, c.SUB = 1;
+    if (q.L == 64 * q.lpl && q.lpl <= 16) {  // (24 and 32 labels per lane: the guarded instances only)
+        c.EXACT = 1, c.PPW = ppw;
+        if (q.lpl <= 8 && q.NDIR <= 4 && q.sw_wide4 != 0) c.PPW = 2 * ppw, c.MAXD = 4;  // at most 4 directions: twice the slabs fit the registers
+    }
+    return c;
+}
+
+// the right view's search (k_wta_right / k_wta_right_any)
+struct WtaRightRequest {
+    int L, Lk, nx, ny, vnx, dmin, dmax, num_cu;
+    int sw_right_seg, sw_right_any;  // MGM_HIP_TUNE=wta_right_seg=<right pixels per workgroup>; MGM_HIP_WTA_RIGHT_ANY=1: the diagonal walk everywhere
+};
+static_assert(std::has_unique_object_representations_v<WtaRightRequest>, "WtaRightRequest: integers only, no padding");
+enum WtaRightFamily { kRightRefuse = 0, kRightStream, kRightDiagonal };
+struct WtaRightChoice {
+    long long grid;
+    int family, LPL, PPW;  // k_wta_right<LPL, PPW>; the diagonal walk has no arguments (0)
+    int seg, ring;         // WtaRightParams::seg / ring of the streaming kernel: right pixels per workgroup, entries of the LDS ring
+};
+inline WtaRightChoice plan_wta_right(const WtaRightRequest &q)
+{
+    WtaRightChoice c{};
+    if (q.L < 1 || q.Lk < q.L || q.nx < 1 || q.ny < 1 || q.vnx < 1 || q.dmax - q.dmin + 1 != q.L) return c;
+    const int cus = q.num_cu > 0 ? q.num_cu : 256;
+    const int lpl = q.Lk % 64 == 0 ? q.Lk / 64 : 0;
+    const bool stream = q.sw_right_any == 0 && (lpl == 1 || lpl == 2 || lpl == 3 || lpl == 4 || lpl == 6 || lpl == 8 || lpl == 12 || lpl == 16);
+    if (!stream) {
+        c.family = kRightDiagonal;
+        c.grid = std::min(((long long)q.vnx * q.ny + 3) / 4, (long long)cus * 64);
+        return c;
+    }
+    // Segments of a row: a workgroup re-reads the L-1 left pixels ahead of its segment, so a row is split only as far as the
+    // device needs workgroups (about four per compute unit), and never below max(64, L) right pixels.
+    const int want = (4 * cus + q.ny - 1) / q.ny;  // segments per row
+    int seg = std::max((q.vnx + want - 1) / want, std::max(64, q.L));
+    if (q.sw_right_seg > 0) seg = q.sw_right_seg;
+    c.seg = std::min(seg, q.vnx);
+    c.grid = (long long)q.ny * ((q.vnx + c.seg - 1) / c.seg);
+    if (c.grid > 0x7fffffffll) return c;
+    c.family = kRightStream, c.LPL = lpl, c.PPW = lpl <= 4 ? 2 : 1;
+    c.ring = 64;
+    while (c.ring < q.L - 1 + 2 * 4 * c.PPW) c.ring *= 2;
+    return c;
+}
+
+// the search on the range-proportional layout (k_wta_rel<SPL, CB>): label slots per lane, bytes per cost code
+struct WtaRelRequest {
+    long long npix, num_cu;
+    int slots, cb;
+};
+static_assert(std::has_unique_object_representations_v<WtaRelRequest>, "WtaRelRequest: integers only, no padding");
+struct WtaRelChoice {
+    long long grid;
+    int SPL, CB;
+};
+inline WtaRelChoice plan_wta_rel(const WtaRelRequest &q)
+{
+    const long long groups = (q.npix + 15) / 16;  // four waves of four pixels per block
+    return WtaRelChoice{std::max(1ll, std::min(groups, q.num_cu * 64)), q.slots == 128 ? 8 : 4, q.cb == 4 ? 4 : (q.cb == 2 ? 2 : 1)};
 }
 
 }  // namespace mgm

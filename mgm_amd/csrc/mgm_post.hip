@@ -4,6 +4,7 @@
 //                                            (of the total order: -0 below +0, in both kernels -- DESIGN section 1)
 //   leftright_test     mgm.cc:68-91          |x - (Lx + R[Lx])| > tau, or Lx outside the other image  =>  NaN
 //   back-projection    mgm.cc:433-443        v sampled at x + d (the reference's float index arithmetic), else u
+//   update_dmin_dmax   mgm.cc:120-158        the ranges of the next TSGM_ITER iteration around the current map (k_minmax, k_update_ranges)
 //
 // One thread per pixel; W*H work, nothing here is hot.  Default floating point (NaN-honouring).
 #include "mgm_device.h"
@@ -174,6 +175,82 @@ hipError_t launch_backproject(const float *u, int nx, int ny, int nch, const flo
 {
     const long long n = (long long)nx * ny * nch;
     hipLaunchKernelGGL(k_backproject, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, u, nx, ny, nch, v, vnx, vny, disp, out);
+    return hipGetLastError();
+}
+
+// ---- update_dmin_dmax (mgm.cc:120-158) + the two remove_nonfinite_values_Img calls that follow it (387-388) ------
+// global finite minimum / maximum of the disparity map (image_minmax, img_tools.h:183-199): floats ordered
+// through their bit patterns so that integer atomics can reduce them
+__global__ void __launch_bounds__(256) k_minmax_init(unsigned *mm)
+{
+    mm[0] = f2ord(__builtin_huge_valf());   // gmin = +INF
+    mm[1] = f2ord(-__builtin_huge_valf());  // gmax = -INF
+}
+__global__ void __launch_bounds__(256) k_minmax(const float *__restrict__ u, long long n, unsigned *mm)
+{
+    float lo = __builtin_huge_valf(), hi = -__builtin_huge_valf();
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+        const float v = u[i];
+        if (finite_bits(v)) {
+            lo = v < lo ? v : lo;
+            hi = v > hi ? v : hi;
+        }
+    }
+    atomicMin(mm + 0, f2ord(lo));
+    atomicMax(mm + 1, f2ord(hi));
+}
+__global__ void __launch_bounds__(256) k_update_ranges(const float *__restrict__ outoff, int nx, int ny, int slack, int r,
+                                                       const unsigned *__restrict__ mm, float *__restrict__ dminI,
+                                                       float *__restrict__ dmaxI)
+{
+    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (long long)nx * ny) return;
+    const int i = (int)(idx % nx), j = (int)(idx / nx);
+    const float gmin = ord2f(mm[0]), gmax = ord2f(mm[1]);
+    float dmin = __builtin_huge_valf(), dmax = -__builtin_huge_valf();
+    for (int dj = -r; dj <= r; dj++)
+        for (int di = -r; di <= r; di++) {
+            int x = i + di, y = j + dj;  // valneumann
+            x = x >= 0 ? x : 0;
+            x = x < nx ? x : nx - 1;
+            y = y >= 0 ? y : 0;
+            y = y < ny ? y : ny - 1;
+            const float v = outoff[x + (long long)y * nx];
+            const float a = finite_bits(v) ? v - slack : gmin - slack;
+            const float b = finite_bits(v) ? v + slack : gmax + slack;
+            dmin = __builtin_fminf(dmin, a);
+            dmax = __builtin_fmaxf(dmax, b);
+        }
+    float lo = dminI[idx], hi = dmaxI[idx];
+    if (finite_bits(dmin)) {
+        lo = dmin;
+        hi = dmax;
+    }
+    // remove_nonfinite_values_Img(dminI, gmin), (dmaxI, gmax)
+    dminI[idx] = finite_bits(lo) ? lo : gmin;
+    dmaxI[idx] = finite_bits(hi) ? hi : gmax;
+}
+
+// image_minmax alone: mm[0] / mm[1] receive the finite minimum / maximum of u as ordered bit patterns (+INF / -INF when
+// there is no finite sample); mgm_pyramid.hip reads them the same way
+hipError_t launch_minmax(const float *u, long long n, unsigned *mm, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_minmax_init, dim3(1), dim3(1), 0, s, mm);
+    long long nb = (n + 255) / 256;
+    if (nb > 1024) nb = 1024;
+    hipLaunchKernelGGL(k_minmax, dim3((unsigned)nb), dim3(256), 0, s, u, n, mm);
+    return hipGetLastError();
+}
+
+hipError_t launch_update_ranges(const float *outoff, int nx, int ny, int slack, int radius, float *dminI, float *dmaxI,
+                                float *scratch2, hipStream_t s)
+{
+    unsigned *mm = reinterpret_cast<unsigned *>(scratch2);
+    const long long n = (long long)nx * ny;
+    if (slack < 0) slack = -slack;
+    if (hipError_t e = launch_minmax(outoff, n, mm, s)) return e;
+    hipLaunchKernelGGL(k_update_ranges, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, outoff, nx, ny, slack, radius, mm, dminI,
+                       dmaxI);
     return hipGetLastError();
 }
 

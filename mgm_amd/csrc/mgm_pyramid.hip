@@ -20,10 +20,6 @@
 namespace mgm {
 
 __device__ __forceinline__ bool pyr_finite(float x) { return (__builtin_bit_cast(unsigned, x) & 0x7f800000u) != 0x7f800000u; }
-__device__ __forceinline__ float pyr_ord2f(unsigned o)  // (the inverse of k_minmax's ordering of floats, mgm_wta.hip)
-{
-    return __builtin_bit_cast(float, (o & 0x80000000u) ? (o & 0x7fffffffu) : ~o);
-}
 
 __global__ void __launch_bounds__(256) k_fill(float *__restrict__ p, long long n, float value)
 {
@@ -122,7 +118,7 @@ __global__ void __launch_bounds__(256) k_ranges_from_coarse(const float *__restr
     if (live) {
         const int cnx = (nx + 1) / 2;
         const int i = (int)(idx % nx), j = (int)(idx / nx);
-        const float gmin = 2.0f * pyr_ord2f(mm[0]), gmax = 2.0f * pyr_ord2f(mm[1]);
+        const float gmin = 2.0f * ord2f(mm[0]), gmax = 2.0f * ord2f(mm[1]);
         const int x0 = (i - r > 0 ? i - r : 0) >> 1, x1 = (i + r < nx ? i + r : nx - 1) >> 1;
         const int y0 = (j - r > 0 ? j - r : 0) >> 1, y1 = (j + r < ny ? j + r : ny - 1) >> 1;
         float dmin = __builtin_huge_valf(), dmax = -__builtin_huge_valf();

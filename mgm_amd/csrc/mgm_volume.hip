@@ -604,19 +604,16 @@ int mgm_cv_free(mgm_ctx *c, mgm_cv *cv)
         (void)hipSetDevice(c->device);
         (void)hipStreamSynchronize(c->stream);
     }
-    for (mgm_ctx *o : {c, cv->owner})
-        if (o)
-            for (int v = 0; v < kMaxBatch; v++)
-                if (o->last_cvs[v] == cv) o->last_cvs[v] = nullptr;
+    for (mgm_ctx *o : {c, cv->owner})  // no context's record of its last aggregation keeps the address
+        if (o) {
+            o->last.forget(cv);
+            o->rel_last.forget(cv);
+        }
     if (cv->d) (void)hipFree(cv->d);
     if (cv->d8) (void)hipFree(cv->d8);
     if (cv->p8) (void)hipFree(cv->p8);
     if (cv->bad8) (void)hipFree(cv->bad8);
     if (cv->relbuf) (void)hipFree(cv->relbuf);
-    for (mgm_ctx *o : {c, cv->owner})
-        if (o)
-            for (int v = 0; v < kMaxBatch; v++)
-                if (o->rel_last_cvs[v] == cv) o->rel_last_cvs[v] = nullptr;
     if (cv->rlo) (void)hipFree(cv->rlo);
     if (cv->rhi) (void)hipFree(cv->rhi);
     delete cv;

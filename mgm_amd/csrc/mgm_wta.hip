@@ -13,13 +13,9 @@
 #include <cstdlib>
 
 #include "mgm_device.h"
+#include "mgm_planner.h"
 
 namespace mgm {
-
-__device__ __forceinline__ bool finite_bits(float x)
-{
-    return (__builtin_bit_cast(unsigned, x) & 0x7f800000u) != 0x7f800000u;
-}
 
 // refine.h:70-92
 __device__ __forceinline__ void vfit(float v0, float v1, float v2, float &v_min, float &x_min)
@@ -595,103 +591,61 @@ __global__ void __launch_bounds__(256) k_wta_pruned(const WtaParams P)
     if (P.stats && lane == 0) atomicAdd(P.stats + (blockIdx.x & 63) * 16, ((unsigned long long)npx << 32) | nloaded);
 }
 
-hipError_t launch_wta(const WtaParams &p, hipStream_t s)
+// The launch tables: from a choice of the planner (plan_wta, mgm_planner.h) to its instance.  Nothing is decided here; a choice
+// that names no instance of its table, and the planner's refusals, are hipErrorInvalidValue.
+static_assert(kWtaWidestLabels == kMaxLPL * 64, "plan_wta sends wider volumes to k_wta_any");
+hipError_t launch_wta(const WtaParams &p, const WtaChoice &c, hipStream_t s)
 {
-    if (p.Lmin) {  // the pruned search (run_wta has checked what it needs: 256 labels, no padding, one-byte compact costs, ...)
-        if (p.L != 256 || p.Lreal != 256 || !p.C8 || p.cbytes != 1 || p.S || p.wlo || p.clo || p.refine > 1 || p.nvol % 32 != 0) return hipErrorInvalidValue;
-        static int ppw = -1, wgs = -1;  // MGM_HIP_TUNE=wta_prune_ppw=1|2, wta_prune_wg=<workgroups per CU> (A/B timing)
-        if (ppw < 0) ppw = (int)tune_num("wta_prune_ppw", 2);
-        if (wgs < 0) wgs = (int)tune_num("wta_prune_wg", 0);
-        const int pw = (ppw == 1 || (p.NDIR != 4 && p.NDIR != 8)) ? 1 : 2;
-        long long nb = (p.npix + 4 * pw - 1) / (4 * pw);
-        const long long cap = (long long)(p.num_cu > 0 ? p.num_cu : 256) * (wgs > 0 ? wgs : 64);
-        if (nb > cap) nb = cap;
-        const dim3 grid((unsigned)nb), block(256);
-        if (p.NDIR == 8 && pw == 2) hipLaunchKernelGGL((k_wta_pruned<2, 8, true>), grid, block, 0, s, p);
-        else if (p.NDIR == 8) hipLaunchKernelGGL((k_wta_pruned<1, 8, true>), grid, block, 0, s, p);
-        else if (p.NDIR == 4 && pw == 2) hipLaunchKernelGGL((k_wta_pruned<2, 4, true>), grid, block, 0, s, p);
-        else if (p.NDIR == 4) hipLaunchKernelGGL((k_wta_pruned<1, 4, true>), grid, block, 0, s, p);
-        else if (p.NDIR < 4) hipLaunchKernelGGL((k_wta_pruned<1, 4, false>), grid, block, 0, s, p);
-        else hipLaunchKernelGGL((k_wta_pruned<1, 8, false>), grid, block, 0, s, p);
-        return hipGetLastError();
+    const dim3 grid((unsigned)c.grid), block(256);
+#define WTA(LPL_, PPW_, EXACT_, MAXD_, SUB_)                                                                     \
+    if (c.LPL == LPL_ && c.PPW == PPW_ && c.EXACT == EXACT_ && c.MAXD == MAXD_ && c.SUB == SUB_) {               \
+        hipLaunchKernelGGL((k_wta<LPL_, PPW_, EXACT_ != 0, MAXD_, SUB_>), grid, block, 0, s, p);                 \
+        return hipGetLastError();                                                                                \
     }
-    long long nb = (p.npix + 3) / 4;  // (an upper bound: waves take several pixels per iteration)
-    static int per_cu = -1;  // MGM_HIP_WTA_WG_PER_CU=n overrides the grid bound (A/B timing)
-    if (per_cu < 0) {
-        per_cu = (int)tune_num("wta_wg_per_cu", 0);
-        if (per_cu < 0) per_cu = 0;
+#define WTA_Q(LPL_, MAXD_)                                                                                       \
+    if (c.LPL == LPL_ && c.MAXD == MAXD_) {                                                                      \
+        hipLaunchKernelGGL((k_wta_q<64 * LPL_, MAXD_>), grid, block, 0, s, p);                                   \
+        return hipGetLastError();                                                                                \
     }
-    static int packed = -1;  // MGM_HIP_WTA_PACKED=0: one pixel per slab also at 128 / 64 labels (A/B timing)
-    if (packed < 0) packed = tune_num("wta_packed", 1) != 0;
-    const bool use_packed = packed && p.Lreal == p.L && (p.L == 128 || p.L == 64) && p.npix % (256 / p.L) == 0;
-    // A bounded grid (workgroups of 4 waves), grid-stride beyond it.  Measured at 1920x1080 (8 / 4 directions): one
-    // pixel per slab is fastest at ~768 workgroups per CU (2.99 ms at 16 -> 2.73 ms: 6.4 TB/s, the read ceiling of the
-    // part), several pixels per slab at ~128 (0.83 -> 0.80 ms); far larger grids lose again.
-    const long long cap = (long long)(p.num_cu > 0 ? p.num_cu : 256) * (per_cu ? per_cu : (use_packed ? 128 : 768));
-    if (nb > cap) nb = cap;
-    const dim3 grid((unsigned)nb), block(256);
-    static int wide4 = -1;  // MGM_HIP_WTA_WIDE4=0: the 8-direction instance also for NDIR <= 4 (A/B timing)
-    if (wide4 < 0) wide4 = tune_num("wta_wide4", 1) != 0;
-    if (p.L > kMaxLPL * 64) {  // beyond the widest k_wta instance
-        hipLaunchKernelGGL(k_wta_any, grid, block, 0, s, p);
-        return hipGetLastError();
+#define WTA_PRUNED(PPW_, MAXD_, ALLD_)                                                                           \
+    if (c.PPW == PPW_ && c.MAXD == MAXD_ && c.ALLD == ALLD_) {                                                   \
+        hipLaunchKernelGGL((k_wta_pruned<PPW_, MAXD_, ALLD_ != 0>), grid, block, 0, s, p);                       \
+        return hipGetLastError();                                                                                \
     }
-    static int quad = -1;  // MGM_HIP_WTA_QUAD=0: 192 / 384 labels on k_wta<3> / <6> (A/B timing)
-    if (quad < 0) quad = tune_num("wta_quad", 1) != 0;
-    if (quad && p.Lreal == p.L && (p.L == 192 || p.L == 384) && p.npix % (768 / p.L) == 0 && !p.wlo && !p.clo && p.refine <= 1) {
-        long long nq = (p.npix / (768 / p.L) + 3) / 4;
-        const long long capq = (long long)(p.num_cu > 0 ? p.num_cu : 256) * (per_cu ? per_cu : 256);
-        if (nq > capq) nq = capq;
-        const dim3 gq((unsigned)nq);
-        if (p.L == 192) {
-            if (p.NDIR <= 4) hipLaunchKernelGGL((k_wta_q<192, 4>), gq, block, 0, s, p);
-            else hipLaunchKernelGGL((k_wta_q<192, kMaxDirs>), gq, block, 0, s, p);
-        } else {
-            if (p.NDIR <= 4) hipLaunchKernelGGL((k_wta_q<384, 4>), gq, block, 0, s, p);
-            else hipLaunchKernelGGL((k_wta_q<384, kMaxDirs>), gq, block, 0, s, p);
-        }
-        return hipGetLastError();
-    }
-    // 128 and 64 labels: two / four pixels per 256-float slab (16-byte loads, one butterfly for all of them)
-    if (use_packed) {
-        if (p.L == 128) {
-            if (p.NDIR <= 4) hipLaunchKernelGGL((k_wta<4, 4, true, 4, 2>), grid, block, 0, s, p);
-            else hipLaunchKernelGGL((k_wta<4, 2, true, kMaxDirs, 2>), grid, block, 0, s, p);
-        } else {
-            if (p.NDIR <= 4) hipLaunchKernelGGL((k_wta<4, 4, true, 4, 4>), grid, block, 0, s, p);
-            else hipLaunchKernelGGL((k_wta<4, 2, true, kMaxDirs, 4>), grid, block, 0, s, p);
-        }
-        return hipGetLastError();
-    }
-    switch (pass_lpl(p.L)) {
-#define WTA_CASE(LPL, PPW)                                                                  \
-    case LPL:                                                                               \
-        if (p.L == 64 * LPL && p.NDIR <= 4 && wide4) hipLaunchKernelGGL((k_wta<LPL, 2 * PPW, true, 4>), grid, block, 0, s, p); \
-        else if (p.L == 64 * LPL) hipLaunchKernelGGL((k_wta<LPL, PPW, true>), grid, block, 0, s, p);  \
-        else hipLaunchKernelGGL((k_wta<LPL, 1, false>), grid, block, 0, s, p);               \
-        break;
-        WTA_CASE(1, 4)
-        WTA_CASE(2, 4)
-        WTA_CASE(3, 2)
-        WTA_CASE(4, 3)
-        WTA_CASE(6, 1)
-        WTA_CASE(8, 1)
-#undef WTA_CASE
-        // 513..2048 labels: one pixel per wave and iteration, guarded loads
-        // (768 and 1024 labels exactly: the second pass-kernel build takes them since round 4, with compact costs)
-        case 12:
-            if (p.L == 768) hipLaunchKernelGGL((k_wta<12, 1, true>), grid, block, 0, s, p);
-            else hipLaunchKernelGGL((k_wta<12, 1, false>), grid, block, 0, s, p);
+    switch (c.family) {
+        case kWtaPruned:  // (LPL 4: 256 labels) pixels per wave, directions it is built for, exactly that many
+            if (!p.Lmin) break;
+            WTA_PRUNED(2, 8, 1) WTA_PRUNED(1, 8, 1) WTA_PRUNED(2, 4, 1) WTA_PRUNED(1, 4, 1) WTA_PRUNED(1, 4, 0) WTA_PRUNED(1, 8, 0)
             break;
-        case 16:
-            if (p.L == 1024) hipLaunchKernelGGL((k_wta<16, 1, true>), grid, block, 0, s, p);
-            else hipLaunchKernelGGL((k_wta<16, 1, false>), grid, block, 0, s, p);
+        case kWtaAny:  // beyond the widest k_wta instance
+            hipLaunchKernelGGL(k_wta_any, grid, block, 0, s, p);
+            return hipGetLastError();
+        case kWtaQuad:  // 192 / 384 labels
+            WTA_Q(3, 4) WTA_Q(3, 8) WTA_Q(6, 4) WTA_Q(6, 8)
             break;
-        case 24: hipLaunchKernelGGL((k_wta<24, 1, false>), grid, block, 0, s, p); break;
-        case 32: hipLaunchKernelGGL((k_wta<32, 1, false>), grid, block, 0, s, p); break;
-        default: return hipErrorInvalidValue;
+        case kWtaPacked:  // 128 and 64 labels: two / four pixels per 256-float slab
+            WTA(4, 4, 1, 4, 2) WTA(4, 2, 1, 8, 2) WTA(4, 4, 1, 4, 4) WTA(4, 2, 1, 8, 4)
+            break;
+        case kWtaPlain:  // per label width: at most 4 directions, up to 8, and the guarded instance of a stride with padding lanes
+            WTA(1, 8, 1, 4, 1) WTA(1, 4, 1, 8, 1) WTA(1, 1, 0, 8, 1)
+            WTA(2, 8, 1, 4, 1) WTA(2, 4, 1, 8, 1) WTA(2, 1, 0, 8, 1)
+            WTA(3, 4, 1, 4, 1) WTA(3, 2, 1, 8, 1) WTA(3, 1, 0, 8, 1)
+            WTA(4, 6, 1, 4, 1) WTA(4, 3, 1, 8, 1) WTA(4, 1, 0, 8, 1)
+            WTA(6, 2, 1, 4, 1) WTA(6, 1, 1, 8, 1) WTA(6, 1, 0, 8, 1)
+            WTA(8, 2, 1, 4, 1) WTA(8, 1, 1, 8, 1) WTA(8, 1, 0, 8, 1)
+            // 513..2048 labels: one pixel per wave and iteration, guarded loads
+            // (768 and 1024 labels exactly: the second pass-kernel build takes them since round 4, with compact costs)
+            WTA(12, 1, 1, 8, 1) WTA(12, 1, 0, 8, 1)
+            WTA(16, 1, 1, 8, 1) WTA(16, 1, 0, 8, 1)
+            WTA(24, 1, 0, 8, 1)
+            WTA(32, 1, 0, 8, 1)
+            break;
+        default: break;
     }
-    return hipGetLastError();
+#undef WTA
+#undef WTA_Q
+#undef WTA_PRUNED
+    return hipErrorInvalidValue;
 }
 
 // refine.h:40-68
@@ -930,19 +884,16 @@ hipError_t launch_rel_S(const WtaRelParams &p, int L, int dmin, float *S, hipStr
 }
 hipError_t launch_wta_rel(const WtaRelParams &p, hipStream_t s)
 {
-    const long long groups = (p.npix + 15) / 16;  // four waves of four pixels per block
-    const long long cap = (long long)p.num_cu * 64;
-    const dim3 grid((unsigned)std::max(1ll, std::min(groups, cap)));
-    if (p.slots == 128) {
-        if (p.cb == 4) hipLaunchKernelGGL((k_wta_rel<8, 4>), grid, dim3(256), 0, s, p);
-        else if (p.cb == 2) hipLaunchKernelGGL((k_wta_rel<8, 2>), grid, dim3(256), 0, s, p);
-        else hipLaunchKernelGGL((k_wta_rel<8, 1>), grid, dim3(256), 0, s, p);
-    } else {
-        if (p.cb == 4) hipLaunchKernelGGL((k_wta_rel<4, 4>), grid, dim3(256), 0, s, p);
-        else if (p.cb == 2) hipLaunchKernelGGL((k_wta_rel<4, 2>), grid, dim3(256), 0, s, p);
-        else hipLaunchKernelGGL((k_wta_rel<4, 1>), grid, dim3(256), 0, s, p);
+    const WtaRelChoice c = plan_wta_rel(WtaRelRequest{p.npix, p.num_cu, p.slots, p.cb});
+    const dim3 grid((unsigned)c.grid);
+#define WTA_REL(SPL_, CB_)                                                                \
+    if (c.SPL == SPL_ && c.CB == CB_) {                                                   \
+        hipLaunchKernelGGL((k_wta_rel<SPL_, CB_>), grid, dim3(256), 0, s, p);             \
+        return hipGetLastError();                                                         \
     }
-    return hipGetLastError();
+    WTA_REL(8, 4) WTA_REL(8, 2) WTA_REL(8, 1) WTA_REL(4, 4) WTA_REL(4, 2) WTA_REL(4, 1)
+#undef WTA_REL
+    return hipErrorInvalidValue;
 }
 
 // Stand-alone refinement on a materialised (corrected) S: one thread per pixel (subpixel_refinement_sgm,
@@ -982,91 +933,6 @@ hipError_t launch_refine(const float *S, long long npix, int L, int dmin, int me
     if (method < 1 || method > 4) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_refine, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, s, S, npix, L, dmin, method, wlo, whi, vout,
                        out, outcost);
-    return hipGetLastError();
-}
-
-// ---- update_dmin_dmax (mgm.cc:120-158) + the two remove_nonfinite_values_Img calls that follow it (387-388) ------
-// global finite minimum / maximum of the disparity map (image_minmax, img_tools.h:183-199): floats ordered
-// through their bit patterns so that integer atomics can reduce them
-__device__ __forceinline__ unsigned f2ord(float f)
-{
-    const unsigned u = __builtin_bit_cast(unsigned, f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float ord2f(unsigned o)
-{
-    return __builtin_bit_cast(float, (o & 0x80000000u) ? (o & 0x7fffffffu) : ~o);
-}
-__global__ void __launch_bounds__(256) k_minmax_init(unsigned *mm)
-{
-    mm[0] = f2ord(__builtin_huge_valf());   // gmin = +INF
-    mm[1] = f2ord(-__builtin_huge_valf());  // gmax = -INF
-}
-__global__ void __launch_bounds__(256) k_minmax(const float *__restrict__ u, long long n, unsigned *mm)
-{
-    float lo = __builtin_huge_valf(), hi = -__builtin_huge_valf();
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-        const float v = u[i];
-        if (finite_bits(v)) {
-            lo = v < lo ? v : lo;
-            hi = v > hi ? v : hi;
-        }
-    }
-    atomicMin(mm + 0, f2ord(lo));
-    atomicMax(mm + 1, f2ord(hi));
-}
-__global__ void __launch_bounds__(256) k_update_ranges(const float *__restrict__ outoff, int nx, int ny, int slack, int r,
-                                                       const unsigned *__restrict__ mm, float *__restrict__ dminI,
-                                                       float *__restrict__ dmaxI)
-{
-    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= (long long)nx * ny) return;
-    const int i = (int)(idx % nx), j = (int)(idx / nx);
-    const float gmin = ord2f(mm[0]), gmax = ord2f(mm[1]);
-    float dmin = __builtin_huge_valf(), dmax = -__builtin_huge_valf();
-    for (int dj = -r; dj <= r; dj++)
-        for (int di = -r; di <= r; di++) {
-            int x = i + di, y = j + dj;  // valneumann
-            x = x >= 0 ? x : 0;
-            x = x < nx ? x : nx - 1;
-            y = y >= 0 ? y : 0;
-            y = y < ny ? y : ny - 1;
-            const float v = outoff[x + (long long)y * nx];
-            const float a = finite_bits(v) ? v - slack : gmin - slack;
-            const float b = finite_bits(v) ? v + slack : gmax + slack;
-            dmin = __builtin_fminf(dmin, a);
-            dmax = __builtin_fmaxf(dmax, b);
-        }
-    float lo = dminI[idx], hi = dmaxI[idx];
-    if (finite_bits(dmin)) {
-        lo = dmin;
-        hi = dmax;
-    }
-    // remove_nonfinite_values_Img(dminI, gmin), (dmaxI, gmax)
-    dminI[idx] = finite_bits(lo) ? lo : gmin;
-    dmaxI[idx] = finite_bits(hi) ? hi : gmax;
-}
-
-// image_minmax alone: mm[0] / mm[1] receive the finite minimum / maximum of u as ordered bit patterns (+INF / -INF when
-// there is no finite sample); mgm_pyramid.hip reads them the same way
-hipError_t launch_minmax(const float *u, long long n, unsigned *mm, hipStream_t s)
-{
-    hipLaunchKernelGGL(k_minmax_init, dim3(1), dim3(1), 0, s, mm);
-    long long nb = (n + 255) / 256;
-    if (nb > 1024) nb = 1024;
-    hipLaunchKernelGGL(k_minmax, dim3((unsigned)nb), dim3(256), 0, s, u, n, mm);
-    return hipGetLastError();
-}
-
-hipError_t launch_update_ranges(const float *outoff, int nx, int ny, int slack, int radius, float *dminI, float *dmaxI,
-                                float *scratch2, hipStream_t s)
-{
-    unsigned *mm = reinterpret_cast<unsigned *>(scratch2);
-    const long long n = (long long)nx * ny;
-    if (slack < 0) slack = -slack;
-    if (hipError_t e = launch_minmax(outoff, n, mm, s)) return e;
-    hipLaunchKernelGGL(k_update_ranges, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, outoff, nx, ny, slack, radius, mm, dminI,
-                       dmaxI);
     return hipGetLastError();
 }
 
@@ -1252,50 +1118,26 @@ __global__ void __launch_bounds__(256) k_wta_right_any(const WtaRightParams P)
     }
 }
 
-hipError_t launch_wta_right(const WtaRightParams &p0, hipStream_t s)
+hipError_t launch_wta_right(const WtaRightParams &p0, const WtaRightChoice &c, hipStream_t s)
 {
-    WtaRightParams p = p0;
-    if (p.L < 1 || p.Lk < p.L || p.nx < 1 || p.ny < 1 || p.vnx < 1 || p.dmax - p.dmin + 1 != p.L) return hipErrorInvalidValue;
-    const int cus = p.num_cu > 0 ? p.num_cu : 256;
-    const int lpl = p.Lk % 64 == 0 ? p.Lk / 64 : 0;
-    // MGM_HIP_WTA_RIGHT_ANY=1 (read at every call: tests switch it inside one process): the diagonal walk everywhere
-    const char *ea = getenv("MGM_HIP_WTA_RIGHT_ANY");
-    const bool force_any = ea && atoi(ea) != 0;
-    const bool stream = !force_any && (lpl == 1 || lpl == 2 || lpl == 3 || lpl == 4 || lpl == 6 || lpl == 8 || lpl == 12 || lpl == 16);
-    if (!stream) {
-        long long nb = ((long long)p.vnx * p.ny + 3) / 4;
-        nb = std::min(nb, (long long)cus * 64);
-        hipLaunchKernelGGL(k_wta_right_any, dim3((unsigned)nb), dim3(256), 0, s, p);
+    const dim3 grid((unsigned)c.grid), block(256);
+    if (c.family == kRightDiagonal) {
+        hipLaunchKernelGGL(k_wta_right_any, grid, block, 0, s, p0);
         return hipGetLastError();
     }
-    // Segments of a row: a workgroup re-reads the L-1 left pixels ahead of its segment, so a row is split only as far as the
-    // device needs workgroups (about four per compute unit), and never below max(64, L) right pixels.
-    static int seg_tune = -1;  // MGM_HIP_TUNE=wta_right_seg=<right pixels per workgroup> (A/B timing)
-    if (seg_tune < 0) seg_tune = (int)tune_num("wta_right_seg", 0);
-    const int want = (4 * cus + p.ny - 1) / p.ny;  // segments per row
-    int seg = (p.vnx + want - 1) / want;
-    seg = std::max(seg, std::max(64, p.L));
-    if (seg_tune > 0) seg = seg_tune;
-    p.seg = std::min(seg, p.vnx);
-    const long long nb = (long long)p.ny * ((p.vnx + p.seg - 1) / p.seg);
-    if (nb > 0x7fffffffll) return hipErrorInvalidValue;
-    const int ppw = lpl <= 4 ? 2 : 1;
-    int ring = 64;
-    while (ring < p.L - 1 + 2 * 4 * ppw) ring *= 2;
-    p.ring = ring;
-    const dim3 grid((unsigned)nb), block(256);
-    const size_t lds = sizeof(unsigned long long) * (size_t)ring;
-    switch (lpl) {
-        case 1: hipLaunchKernelGGL((k_wta_right<1, 2>), grid, block, lds, s, p); break;
-        case 2: hipLaunchKernelGGL((k_wta_right<2, 2>), grid, block, lds, s, p); break;
-        case 3: hipLaunchKernelGGL((k_wta_right<3, 2>), grid, block, lds, s, p); break;
-        case 4: hipLaunchKernelGGL((k_wta_right<4, 2>), grid, block, lds, s, p); break;
-        case 6: hipLaunchKernelGGL((k_wta_right<6, 1>), grid, block, lds, s, p); break;
-        case 8: hipLaunchKernelGGL((k_wta_right<8, 1>), grid, block, lds, s, p); break;
-        case 12: hipLaunchKernelGGL((k_wta_right<12, 1>), grid, block, lds, s, p); break;
-        default: hipLaunchKernelGGL((k_wta_right<16, 1>), grid, block, lds, s, p); break;
+    if (c.family != kRightStream) return hipErrorInvalidValue;
+    WtaRightParams p = p0;
+    p.seg = c.seg;
+    p.ring = c.ring;
+    const size_t lds = sizeof(unsigned long long) * (size_t)c.ring;
+#define WTA_RIGHT(LPL_, PPW_)                                                             \
+    if (c.LPL == LPL_ && c.PPW == PPW_) {                                                 \
+        hipLaunchKernelGGL((k_wta_right<LPL_, PPW_>), grid, block, lds, s, p);            \
+        return hipGetLastError();                                                         \
     }
-    return hipGetLastError();
+    WTA_RIGHT(1, 2) WTA_RIGHT(2, 2) WTA_RIGHT(3, 2) WTA_RIGHT(4, 2) WTA_RIGHT(6, 1) WTA_RIGHT(8, 1) WTA_RIGHT(12, 1) WTA_RIGHT(16, 1)
+#undef WTA_RIGHT
+    return hipErrorInvalidValue;
 }
 
 }  // namespace mgm
