@@ -60,6 +60,100 @@ static int check_aggregate_args(mgm_ctx *c, int n, const mgm_cv *const *C, const
     return MGM_OK;
 }
 
+// mgm_ctx_set_placement_tries: the Lr workspace has just been (re)allocated by `launch` -- time that very launch on a few physical
+// placements and keep the fastest (the launch is idempotent: same inputs, same Lr volumes, whichever allocation).  `r`: the
+// launch's result; returns what the last launch on the kept workspace gave.  *stop: an error ends the call here (no halving).
+static int place_workspace(mgm_ctx *c, int r, const std::function<int()> &launch, bool *stop)
+{
+    *stop = false;
+    if (!(r == MGM_OK && c->place_tries >= 2 && c->lr.p && (c->lr.p != c->placed_ptr || c->lr.cap != c->placed_cap) && c->lr.cap >= (1ull << 28))) return r;
+    *stop = true;
+    auto timed = [&](float *ms) -> int {
+        struct Ev {  // (destroyed on every exit path)
+            hipEvent_t e = nullptr;
+            ~Ev() { if (e) (void)hipEventDestroy(e); }
+        } a, b;
+        HIPCHK(c, hipEventCreate(&a.e));
+        HIPCHK(c, hipEventCreate(&b.e));
+        HIPCHK(c, hipEventRecord(a.e, c->stream));
+        int rr = launch();
+        if (rr == MGM_OK) {
+            HIPCHK(c, hipEventRecord(b.e, c->stream));
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            HIPCHK(c, hipEventElapsedTime(ms, a.e, b.e));
+        }
+        return rr;
+    };
+    float best = 0;
+    if ((r = timed(&best))) return r;  // (the first run, the caller's, was the warm-up)
+    struct Held {  // the allocations that are only held so that the next try lands elsewhere: freed on every exit path
+        std::vector<Buf> v;
+        void release() { for (Buf &h : v) if (h.p) (void)hipFree(h.p); v.clear(); }
+        ~Held() { release(); }
+        void push_back(const Buf &b) { v.push_back(b); }
+    } held;
+    for (int t = 1; t < c->place_tries && r == MGM_OK; t++) {
+        size_t fr = 0, tot = 0;
+        if (hipMemGetInfo(&fr, &tot) != hipSuccess || fr < c->lr.cap + (1ull << 30)) break;  // no room for a second workspace
+        Buf old = c->lr;
+        c->lr = Buf{};
+        float ms = 0;
+        int rr = launch();  // allocates; warm-up
+        if (rr == MGM_OK) rr = timed(&ms);
+        if (rr != MGM_OK) {  // (out of memory after all: back to what we had)
+            if (c->lr.p) (void)hipFree(c->lr.p);
+            c->lr = old;
+            (void)hipGetLastError();
+            c->err.clear();
+            r = launch();
+            break;
+        }
+        if (tune_num("show_plan", 0)) fprintf(stderr, "[mgm place] try %d: %.3f ms (best so far %.3f)\n", t, ms, best);
+        if (ms < best * 0.985f) {  // the new placement is the faster one: the old allocation is only held (so that the next try lands elsewhere)
+            held.push_back(old);
+            best = ms;
+        } else {  // keep the old one: hold the new one instead, and run the launch on the old workspace again (its Lr volumes are what k_wta reads)
+            held.push_back(c->lr);
+            c->lr = old;
+            r = launch();
+        }
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    held.release();
+    c->placed_ptr = c->lr.p;
+    c->placed_cap = c->lr.cap;
+    *stop = false;
+    return r;
+}
+
+// Range-proportional kernels or dense hull: plan_agg_route (mgm_planner.h) asks for the facts it needs, one at a time.
+static int resolve_route(mgm_ctx *c, int n, const mgm_cv *const *C, const mgm_img *const *w8, float P1, float P2, int MGM, int use_fh, bool want_S,
+                         RouteDecision *out)
+{
+    RouteRequest q{};
+    q.n = n, q.MGM = MGM, q.fh = use_fh > 0, q.want_S = want_S, q.weights_given = w8 && w8[0];
+    q.p1_nonneg = P1 >= 0.0f, q.p2_nonneg = P2 >= 0.0f, q.p2_finite = P2 < __builtin_huge_valf();
+    q.only_rel = 1;
+    for (int v = 0; v < n; v++) q.only_rel = q.only_rel && C[v]->rel_only;
+    q.rel_enabled = rel_enabled(), q.sw_rel = (int)tune_num("rel", 1), q.sw_rel_tie = (int)tune_num("rel_tie", 1);
+    q.sw_rel_S = (int)tune_num("rel_S", 1), q.sw_rel_fh2 = (int)tune_num("rel_fh2", 1);
+    q.w_odd = q.w_any = -1;
+    for (int v = 0; v < kMaxBatch; v++) q.rel_usable[v] = q.rel_slots[v] = q.rel_cb[v] = -1;
+    for (;;) {
+        const RouteDecision d = *out = plan_agg_route(q);
+        if (d.need == kNeedNothing) return MGM_OK;
+        int r;
+        bool odd = false, any = false, u = false;
+        if (d.need == kNeedWeightValues) {
+            if ((r = weights_have_odd_values(c, w8, n, (long long)C[0]->nx * C[0]->ny, &odd, &any))) return r;
+            q.w_odd = odd, q.w_any = any;
+        } else {  // kNeedRelCopy
+            if ((r = rel_resolve(c, C[d.arg], &u))) return r;
+            q.rel_usable[d.arg] = u, q.rel_slots[d.arg] = C[d.arg]->rel_slots, q.rel_cb[d.arg] = C[d.arg]->rel_cb;
+        }
+    }
+}
+
 // The aggregation itself, now: one pass launch over the batch (several if it does not fit), then the winner search per volume.
 static int aggregate_batch_now(mgm_ctx *c, int n, const mgm_cv *const *C, const mgm_img *const *w8, float P1, float P2, int NDIR,
                                int MGM, int use_fh, int fix_overcount, const char *refine, mgm_img *const *out,
@@ -74,156 +168,49 @@ static int aggregate_batch_now(mgm_ctx *c, int n, const mgm_cv *const *C, const 
         for (int v = 0; v < n; v++) S[v] = nullptr;
     c->wta_stats_n = 0;  // (mgm_debug_wta_stats: the pruned searches of THIS call)
     // Ragged volumes whose range-proportional copies are usable take the kernels that walk the pixels' own windows
-    // (mgm_pass_rel.hip): not when S is wanted (a dense volume), with TSGM = 2 (unweighted: other update functions), with
-    // P2 = +INF (all-INF slabs: the operand-order-faithful kernel).
+    // (mgm_pass_rel.hip): not with P2 = +INF (all-INF slabs: the operand-order-faithful kernel), negative penalties or odd weights
+    // (plan_agg_route, mgm_planner.h).
     // Measured (round 5, 1920x1080, windows of 49 labels in a hull of 256, K3 + search): FH 21.3 + 3.9 ms on the hull (the general
     // weighted kernels: the min-convolution runs over the RECEIVING pixel's range) -> 14.0 + 1.5 ms; free-form weights,
     // Hirschmueller: 11.4 + 3.9 -> 7.1 + 1.5; unit weights, Hirschmueller: 4.75 + 3.9 on the hull's queue kernels against
-    // 7.1 + 1.5 + 0.45 (gather) -- a tie, and those keep the hull (MGM_HIP_TUNE=rel=2 sends them here too).
-    // (round 5, later: unit-weight Hirschmueller volumes publish E on the producer side there, k_pass_rel PUBE: one volume 7.5 + 1.5 +
-    // 0.45 ms against 4.6 + 3.9 -- still a tie --, two 10.5 + 2.9 + 0.9 against 9.2 + 7.7, four 16.0 + 5.9 + 1.7 against 15.2 + 14.8:
-    // batches of them go)
-    // (round 5, last: four scan lines per wave -- two volumes 9.3 + 3.0, four 10.5 + 5.9 --, and census volumes whose ONLY copy is the
-    // range-proportional one: the hull would first have to be expanded and encoded again, 2.2 ms, so those go too: 8.1 + 1.5)
-    bool only_rel = true;
-    for (int v = 0; v < n; v++) only_rel = only_rel && C[v]->rel_only;
-    // (round 6: with slope 1, two strips and the 5.6 ms launch the tie is gone -- one unit-weight Hirschmueller volume that HAS its hull,
-    // 1920x1080, windows of 49 labels: 5.3 + 3.7 ms on the hull's queue kernels against 5.6 + 0.8 here, the gather paid either way:
-    // every usable copy is walked; tune rel_tie=0 restores round 5's rule)
-    const bool rel_pays = use_fh > 0 || (w8 && w8[0]) || n >= 2 || only_rel || tune_num("rel", 1) >= 2 || tune_num("rel_tie", 1) != 0;
-    //  the hand-off of k_pass_rel keeps the launch's tag in the sign bit of every published word, so every L / E / minimum
-    // must be >= +0: non-negative penalties (the dense path's own gate, run_passes `first_build`) and, for weighted launches,
-    // positive finite weights (a negative or NaN weight makes N + P1 D - m negative or NaN): those take the dense kernels.
-    // (round 6) TSGM = 2: with weights it is update_costW[_trunclinear] like every other TSGM; without -- weight images of ones
-    // count as none, mgm_core.cc:420-423 -- Hirschmueller is update_cost2 (built: PUBE with halved terms), FH is
-    // update_cost2_trunclinear with its boundary fix-up (not built here: the dense hull has it).
-    bool rel_sign_ok = P1 >= 0.0f && P2 >= 0.0f;
-    bool rel_weighted = w8 && w8[0];
-    // (round 6, last: S wanted is no reason for the hull any more -- k_rel_S expands the corrected sum from the range-proportional Lr volumes)
-    const bool rel_candidate = (!S || tune_num("rel_S", 1) != 0) && P2 < __builtin_huge_valf() && rel_pays && rel_sign_ok && rel_enabled();
-    if (rel_candidate && rel_weighted) {
-        bool odd = false, any = false;
-        if ((r = weights_have_odd_values(c, w8, n, npix, &odd, &any))) return r;
-        rel_sign_ok = !odd;
-        if (MGM == 2 && !any) rel_weighted = false;  // planes of ones: the reference runs unweighted
-    }
-    const bool rel_fn_ok = MGM != 2 || rel_weighted || use_fh <= 0 || tune_num("rel_fh2", 1) != 0;  // (round 6, last: update_cost2_trunclinear is built too, k_pass_rel FH2)
-    if (rel_candidate && rel_sign_ok && rel_fn_ok) {
-        bool all = true;
-        for (int v = 0; v < n && all; v++) {
-            bool u = false;
-            if ((r = rel_resolve(c, C[v], &u))) return r;
-            all = u && C[v]->rel_slots == C[0]->rel_slots && C[v]->rel_cb == C[0]->rel_cb;  // (one format per launch)
-        }
-        // the one combination whose LDS rings do not fit a CU: update_cost2_trunclinear ([L][F][B] entries) on 128 slots of fp32 costs
-        // (116 KB of rings + 64 KB of cost pieces): the dense hull keeps it
-        if (all && use_fh > 0 && MGM == 2 && !rel_weighted && C[0]->rel_slots == 128 && C[0]->rel_cb == 4) all = false;
-        if (all) {
-            //  the range-proportional launch honours the workspace limit too, and a batch the device cannot hold is run
-            // in halves instead of failing: NDIR x npix x slots floats per volume (+ ~16 % of hand-off slots: two lines per band on the anti-diagonal passes)
-            int chunk = n;
-            const double per_vol = 4.0 * ((double)npix * C[0]->rel_slots + (double)lr_pad_floats()) * NDIR * 1.16;
-            if (c->ws_limit)
-                while (chunk > 1 && per_vol * chunk > (double)c->ws_limit) chunk--;
-            for (int v0 = 0; v0 < n;) {
-                const int m = std::min(chunk, n - v0);
-                r = run_rel(c, C + v0, rel_weighted ? w8 + v0 : nullptr, m, P1, P2, MGM, use_fh, NDIR, fix_overcount, ridx, out + v0, outcost + v0, S ? S + v0 : nullptr);
-                if (r == MGM_ERR_NOMEM && m > 1) {
-                    chunk = std::max(1, m / 2);
-                    (void)hipGetLastError();
-                    c->err.clear();
-                    continue;
-                }
-                if (r) return r;
-                v0 += m;
-            }
-            return MGM_OK;
-        }
-    }
-    // The Lr volumes of a launch take NDIR x W x H x L floats per volume.  A batch that does not fit the caller's
-    // workspace limit (mgm_ctx_set_workspace_limit), or the device (hipMalloc fails), is run as several launches over
-    // the largest sub-batches that do -- multiples of four / two volumes first, so that volumes keep sharing waves at
-    // 64 / 128 labels -- instead of failing with MGM_ERR_NOMEM: same results, the later volumes just wait their turn.
-    int chunk = n;
-    // what the winner search behind the launch will be: run_passes decides with it whether the launch writes the chunk minima
+    // 7.1 + 1.5 + 0.45 (gather) -- a tie then; round 6 (slope 1, two strips): 5.3 + 3.7 ms against 5.6 + 0.8, the gather paid either
+    // way: every usable copy is walked.  Census volumes whose ONLY copy is the range-proportional one would first have to be expanded
+    // and encoded again for the hull, 2.2 ms.
+    RouteDecision route;
+    if ((r = resolve_route(c, n, C, w8, P1, P2, MGM, use_fh, S != nullptr, &route))) return r;
+    const bool rel = route.route == kRouteRel;
+    // what the winner search behind a dense launch will be: run_passes decides with it whether the launch writes the chunk minima
     // the pruned search reads (mgm_planner.h, plan_wta_prune)
     const bool search_S = S != nullptr;
-    if (c->ws_limit) {
-        const int Lk = padded_labels(L) ? padded_labels(L) : L;
-        // (+ the hand-off slots: ~7 %; + the chunk minima where a launch may write them: one float per 32 of Lr)
-        const double per_vol = 4.0 * ((double)npix * Lk + (double)lr_pad_floats()) * NDIR * (1.07 + ((L == 256 && !S && ridx <= 1 && wta_prune_enabled()) ? 1.0 / kChunkLabels : 0.0));
-        while (chunk > 1 && per_vol * chunk > (double)c->ws_limit) chunk--;
-        if (chunk >= 4) chunk -= chunk % 4;
-        else if (chunk == 3) chunk = 2;
-    }
+    // the passes of the volumes [v0, v0 + m) -- and, on the range-proportional route, their winner search
+    auto launch = [&](int v0, int m) -> int {
+        if (rel) return run_rel(c, C + v0, route.rel_weighted ? w8 + v0 : nullptr, m, P1, P2, MGM, use_fh, NDIR, fix_overcount, ridx, out + v0, outcost + v0, S ? S + v0 : nullptr);
+        return run_passes(c, C + v0, (w8 && w8[0]) ? w8 + v0 : nullptr, m, P1, P2, MGM, use_fh, 0, NDIR, /*allow_pad=*/true, 0, 0, 0, ridx, search_S);
+    };
+    // The sub-batches (plan_subbatch): what fits the workspace limit, halved when the device cannot hold it either -- same results,
+    // the later volumes just wait their turn.
+    SubbatchRequest sq{};
+    sq.npix = npix, sq.ws_limit = (long long)c->ws_limit, sq.lr_pad = lr_pad_floats(), sq.route = route.route, sq.n = n, sq.NDIR = NDIR, sq.L = L;
+    sq.rel_slots = C[0]->rel_slots, sq.want_S = S != nullptr, sq.refine = ridx, sq.prune_enabled = wta_prune_enabled();
+    int chunk = plan_subbatch(sq);
     for (int v0 = 0; v0 < n && !r;) {
-        int m = std::min(chunk, n - v0);
-        r = run_passes(c, C + v0, (w8 && w8[0]) ? w8 + v0 : nullptr, m, P1, P2, MGM, use_fh, 0, NDIR, /*allow_pad=*/true, 0, 0, 0, ridx, search_S);
-        // mgm_ctx_set_placement_tries: the workspace has just been (re)allocated -- time this very launch on a few physical
-        // placements and keep the fastest (the launch is idempotent: same inputs, same Lr volumes, whichever allocation)
-        if (r == MGM_OK && c->place_tries >= 2 && c->lr.p && (c->lr.p != c->placed_ptr || c->lr.cap != c->placed_cap) && c->lr.cap >= (1ull << 28)) {
-            auto timed = [&](float *ms) -> int {
-                struct Ev {  // (destroyed on every exit path)
-                    hipEvent_t e = nullptr;
-                    ~Ev() { if (e) (void)hipEventDestroy(e); }
-                } a, b;
-                HIPCHK(c, hipEventCreate(&a.e));
-                HIPCHK(c, hipEventCreate(&b.e));
-                HIPCHK(c, hipEventRecord(a.e, c->stream));
-                int rr = run_passes(c, C + v0, (w8 && w8[0]) ? w8 + v0 : nullptr, m, P1, P2, MGM, use_fh, 0, NDIR, true, 0, 0, 0, ridx, search_S);
-                if (rr == MGM_OK) {
-                    HIPCHK(c, hipEventRecord(b.e, c->stream));
-                    HIPCHK(c, hipStreamSynchronize(c->stream));
-                    HIPCHK(c, hipEventElapsedTime(ms, a.e, b.e));
-                }
-                return rr;
-            };
-            float best = 0;
-            if ((r = timed(&best))) break;  // (the first run above was the warm-up)
-            struct Held {  // the allocations that are only held so that the next try lands elsewhere: freed on every exit path
-                std::vector<Buf> v;
-                void release() { for (Buf &h : v) if (h.p) (void)hipFree(h.p); v.clear(); }
-                ~Held() { release(); }
-                void push_back(const Buf &b) { v.push_back(b); }
-            } held;
-            for (int t = 1; t < c->place_tries && r == MGM_OK; t++) {
-                size_t fr = 0, tot = 0;
-                if (hipMemGetInfo(&fr, &tot) != hipSuccess || fr < c->lr.cap + (1ull << 30)) break;  // no room for a second workspace
-                Buf old = c->lr;
-                c->lr = Buf{};
-                float ms = 0;
-                int rr = run_passes(c, C + v0, (w8 && w8[0]) ? w8 + v0 : nullptr, m, P1, P2, MGM, use_fh, 0, NDIR, true, 0, 0, 0, ridx, search_S);  // allocates; warm-up
-                if (rr == MGM_OK) rr = timed(&ms);
-                if (rr != MGM_OK) {  // (out of memory after all: back to what we had)
-                    if (c->lr.p) (void)hipFree(c->lr.p);
-                    c->lr = old;
-                    (void)hipGetLastError();
-                    c->err.clear();
-                    r = run_passes(c, C + v0, (w8 && w8[0]) ? w8 + v0 : nullptr, m, P1, P2, MGM, use_fh, 0, NDIR, true, 0, 0, 0, ridx, search_S);
-                    break;
-                }
-                if (tune_num("show_plan", 0)) fprintf(stderr, "[mgm place] try %d: %.3f ms (best so far %.3f)\n", t, ms, best);
-                if (ms < best * 0.985f) {  // the new placement is the faster one: the old allocation is only held (so that the next try lands elsewhere)
-                    held.push_back(old);
-                    best = ms;
-                } else {  // keep the old one: hold the new one instead, and run the launch on the old workspace again (its Lr volumes are what k_wta reads)
-                    held.push_back(c->lr);
-                    c->lr = old;
-                    r = run_passes(c, C + v0, (w8 && w8[0]) ? w8 + v0 : nullptr, m, P1, P2, MGM, use_fh, 0, NDIR, true, 0, 0, 0, ridx, search_S);
-                }
-            }
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-            held.release();
-            c->placed_ptr = c->lr.p;
-            c->placed_cap = c->lr.cap;
+        const int m = std::min(chunk, n - v0);
+        r = launch(v0, m);
+        if (!rel) {
+            bool stop = false;
+            r = place_workspace(c, r, [&] { return launch(v0, m); }, &stop);
+            if (stop) break;
         }
         if (r == MGM_ERR_NOMEM && m > 1) {  // does not fit the device either: halve and try again
-            chunk = m > 4 ? (m / 2) - (m / 2) % 2 : m / 2;
-            chunk = std::max(chunk, 1);
+            chunk = shrink_after_nomem(route.route, m);
+            if (rel) {
+                (void)hipGetLastError();
+                c->err.clear();
+            }
             r = MGM_OK;
             continue;
         }
-        for (int v = 0; v < m && !r; v++) {
+        for (int v = 0; v < m && !r && !rel; v++) {  // (the dense route's search; run_rel has done its own)
             float *Sout = nullptr;
             if (S) {
                 if ((r = mgm_cv_create(c, nx, ny, C[v0 + v]->dmin, C[v0 + v]->dmax, &S[v0 + v]))) break;
@@ -234,7 +221,7 @@ static int aggregate_batch_now(mgm_ctx *c, int n, const mgm_cv *const *C, const 
         }
         v0 += m;
     }
-    if (r && S) {  // no S volume of a failed call is handed out
+    if (r && S && !rel) {  // no S volume of a failed dense call is handed out (run_rel leaves what it made)
         const std::string msg = c->err;
         for (int v = 0; v < n; v++) {
             if (S[v]) mgm_cv_free(c, S[v]);

@@ -297,7 +297,7 @@ __device__ __forceinline__ void combine_w2(const float (&C)[LPL], const Nb<LPL, 
 // land, and a step that is shorter than the memory latency (~0.8 us under load) waits for it: measured (round 3, same
 // box, shallow -> deep) 4096x4096x192 x 1: K3 32.5 -> 27.7 ms; 1920x1080x128 x 1: 2.69 -> 2.34; 256 labels x 1: 5.71 -> 5.50
 // (Hirschmueller), 7.23 -> 7.03 (FH); x 2: 11.24 -> 10.95; eight / sixteen 128-label volumes 9.11 -> 8.69 / 16.6 -> 15.9;
-// twelve 256-label volumes 48.5 -> 48.2.  The default of every compact unweighted launch (mgm_api.hip, run_passes); the
+// twelve 256-label volumes 48.5 -> 48.2.  The default of every compact unweighted launch (mgm_plan.hip, run_passes); the
 // shallow build stays for A/B runs (MGM_HIP_DEEP=0).
 // where the work-item word lives in the workgroup's LDS (the layout of pass2_item, below)
 template <int LPL, bool FH, bool WEIGHTED, int MGM, int C8, bool DEEP, bool W2 = false>
@@ -1066,7 +1066,7 @@ __device__ __forceinline__ void pass2_item(const PassParams &P, const int ticket
 }
 
 // The kernel: one work item per workgroup, taken by ticket -- or, XCDQ, the work items of the XCD the workgroup finds
-// itself on.  XCDQ (launches in which the chains of bands matter; mgm_api.hip, run_passes): the host deals the bands of
+// itself on.  XCDQ (launches in which the chains of bands matter; mgm_plan.hip, run_passes): the host deals the bands of
 // every pass in blocks of consecutive bands -- or whole passes -- to eight queues, one per XCD; a workgroup reads its XCC id at run time and
 // works through THAT queue, one item after the other, until it is empty.  A band whose successor sits in the same queue
 // hands its slabs over with PLAIN stores: they stay in the XCD's L2, where the successor's L2-served (sc1) loads find

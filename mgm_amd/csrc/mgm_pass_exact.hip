@@ -3,7 +3,7 @@
 // `a < b ? a : b` (mgm_core.cc:48), fmin3 by two strict `>` tests (54-60), Dvec::get_minvalue by a strict `<` scan in
 // label order (dvec.cc:81-88) -- and compiled WITHOUT -fno-honor-nans, so that a NaN operand gives what it gives in the
 // reference: which operand holds the NaN decides the result, something v_min_f32 and the fused DPP scans of the fast
-// builds do not reproduce.  Taken only for the volumes that can produce NaNs (mgm_api.hip, run_passes):
+// builds do not reproduce.  Taken only for the volumes that can produce NaNs (mgm_plan.hip, run_passes):
 //   * an uploaded volume that holds NaN costs;
 //   * a volume built by `-p census` with a non-census distance from descriptors of more than 24 bits: the costs are
 //     differences of descriptor WORDS read as floats (mgm_costvolume.h:355-362), NaN patterns included;

@@ -281,18 +281,12 @@ static int run_passes_exact(mgm_ctx *c, const mgm_cv *const *Cs, const mgm_img *
 
 // ---- K3 on the dense layout --------------------------------------------------------------------------------------------------
 // Stage 1 of a dense launch: what the volumes and weights of the call ARE, found out on the device -- the weights' values,
-// NaN costs, the compact and padded forms of the costs -- and with that, which kernels can take them.
-struct DenseOperands {
-    bool exact = false;        // the slow operand-order-faithful kernel takes the call (run_passes_exact)
-    bool first_build = false;  // the first build only
-    int Lreal = 0, L = 0;      // labels of the volumes; label slots the kernels see (padded launch: the next count of the second build)
-    bool padded = false, own_padded = false;  // ... padded; every volume carries the padded compact copy K2 wrote (mgm_cv::p8)
-    bool use_c8 = true;        // compact costs ...
-    int cb = 1;                // ... of this many bytes
-    bool weighted = false, weighted_given = false;  // the weighted kernels run; the caller's weights hold a value != 1
-    bool w2cand = false;       // every weighted volume's weights are 1 and ONE other positive finite value
-    float w2a[kMaxBatch] = {};  // ... that value
-    bool ragged = false, fh2_ragged = false;
+// NaN costs, the compact and padded forms of the costs -- and with that, which kernels can take them: the decision is
+// plan_dense_kernels' (mgm_planner.h), which asks for those facts one at a time; what is left here is probing and materialising.
+static_assert(kFastKernelLabels == kMaxLPL * 64, "plan_dense_kernels: the widest fast pass kernel");
+struct DenseOperands : DenseKernels {
+    int Lreal = 0;              // labels of the volumes
+    float w2a[kMaxBatch] = {};  // two-valued weights: the other value
     const float *ones8 = nullptr;  // all-ones weights of a ragged FH launch without weights (it borrows the weighted kernels)
 };
 
@@ -308,159 +302,84 @@ static int pad_f32(mgm_ctx *c, const mgm_cv *const *Cs, int nb, long long npix, 
     return MGM_OK;
 }
 
+// padded copies of the costs of all volumes as compact costs of `tb` bytes (mgm_ctx::pad8): *fits = every cost has a code
+static int try_pad(mgm_ctx *c, const mgm_cv *const *Cs, int nb, long long npix, int Lreal, int L, int tb, int *fits)
+{
+    unsigned *words = (unsigned *)c->words.p;
+    int r;
+    HIPCHK(c, hipMemsetAsync(words + 3, 0, sizeof(unsigned), c->stream));
+    for (int v = 0; v < nb; v++) {
+        if ((r = ensure_f32(c, Cs[v]))) return r;
+        if ((r = reserve(c, c->pad8[v], (size_t)npix * L * tb))) return r;
+        TimeScope ts(c, "k_pad");
+        HIPCHK(c, launch_pad(Cs[v]->d, npix, Lreal, L, nullptr, (uint8_t *)c->pad8[v].p, tb, words + 3, c->stream));
+    }
+    HIPCHK(c, hipMemcpyAsync(c->h_words + 3, words + 3, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    *fits = c->h_words[3] == 0;
+    return MGM_OK;
+}
+
+static int dense_error(mgm_ctx *c, int err)
+{
+    if (err == kDenseMixedWeights) return fail(c, MGM_ERR_UNSUPPORTED, "batched volumes must be all weighted or all unweighted");
+    if (err == kDenseRaggedHulls) return fail(c, MGM_ERR_UNSUPPORTED, "batched ragged volumes must share their hull under FH potentials");
+    return fail(c, MGM_ERR_UNSUPPORTED, "FH potentials with TSGM=2 and no weights on a ragged cost volume need the second build");
+}
+
 static int resolve_dense_operands(mgm_ctx *c, const mgm_cv *const *Cs, const mgm_img *const *w8s, int nb, float P1, float P2, int MGM, bool fh, bool allow_pad,
                                   DenseOperands &o)
 {
-    const mgm_cv *C = Cs[0];
-    const int nx = C->nx, ny = C->ny, Lreal = o.Lreal = C->dmax - C->dmin + 1;
-    unsigned *words = (unsigned *)c->words.p;
+    const int Lreal = o.Lreal = Cs[0]->dmax - Cs[0]->dmin + 1, LP = padded_labels(Lreal);
+    const long long npix = (long long)Cs[0]->nx * Cs[0]->ny;
     int r;
-    // The second build's unweighted kernels keep the sign bit of the slabs they hand from band to band for a validity
-    // tag, which needs E = T - m >= +0, i.e. non-negative penalties (mgm_pass2.hip, TAGS): anything else takes the first build.
-    const bool first_build = o.first_build = c->force_build == 1 || !(P1 >= 0.0f) || !(P2 >= 0.0f);
-
-    // A label count the second build does not take (not 64, 128, 192, 256, 384 or 512) runs PADDED: the kernels see
-    // the next such count, the extra label slots hold +INF costs -- "no such label", exactly what a read past a Dvec
-    // returns (dvec.cc:129) -- and stay +INF through every update: C = +INF there and every pixel of a volume with a
-    // uniform range has a finite minimum, so the added term is finite.
-    int L = Lreal;
-    bool padded = false;
-    // (weights with more than 512 labels run on the first build, which takes any label count as it is: no padding then)
-    if (allow_pad && !first_build && pass2_lines(Lreal, false) == 0 && dev().pad && !(w8s && w8s[0] && Lreal > 512)) {
-        const int lp = padded_labels(Lreal);
-        if (lp) {
-            L = lp;
-            padded = true;
-        }
+    // the request: what is known without the device ...
+    DenseKernelsRequest q{};
+    q.nb = nb, q.MGM = MGM, q.fh = fh, q.allow_pad = allow_pad, q.Lreal = Lreal;
+    q.p1_nonneg = P1 >= 0.0f, q.p2_nonneg = P2 >= 0.0f, q.p2_finite = P2 < __builtin_huge_valf();
+    q.force_build = c->force_build, q.lines_real = pass2_lines(Lreal, false), q.lines_pad = LP ? pass2_lines(LP, false) : 0;
+    q.lpl_real = pass_lpl(Lreal), q.lpl_pad = LP ? pass_lpl(LP) : 0;
+    q.sw_pad = dev().pad, q.sw_c8 = dev().c8, q.sw_deep = dev().deep;
+    q.weights_given = w8s && w8s[0], q.same_hull = 1, q.pad_hint = Cs[0]->pad_hint;
+    for (int v = 0; v < nb; v++) {
+        q.w_given[v] = w8s && w8s[v];
+        q.ragged |= Cs[v]->rlo != nullptr, q.nan_words |= Cs[v]->nan_words, q.same_hull &= Cs[v]->dmin == Cs[0]->dmin;
+        q.p8_valid[v] = Cs[v]->p8_state == CopyState::Valid, q.p8_L[v] = Cs[v]->p8_L, q.p8_cb[v] = Cs[v]->p8_cb;
     }
-    o.L = L, o.padded = padded;
-    const long long npix = (long long)nx * ny;
-    const int lpl = pass_lpl(L);
-
-    // weighted? (mgm_core.cc:420-423: any value != 1.0 switches every update) -- and what values do the weights take: the
-    // planes compute_mgm_weights makes hold 1 and ONE other value, which the pass kernel exploits (k_pass2, W2)
-    bool weighted = false, w2cand = false, wodd = false;  // wodd: a weight that is not positive and finite (<= 0, NaN, INF)
-    if (w8s && w8s[0]) {
-        unsigned got[4 * kMaxBatch];
-        if ((r = scan_weights(c, w8s, nb, npix, got))) return r;
-        w2cand = true;
-        for (int v = 0; v < nb; v++) {
-            const bool wv = w8s[v] && got[4 * v] != 0;
-            // Planes of ones beside real weights: with TSGM != 2 the reference calls the SAME update function either way
-            // (update_costW[_trunclinear] with DeltaI = 1.0, mgm_core.cc:563-575), so the launch simply runs weighted; with
-            // TSGM = 2 the unweighted volume is update_cost2's, a different function: not in one launch.
-            if (v && wv != weighted && (MGM == 2 || !w8s[v]))
-                return fail(c, MGM_ERR_UNSUPPORTED, "batched volumes must be all weighted or all unweighted");
-            weighted = weighted || wv;
-            wodd = wodd || (wv && got[4 * v + 3] != 0);
-            w2cand = w2cand && (!wv || (got[4 * v + 3] == 0 && got[4 * v + 1] == got[4 * v + 2]));
-            if (wv) memcpy(&o.w2a[v], &got[4 * v + 1], 4);
-            else o.w2a[v] = 1.0f;  // (planes of ones in a weighted launch: no selector bit is set, the other value is never used)
-        }
-        w2cand = w2cand && weighted;
+    // ... and what is not: -1 until the planner has asked for it
+    for (int v = 0; v < kMaxBatch; v++) q.w_not_one[v] = q.w_odd[v] = q.w_one_other[v] = q.c8_use[v] = q.c8_bytes[v] = q.nan_found[v] = -1;
+    q.pad_fits[0] = q.pad_fits[1] = q.pad_fits[2] = -1;
+    DenseKernels d;
+    while ((d = plan_dense_kernels(q)).need != kNeedNothing) {
+        if (d.need == kNeedWeightValues) {
+            unsigned got[4 * kMaxBatch];
+            if ((r = scan_weights(c, w8s, nb, npix, got))) return r;
+            for (int v = 0; v < nb; v++) {
+                q.w_not_one[v] = got[4 * v] != 0, q.w_odd[v] = got[4 * v + 3] != 0, q.w_one_other[v] = got[4 * v + 1] == got[4 * v + 2];
+                if (q.w_given[v] && q.w_not_one[v]) memcpy(&o.w2a[v], &got[4 * v + 1], 4);
+                else o.w2a[v] = 1.0f;  // (planes of ones in a weighted launch: no selector bit is set, the other value is never used)
+            }
+        } else if (d.need == kNeedCompactCopy) {
+            bool u = false;
+            if ((r = c8_resolve(c, Cs[d.arg], &u))) return r;
+            q.c8_use[d.arg] = u, q.c8_bytes[d.arg] = Cs[d.arg]->cbytes, q.nan_found[d.arg] = Cs[d.arg]->nan_state == CopyState::Invalid;
+        } else if ((r = try_pad(c, Cs, nb, npix, Lreal, LP, d.arg, &q.pad_fits[d.arg])))  // kNeedPadTry (a padded launch: LP label slots)
+            return r;
     }
-    o.weighted_given = weighted;  // (before the ragged FH path borrows the weighted kernels below)
-    // FH potentials on a ragged volume: the min-convolution runs over the RECEIVING pixel's range (mgm_core.cc:242-271), so
-    // it cannot be done once by the producer.  The weighted FH kernels convolve on the consumer side anyway: use them,
-    // with all-ones weights if the caller has none (update_costW_trunclinear with DeltaI = 1 is what the reference calls
-    // then, mgm_core.cc:563-570) -- except for TSGM = 2 without weights, which is update_cost2_trunclinear with its
-    // boundary fix-up (166-186, 197-219) and is not built.
-    bool ragged = false;
-    for (int v = 0; v < nb; v++) ragged |= Cs[v]->rlo != nullptr;
-    o.ragged = ragged;
-    // Volumes whose aggregation can meet NaNs take the slow kernel that keeps the operand order of the reference's minima
-    // (mgm_pass_exact.hip; the fast builds are compiled NaN-free):
-    //   * costs that are descriptor WORDS differenced as floats (-p census with a non-census distance, > 24 bits);
-    //   * a ragged volume with P2 = +INF: the dense layout relies on every slab keeping a finite minimum, which a finite
-    //     P2 guarantees (every term is capped at m + P2); with P2 = +INF a pixel whose neighbours' ranges miss its own gets
-    //     an all-INF slab and the next one INF - INF = NaN;
-    //   * (found below, by the scan of an uploaded volume) NaN costs.
-    //   * more than 2048 labels: no fast kernel is built that wide (the reference's Dvec has no label limit, dvec.cc:60).
-    //   * (round 6, found by the ragged parity tests of tests/) FH potentials on a ragged volume with a NEGATIVE slope -- P1 < 0, or a
-    //     weight <= 0 / NaN scaling it: the fast kernels mask the neighbour's slab to the receiving pixel's range and convolve
-    //     over the whole hull, which equals the reference's convolution over the range (mgm_core.cc:242-271) only while the
-    //     ramp the forward pass leaves ABOVE the range cannot flow back into it (M[rh] + 2 P1 >= M[rh]).
-    o.exact = (ragged && !(P2 < __builtin_huge_valf())) || Lreal > kMaxLPL * 64 || (ragged && fh && (!(P1 >= 0.0f) || wodd));
-    for (int v = 0; v < nb; v++) o.exact |= Cs[v]->nan_words;
-    if (o.exact) return MGM_OK;
-    if (fh && ragged)
-        for (int v = 1; v < nb; v++)
-            if (Cs[v]->dmin != Cs[0]->dmin) return fail(c, MGM_ERR_UNSUPPORTED, "batched ragged volumes must share their hull under FH potentials");
-    if (fh && ragged && !weighted) {
-        // TSGM = 2 without weights is update_cost2_trunclinear with its boundary fix-up (166-186, 197-219): the second
-        // build has it (combine_fh2_ragged); the first build does not
-        o.fh2_ragged = MGM == 2;
-        if (o.fh2_ragged && (first_build || (pass2_lines(L, false) == 0)))
-            return fail(c, MGM_ERR_UNSUPPORTED, "FH potentials with TSGM=2 and no weights on a ragged cost volume need the second build");
+    if (d.err) return dense_error(c, d.err);
+    static_cast<DenseKernels &>(o) = d;
+    if (d.exact) return MGM_OK;
+    // materialise: the borrowed weights, what the pad tries found, the padded fp32 copies
+    if (d.borrow_ones) {
         if ((r = reserve(c, c->ones8, sizeof(float) * (size_t)npix * 8))) return r;
         std::vector<float> one((size_t)npix * 8, 1.0f);
         HIPCHK(c, hipMemcpyAsync(c->ones8.p, one.data(), sizeof(float) * one.size(), hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         o.ones8 = (const float *)c->ones8.p;
-        weighted = true;
     }
-    o.weighted = weighted, o.w2cand = w2cand;
-
-    // compact costs (one byte per label) when the volume allows it
-    bool use_c8 = true;
-    std::vector<char> c8ok(nb, 0);
-    for (int v = 0; v < nb; v++) {  // (also resolves mgm_cv::nan_state: one scan per filling of a volume)
-        bool u = false;
-        if ((r = c8_resolve(c, Cs[v], &u))) return r;
-        c8ok[v] = u;
-        o.exact |= Cs[v]->nan_state == CopyState::Invalid;
-    }
-    if (o.exact) return MGM_OK;
-    int cb = 1;  // bytes per compact cost of this launch
-    // padded launch whose volumes all carry the padded compact copy K2 wrote (mgm_cv::p8): nothing to pad or encode
-    bool own_padded = padded && dev().c8;
-    for (int v = 0; v < nb && own_padded; v++)
-        own_padded = Cs[v]->p8_state == CopyState::Valid && Cs[v]->p8_L == L && Cs[v]->p8_cb == Cs[0]->p8_cb;
-    if (own_padded) {
-        cb = Cs[0]->p8_cb;
-    } else if (padded) {
-        // padded copies of the costs: a compact form if every volume allows it -- the one that worked for the first volume
-        // last time first (mgm_cv::pad_hint), then the other --, else fp32
-        int tries[3] = {Cs[0]->pad_hint == 2 ? 2 : 1, Cs[0]->pad_hint == 2 ? 1 : 2, 0};
-        if (Cs[0]->pad_hint == 0) tries[0] = 0;
-        use_c8 = false;
-        for (int t = 0; t < 3 && dev().c8 && !use_c8; t++) {
-            const int tb = tries[t];
-            if (tb == 0 || (tb == 2 && L > 512)) break;
-            HIPCHK(c, hipMemsetAsync(words + 3, 0, sizeof(unsigned), c->stream));
-            for (int v = 0; v < nb; v++) {
-                if ((r = ensure_f32(c, Cs[v]))) return r;
-                if ((r = reserve(c, c->pad8[v], (size_t)npix * L * tb))) return r;
-                TimeScope ts(c, "k_pad");
-                HIPCHK(c, launch_pad(Cs[v]->d, npix, Lreal, L, nullptr, (uint8_t *)c->pad8[v].p, tb, words + 3, c->stream));
-            }
-            HIPCHK(c, hipMemcpyAsync(c->h_words + 3, words + 3, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-            if (c->h_words[3] == 0) {
-                use_c8 = true;
-                cb = tb;
-            }
-        }
-        for (int v = 0; v < nb; v++) Cs[v]->pad_hint = use_c8 ? cb : 0;
-        if (!use_c8 && (r = pad_f32(c, Cs, nb, npix, Lreal, L))) return r;
-    } else {
-        for (int v = 0; v < nb; v++) use_c8 = use_c8 && c8ok[v] && Cs[v]->cbytes == Cs[0]->cbytes;
-        cb = use_c8 ? Cs[0]->cbytes : 1;
-    }
-    // Two bytes per cost: read by the unweighted kernels with deep rings that publish E, up to 512 labels (k_pass2, C8 == 2);
-    // everything else reads the fp32 volume.  Since round 4 K2 writes AD / SD volumes compact-ONLY (f32_state 0), so a
-    // weighted launch, FH with TSGM = 2 or a shallow-ring launch on such a volume pays an expansion (ensure_f32: k_expand
-    // plus a W*H*L fp32 allocation) the first time -- correct, but four times the cost bytes; bench.py's cost_bytes prices
-    // weighted launches on fp32 costs for that reason.
-    if (use_c8 && cb == 2 && (weighted || (fh && MGM == 2) || lpl > 8 || dev().deep == 0)) {
-        own_padded = false;
-        if (padded && (r = pad_f32(c, Cs, nb, npix, Lreal, L))) return r;
-        use_c8 = false;
-    }
-    // (768 / 1024 labels with weights that are not two-valued-and-narrow: the weighted kernels of the second build stop at
-    // 512 labels -- two slabs per slot do not fit the LDS beyond -- so those take the first build, which has no compact costs)
-    if (first_build || (weighted && lpl > 8)) use_c8 = false;
-    o.use_c8 = use_c8, o.cb = cb, o.own_padded = own_padded;
+    if (d.pad_hint >= 0)
+        for (int v = 0; v < nb; v++) Cs[v]->pad_hint = d.pad_hint;
+    if (d.need_pad_f32 && (r = pad_f32(c, Cs, nb, npix, Lreal, d.L))) return r;
     return MGM_OK;
 }
 

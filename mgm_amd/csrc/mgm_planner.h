@@ -5,6 +5,8 @@
 // caches the plans BY the requests and launches; tests/test_planner.py runs the planner on the host.
 // The winner search is planned here as well (plan_wta, plan_wta_right, plan_wta_rel at the end: which instance, which grid,
 // pruned or not); tests/test_wta_plan.py.
+// ... and which kernels take an aggregation call at all (plan_agg_route, plan_subbatch, plan_dense_kernels behind them: pure functions
+// that ASK for the facts of the device they need, one at a time); tests/test_route_plan.py.
 #pragma once
 #include <algorithm>
 #include <cstring>
@@ -13,6 +15,7 @@
 #include <utility>
 #include <vector>
 
+#include "mgm_fillplan.h"  // padded_labels
 #include "mgm_geom.h"
 
 namespace mgm {
@@ -820,6 +823,251 @@ inline WtaRelChoice plan_wta_rel(const WtaRelRequest &q)
 {
     const long long groups = (q.npix + 15) / 16;  // four waves of four pixels per block
     return WtaRelChoice{std::max(1ll, std::min(groups, q.num_cu * 64)), q.slots == 128 ? 8 : 4, q.cb == 4 ? 4 : (q.cb == 2 ? 2 : 1)};
+}
+
+// ---- which kernels take an aggregation call ----------------------------------------------------------------------------------
+// Three decisions that need facts only the device knows (the weights' values, whether a volume's compact or range-proportional copy
+// is usable, whether a padded copy fits a compact form), and must not ask for one they can do without: a call that is no candidate
+// for the range-proportional kernels never scans its weights for them, a padded launch tries two-byte costs only after one-byte
+// costs failed.  So ONE protocol: a fact of the device starts as -1 in the request ("not probed"), and the planner returns either a
+// finished decision (need == kNeedNothing) or the one fact it wants next; the driver (mgm_api.hip, mgm_plan.hip) probes it, writes
+// it into the request and asks again.  The floats of a call enter as the predicates the code has always used.  tests/test_route_plan.py
+// holds the three to a transcription of the control flow they replace, probe for probe.
+enum PlanNeed {
+    kNeedNothing = 0,
+    kNeedWeightValues,  // the weights' values, all volumes in one scan
+    kNeedRelCopy,       // volume `arg`: is its range-proportional copy usable, and in which format (rel_resolve)
+    kNeedCompactCopy,   // volume `arg`: its compact copy and whether it holds NaN costs (c8_resolve)
+    kNeedPadTry,        // do the padded copies of all volumes fit compact costs of `arg` bytes (k_pad + read-back)
+};
+
+// the range-proportional kernels (run_rel) or the dense hull (run_passes)?
+struct RouteRequest {
+    int n, MGM, fh, want_S;
+    int weights_given;                  // the call has weight images
+    int p1_nonneg, p2_nonneg, p2_finite;  // P1 >= 0, P2 >= 0, P2 < +INF
+    int only_rel;                       // every volume's ONLY copy is the range-proportional one
+    int rel_enabled;                    // MGM_HIP_REL / tune rel: not 0
+    int sw_rel, sw_rel_tie, sw_rel_S, sw_rel_fh2;  // tune rel, rel_tie, rel_S, rel_fh2
+    int w_odd, w_any;                   // (device) some weight is not positive and finite; some weight is not 1
+    int rel_usable[kMaxBatch], rel_slots[kMaxBatch], rel_cb[kMaxBatch];  // (device) per volume, after rel_resolve
+};
+static_assert(std::has_unique_object_representations_v<RouteRequest>, "RouteRequest: integers only, no padding");
+enum { kRouteDense = 0, kRouteRel = 1 };
+struct RouteDecision {
+    int need, arg;
+    int route, rel_weighted;  // rel_weighted: the range-proportional launch runs its weighted kernels (0 on the dense route, which decides for itself)
+};
+inline RouteDecision plan_agg_route(const RouteRequest &q)
+{
+    RouteDecision d{};
+    const bool fh = q.fh != 0;
+    // (round 6: with slope 1, two strips and the 5.6 ms launch the tie is gone: every usable copy is walked; tune rel_tie=0 restores round 5's rule)
+    const bool rel_pays = fh || q.weights_given || q.n >= 2 || q.only_rel || q.sw_rel >= 2 || q.sw_rel_tie != 0;
+    //  the hand-off of k_pass_rel keeps the launch's tag in the sign bit of every published word, so every L / E / minimum
+    // must be >= +0: non-negative penalties and, for weighted launches, positive finite weights: anything else takes the dense kernels.
+    bool sign_ok = q.p1_nonneg && q.p2_nonneg;
+    bool weighted = q.weights_given != 0;
+    const bool candidate = (!q.want_S || q.sw_rel_S != 0) && q.p2_finite && rel_pays && sign_ok && q.rel_enabled;
+    if (candidate && weighted) {
+        if (q.w_odd < 0) return d.need = kNeedWeightValues, d;
+        sign_ok = !q.w_odd;
+        if (q.MGM == 2 && !q.w_any) weighted = false;  // planes of ones: the reference runs unweighted
+    }
+    const bool fn_ok = q.MGM != 2 || weighted || !fh || q.sw_rel_fh2 != 0;  // (update_cost2_trunclinear: k_pass_rel FH2)
+    if (!(candidate && sign_ok && fn_ok)) return d;
+    for (int v = 0; v < q.n; v++) {  // (one format per launch; the first volume that fails ends the asking)
+        if (q.rel_usable[v] < 0) return d.need = kNeedRelCopy, d.arg = v, d;
+        if (!(q.rel_usable[v] && q.rel_slots[v] == q.rel_slots[0] && q.rel_cb[v] == q.rel_cb[0])) return d;
+    }
+    // the one combination whose LDS rings do not fit a CU: update_cost2_trunclinear ([L][F][B] entries) on 128 slots of fp32 costs
+    // (116 KB of rings + 64 KB of cost pieces): the dense hull keeps it
+    if (fh && q.MGM == 2 && !weighted && q.rel_slots[0] == 128 && q.rel_cb[0] == 4) return d;
+    d.route = kRouteRel, d.rel_weighted = weighted ? 1 : 0;
+    return d;
+}
+
+// The sub-batches of a call.  The Lr volumes of a launch take NDIR x W x H x label slots floats per volume; a batch that does not
+// fit the caller's workspace limit is run as several launches over the largest sub-batches that do, and one the device cannot hold
+// (MGM_ERR_NOMEM) in halves.  The two routes differ in their allowances and their rounding, and keep them:
+//   * dense: + ~7 % of hand-off slots, + the chunk minima where a launch may write them (one float per 32 of Lr); multiples of
+//     four volumes, else two, so that volumes keep sharing waves at 64 / 128 labels; halves stay even above four;
+//   * range-proportional: + ~16 % (two hand-off lines per band on the anti-diagonal passes); no rounding.
+struct SubbatchRequest {
+    long long npix, ws_limit, lr_pad;  // pixels; mgm_ctx_set_workspace_limit (0: none); floats between Lr volumes (lr_pad_floats)
+    int route, n, NDIR;
+    int L, rel_slots;                  // labels of the volumes; label slots of their range-proportional format
+    int want_S, refine, prune_enabled;  // what the minima term asks (plan_wta_prune)
+};
+static_assert(std::has_unique_object_representations_v<SubbatchRequest>, "SubbatchRequest: integers only, no padding");
+inline int plan_subbatch(const SubbatchRequest &q)
+{
+    int chunk = q.n;
+    if (!q.ws_limit) return chunk;
+    if (q.route == kRouteRel) {
+        const double per_vol = 4.0 * ((double)q.npix * q.rel_slots + (double)q.lr_pad) * q.NDIR * 1.16;
+        while (chunk > 1 && per_vol * chunk > (double)q.ws_limit) chunk--;
+        return chunk;
+    }
+    const int Lk = padded_labels(q.L) ? padded_labels(q.L) : q.L;
+    const double per_vol = 4.0 * ((double)q.npix * Lk + (double)q.lr_pad) * q.NDIR *
+                           (1.07 + ((q.L == 256 && !q.want_S && q.refine <= 1 && q.prune_enabled) ? 1.0 / kChunkLabels : 0.0));
+    while (chunk > 1 && per_vol * chunk > (double)q.ws_limit) chunk--;
+    if (chunk >= 4) chunk -= chunk % 4;
+    else if (chunk == 3) chunk = 2;
+    return chunk;
+}
+inline int shrink_after_nomem(int route, int m)  // a launch of m > 1 volumes did not fit the device
+{
+    if (route == kRouteRel) return std::max(1, m / 2);
+    return std::max(m > 4 ? (m / 2) - (m / 2) % 2 : m / 2, 1);
+}
+
+// What the volumes and weights of a dense launch ARE, and with that, which kernels can take them (run_passes, stage 1).
+struct DenseKernelsRequest {
+    int nb, MGM, fh, allow_pad, Lreal;
+    int p1_nonneg, p2_nonneg, p2_finite;
+    int force_build;                    // mgm_ctx::force_build (1: the first build only)
+    int lines_real, lines_pad;          // pass2_lines(Lreal, false); pass2_lines(padded_labels(Lreal), false), 0 if there is none
+    int lpl_real, lpl_pad;              // pass_lpl of the two
+    int sw_pad, sw_c8, sw_deep;         // DevSwitches
+    int weights_given;                  // the call has weight images ...
+    int w_given[kMaxBatch];             // ... for this volume
+    int ragged, nan_words, same_hull;   // some volume has per-pixel ranges / costs that are descriptor words; all volumes share dmin
+    int p8_valid[kMaxBatch], p8_L[kMaxBatch], p8_cb[kMaxBatch];  // the padded compact copy the cost kernel wrote (mgm_cv::p8)
+    int pad_hint;                       // the first volume's mgm_cv::pad_hint
+    // (device) the weights' values per volume: some != 1; some not positive and finite; the values != 1 are ONE value
+    int w_not_one[kMaxBatch], w_odd[kMaxBatch], w_one_other[kMaxBatch];
+    // (device) c8_resolve per volume: compact copy usable, its bytes per cost, NaN costs found
+    int c8_use[kMaxBatch], c8_bytes[kMaxBatch], nan_found[kMaxBatch];
+    int pad_fits[3];                    // (device) [bytes per cost]: the padded copies fit that compact form
+};
+static_assert(std::has_unique_object_representations_v<DenseKernelsRequest>, "DenseKernelsRequest: integers only, no padding");
+enum { kDenseOk = 0, kDenseMixedWeights, kDenseRaggedHulls, kDenseFh2NeedsSecondBuild };
+struct DenseKernels {
+    int need = kNeedNothing, arg = 0, err = kDenseOk;
+    int exact = 0;        // the slow operand-order-faithful kernel takes the call (run_passes_exact)
+    int first_build = 0;  // the first build only
+    int L = 0;            // label slots the kernels see (padded launch: the next count of the second build)
+    int padded = 0, own_padded = 0;  // ... padded; every volume carries the padded compact copy K2 wrote (mgm_cv::p8)
+    int use_c8 = 1, cb = 1;          // compact costs of this many bytes
+    int weighted = 0, weighted_given = 0;  // the weighted kernels run; the caller's weights hold a value != 1
+    int w2cand = 0;       // every weighted volume's weights are 1 and ONE other positive finite value
+    int ragged = 0, fh2_ragged = 0;
+    int borrow_ones = 0;  // a ragged FH launch without weights borrows the weighted kernels with all-ones weights
+    int need_pad_f32 = 0;  // the launch reads padded fp32 copies (pad_f32)
+    int pad_hint = -1;    // >= 0: what the pad tries found, to be remembered in the volumes (mgm_cv::pad_hint)
+};
+constexpr int kFastKernelLabels = 2048;  // no fast pass kernel is built wider (64 * kMaxLPL; mgm_plan.hip asserts it)
+inline DenseKernels plan_dense_kernels(const DenseKernelsRequest &q)
+{
+    DenseKernels d;
+    auto ask = [](int need, int arg) { DenseKernels a; return a.need = need, a.arg = arg, a; };
+    auto refuse = [](int err) { DenseKernels a; return a.err = err, a; };
+    const bool fh = q.fh != 0, ragged = q.ragged != 0;
+    // The second build's unweighted kernels keep the sign bit of the slabs they hand from band to band for a validity
+    // tag, which needs E = T - m >= +0, i.e. non-negative penalties (mgm_pass2.hip, TAGS): anything else takes the first build.
+    const bool first_build = q.force_build == 1 || !q.p1_nonneg || !q.p2_nonneg;
+    // A label count the second build does not take (not 64, 128, 192, 256, 384 or 512) runs PADDED: the kernels see
+    // the next such count, the extra label slots hold +INF costs -- "no such label", exactly what a read past a Dvec
+    // returns (dvec.cc:129) -- and stay +INF through every update: C = +INF there and every pixel of a volume with a
+    // uniform range has a finite minimum, so the added term is finite.
+    // (weights with more than 512 labels run on the first build, which takes any label count as it is: no padding then)
+    const bool padded = q.allow_pad && !first_build && q.lines_real == 0 && q.sw_pad && !(q.weights_given && q.Lreal > 512) && padded_labels(q.Lreal) != 0;
+    const int L = padded ? padded_labels(q.Lreal) : q.Lreal, lpl = padded ? q.lpl_pad : q.lpl_real;
+    d.first_build = first_build, d.L = L, d.padded = padded, d.ragged = ragged;
+
+    // weighted? (mgm_core.cc:420-423: any value != 1.0 switches every update) -- and what values do the weights take: the
+    // planes compute_mgm_weights makes hold 1 and ONE other value, which the pass kernel exploits (k_pass2, W2)
+    bool weighted = false, w2cand = false, wodd = false;  // wodd: a weight that is not positive and finite (<= 0, NaN, INF)
+    if (q.weights_given) {
+        if (q.w_not_one[0] < 0) return ask(kNeedWeightValues, 0);
+        w2cand = true;
+        for (int v = 0; v < q.nb; v++) {
+            const bool wv = q.w_given[v] && q.w_not_one[v];
+            // Planes of ones beside real weights: with TSGM != 2 the reference calls the SAME update function either way
+            // (update_costW[_trunclinear] with DeltaI = 1.0, mgm_core.cc:563-575), so the launch simply runs weighted; with
+            // TSGM = 2 the unweighted volume is update_cost2's, a different function: not in one launch.
+            if (v && wv != weighted && (q.MGM == 2 || !q.w_given[v])) return refuse(kDenseMixedWeights);
+            weighted = weighted || wv;
+            wodd = wodd || (wv && q.w_odd[v]);
+            w2cand = w2cand && (!wv || (!q.w_odd[v] && q.w_one_other[v]));
+        }
+        w2cand = w2cand && weighted;
+    }
+    d.weighted_given = weighted;  // (before the ragged FH path borrows the weighted kernels below)
+    // Volumes whose aggregation can meet NaNs take the slow kernel that keeps the operand order of the reference's minima
+    // (mgm_pass_exact.hip; the fast builds are compiled NaN-free):
+    //   * costs that are descriptor WORDS differenced as floats (-p census with a non-census distance, > 24 bits);
+    //   * a ragged volume with P2 = +INF: the dense layout relies on every slab keeping a finite minimum, which a finite
+    //     P2 guarantees (every term is capped at m + P2); with P2 = +INF a pixel whose neighbours' ranges miss its own gets
+    //     an all-INF slab and the next one INF - INF = NaN;
+    //   * (found below, by the scan of an uploaded volume) NaN costs.
+    //   * more than 2048 labels: no fast kernel is built that wide (the reference's Dvec has no label limit, dvec.cc:60).
+    //   * (round 6, found by the ragged parity tests of tests/) FH potentials on a ragged volume with a NEGATIVE slope -- P1 < 0, or a
+    //     weight <= 0 / NaN scaling it: the fast kernels mask the neighbour's slab to the receiving pixel's range and convolve
+    //     over the whole hull, which equals the reference's convolution over the range (mgm_core.cc:242-271) only while the
+    //     ramp the forward pass leaves ABOVE the range cannot flow back into it (M[rh] + 2 P1 >= M[rh]).
+    d.exact = (ragged && !q.p2_finite) || q.Lreal > kFastKernelLabels || (ragged && fh && (!q.p1_nonneg || wodd)) || q.nan_words;
+    if (d.exact) return d;
+    if (fh && ragged && !q.same_hull) return refuse(kDenseRaggedHulls);
+    // FH potentials on a ragged volume: the min-convolution runs over the RECEIVING pixel's range (mgm_core.cc:242-271), so
+    // it cannot be done once by the producer.  The weighted FH kernels convolve on the consumer side anyway: use them,
+    // with all-ones weights if the caller has none (update_costW_trunclinear with DeltaI = 1 is what the reference calls
+    // then, mgm_core.cc:563-570) -- except for TSGM = 2 without weights, which is update_cost2_trunclinear with its
+    // boundary fix-up (166-186, 197-219): the second build has it (combine_fh2_ragged); the first build does not
+    if (fh && ragged && !weighted) {
+        d.fh2_ragged = q.MGM == 2;
+        if (d.fh2_ragged && (first_build || (padded ? q.lines_pad : q.lines_real) == 0)) return refuse(kDenseFh2NeedsSecondBuild);
+        d.borrow_ones = 1;
+        weighted = true;
+    }
+    d.weighted = weighted, d.w2cand = w2cand;
+
+    // compact costs when the volumes allow it (c8_resolve also resolves mgm_cv::nan_state: one scan per filling of a volume)
+    for (int v = 0; v < q.nb; v++)
+        if (q.c8_use[v] < 0) return ask(kNeedCompactCopy, v);
+    for (int v = 0; v < q.nb; v++) d.exact |= q.nan_found[v] != 0;
+    if (d.exact) return d;
+    bool use_c8 = true;
+    int cb = 1;  // bytes per compact cost of this launch
+    // padded launch whose volumes all carry the padded compact copy K2 wrote (mgm_cv::p8): nothing to pad or encode
+    bool own_padded = padded && q.sw_c8;
+    for (int v = 0; v < q.nb && own_padded; v++) own_padded = q.p8_valid[v] && q.p8_L[v] == L && q.p8_cb[v] == q.p8_cb[0];
+    if (own_padded) {
+        cb = q.p8_cb[0];
+    } else if (padded) {
+        // padded copies of the costs: a compact form if every volume allows it -- the one that worked for the first volume
+        // last time first (mgm_cv::pad_hint), then the other --, else fp32
+        const int tries[3] = {q.pad_hint == 0 ? 0 : (q.pad_hint == 2 ? 2 : 1), q.pad_hint == 2 ? 1 : 2, 0};
+        use_c8 = false;
+        for (int t = 0; t < 3 && q.sw_c8 && !use_c8; t++) {
+            const int tb = tries[t];
+            if (tb == 0 || (tb == 2 && L > 512)) break;
+            if (q.pad_fits[tb] < 0) return ask(kNeedPadTry, tb);
+            if (q.pad_fits[tb]) use_c8 = true, cb = tb;
+        }
+        d.pad_hint = use_c8 ? cb : 0;
+        d.need_pad_f32 = !use_c8;
+    } else {
+        for (int v = 0; v < q.nb; v++) use_c8 = use_c8 && q.c8_use[v] && q.c8_bytes[v] == q.c8_bytes[0];
+        cb = use_c8 ? q.c8_bytes[0] : 1;
+    }
+    // Two bytes per cost: read by the unweighted kernels with deep rings that publish E, up to 512 labels (k_pass2, C8 == 2);
+    // everything else reads the fp32 volume.  Since round 4 K2 writes AD / SD volumes compact-ONLY (f32_state 0), so a
+    // weighted launch, FH with TSGM = 2 or a shallow-ring launch on such a volume pays an expansion (ensure_f32: k_expand
+    // plus a W*H*L fp32 allocation) the first time -- correct, but four times the cost bytes; bench.py's cost_bytes prices
+    // weighted launches on fp32 costs for that reason.
+    if (use_c8 && cb == 2 && (weighted || (fh && q.MGM == 2) || lpl > 8 || q.sw_deep == 0)) {
+        own_padded = false;
+        if (padded) d.need_pad_f32 = 1;
+        use_c8 = false;
+    }
+    // (768 / 1024 labels with weights that are not two-valued-and-narrow: the weighted kernels of the second build stop at
+    // 512 labels -- two slabs per slot do not fit the LDS beyond -- so those take the first build, which has no compact costs)
+    if (first_build || (weighted && lpl > 8)) use_c8 = false;
+    d.use_c8 = use_c8, d.cb = cb, d.own_padded = own_padded;
+    return d;
 }
 
 }  // namespace mgm
