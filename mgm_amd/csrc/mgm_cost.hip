@@ -401,15 +401,10 @@ hipError_t launch_compact(const float *C, long long n, uint8_t *C8, int cbytes, 
     return hipGetLastError();
 }
 
-hipError_t launch_cost(const CostParams &p, hipStream_t s, const char **which)
+// the general kernel, one wavefront per pixel (launch_cost, mgm_cost_fast.hip, is the table that leads here)
+hipError_t launch_cost_general(const CostParams &p, unsigned grid, hipStream_t s)
 {
-    bool taken = false;
-    const hipError_t e = launch_cost_fast(p, s, &taken, which);  // (mgm_cost_fast.hip)
-    if (taken || e != hipSuccess) return e;
-    if (which) *which = "k_cost_general";
-    const long long npix = (long long)p.nx * p.ny;
-    if (p.Lreal != p.L) return hipErrorInvalidValue;  // (padded layouts: only the kernels of mgm_cost_fast.hip write them)
-    hipLaunchKernelGGL(k_cost, dim3((unsigned)((npix + 3) / 4)), dim3(256), 0, s, p);
+    hipLaunchKernelGGL(k_cost, dim3(grid), dim3(256), 0, s, p);
     return hipGetLastError();
 }
 

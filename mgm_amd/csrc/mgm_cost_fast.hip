@@ -1,8 +1,9 @@
 // mgm_cost_fast.hip -- K2, the restructured cost-volume kernels of the costs the hot paths use (round 4): single-word census
 // (compact copy only, padded layouts), absolute / squared differences (the same), Birchfield-Tomasi, census over several
 // descriptor words and differences without a compact form (fp32, four pixels per lane), clipped NCC (window statistics once
-// per pixel).  launch_cost (mgm_cost.hip) tries launch_cost_fast first; the general kernel there takes whatever is left
-// (ragged volumes, prefiltered NCC / Birchfield-Tomasi, label counts that are not multiples of four).
+// per pixel) -- and launch_cost, the table from a CostKernelChoice (plan_cost_kernel, mgm_fillplan.h, which decides) to one of
+// these instances or to the general kernel of mgm_cost.hip.  k_cost_census8 serves images of 2^31 - 1 pixels and more, which
+// no test reaches; every smaller single-word census volume goes to k_cost_census8x.
 //
 // Compiled with default (NaN-honouring) floating point, like mgm_cost.hip.
 #include "mgm_cost_common.h"
@@ -80,76 +81,10 @@ __global__ void __launch_bounds__(256) k_cost_census8(const uint32_t *__restrict
     }
 }
 
-// The same costs for label counts that divide 1024, sixteen labels per lane: a wave writes 1 KiB = 1024 / L whole
-// pixels per iteration with 16-byte stores (the 4-byte version above spends its time in per-pixel index arithmetic
-// and load latency: one pixel per wave and iteration).
-template <int L>
-__global__ void __launch_bounds__(256) k_cost_census8w(const uint32_t *__restrict__ cu, const uint32_t *__restrict__ cv,
-                                                       int nx, int ny, int vnx, int vny, int dmin, unsigned tb,
-                                                       uint8_t *__restrict__ C8)
-{
-    static_assert(L == 64 || L == 128 || L == 256 || L == 512, "whole pixels per KiB");
-    constexpr int LP = L / 16;    // lanes per pixel
-    constexpr int PPC = 64 / LP;  // pixels per wave and iteration
-    const long long npix = (long long)nx * ny;
-    const long long nchunk = (npix + PPC - 1) / PPC;
-    const int lane = threadIdx.x & 63, sub = lane / LP, part = lane % LP;
-    const unsigned long long group = (LP == 64 ? ~0ull : ((1ull << (LP % 64)) - 1ull)) << (sub * LP);
-    for (long long chunk = (long long)blockIdx.x * 4 + (threadIdx.x >> 6); chunk < nchunk; chunk += (long long)gridDim.x * 4) {
-        const long long pix = chunk * PPC + sub;
-        const bool live = pix < npix;
-        const unsigned p32 = live ? (unsigned)pix : 0u;  // (npix < 2^31: checked by the caller)
-        const int y = (int)(p32 / (unsigned)nx), x = (int)(p32 - (unsigned)y * (unsigned)nx);
-        const uint32_t wu = cu[p32];
-        const int q0 = x + dmin + part * 16;
-        const bool yin = y < vny;
-        const uint32_t *row = cv + (long long)(yin ? y : 0) * vnx;
-        unsigned w[4];
-        bool fin = false;
-        if (yin && q0 >= 0 && q0 + 16 <= vnx) {  // the lane's sixteen labels lie inside the right image
-            u32x4_a4 t[4];
-#pragma unroll
-            for (int h = 0; h < 4; h++) t[h] = *reinterpret_cast<const u32x4_a4 *>(row + q0 + 4 * h);
-#pragma unroll
-            for (int h = 0; h < 4; h++) {
-                const unsigned v[4] = {t[h].x, t[h].y, t[h].z, t[h].w};
-                unsigned b[4];
-#pragma unroll
-                for (int k = 0; k < 4; k++) {
-                    const unsigned pc = (unsigned)__builtin_popcount(wu ^ v[k]);
-                    b[k] = pc < tb ? pc : tb;
-                    fin |= b[k] != 255u;
-                }
-                w[h] = b[0] | (b[1] << 8) | (b[2] << 16) | (b[3] << 24);
-            }
-        } else {
-#pragma unroll
-            for (int h = 0; h < 4; h++) {
-                unsigned b[4];
-#pragma unroll
-                for (int k = 0; k < 4; k++) {
-                    const int q = q0 + 4 * h + k;
-                    const bool in = yin && q >= 0 && q < vnx;
-                    const unsigned pc = (unsigned)__builtin_popcount(wu ^ row[in ? q : 0]);
-                    b[k] = in ? (pc < tb ? pc : tb) : tb;
-                    fin |= b[k] != 255u;
-                }
-                w[h] = b[0] | (b[1] << 8) | (b[2] << 16) | (b[3] << 24);
-            }
-        }
-        const bool anyfinite = (__builtin_amdgcn_ballot_w64(fin) & group) != 0ull;  // of this pixel's labels
-        if (live) {
-            uint4 o;
-            o.x = anyfinite ? w[0] : 0u; o.y = anyfinite ? w[1] : 0u; o.z = anyfinite ? w[2] : 0u; o.w = anyfinite ? w[3] : 0u;
-            *reinterpret_cast<uint4 *>(C8 + pix * L + part * 16) = o;
-        }
-    }
-}
-
-// The same again with FOUR consecutive pixels of a row per lane (any image width: see W4; any compact
+// The same costs with FOUR consecutive pixels of a row and sixteen labels per lane (any image width: see W4; any compact
 // label count -- at 192 / 384 labels a pixel group takes 12 / 24 lanes and the last 4 / 16 lanes of the wave idle): the sixteen
 // labels of a lane slide along the right image by one word per pixel, so the four pixels share 19 census words where
-// four separate lanes load 64 -- the kernel above is bound by those (L1-resident, unaligned) loads, not by its stores.
+// four separate lanes load 64 -- the kernel above is bound by those (L1-resident, unaligned) loads and its per-pixel index arithmetic.
 template <int L, bool W4>  // W4: the image width is a multiple of four (every group whole and 16-byte aligned); else the last
                             // group of a row holds fewer pixels and the loads / stores are guarded
 __global__ void __launch_bounds__(256) k_cost_census8x(const uint32_t *__restrict__ cu, const uint32_t *__restrict__ cv,
@@ -412,17 +347,6 @@ __global__ void __launch_bounds__(256) k_cost_diffx(const CostParams P)
     if (__builtin_amdgcn_ballot_w64(odd) != 0ull && lane == 0) flag_once(P.bad8, 1u);
     if (__builtin_amdgcn_ballot_w64(odd && hopeless) != 0ull && lane == 0) flag_once(P.bad8, 8u);
 }
-template <int CB, bool SD>
-static void launch_diffx(const CostParams &p, hipStream_t s)
-{
-    long long nw = ((long long)((p.nx + 3) / 4) * p.ny * 4 * p.L * CB / 4096 + 3) / 4 + 1;
-    if (nw > 256 * 32) nw = 256 * 32;
-    const dim3 grid((unsigned)nw), block(256);
-    if (p.nch == 1) hipLaunchKernelGGL((k_cost_diffx<CB, 1, SD>), grid, block, 0, s, p);
-    else if (p.nch == 3) hipLaunchKernelGGL((k_cost_diffx<CB, 3, SD>), grid, block, 0, s, p);
-    else hipLaunchKernelGGL((k_cost_diffx<CB, 0, SD>), grid, block, 0, s, p);
-}
-
 // ---- Birchfield-Tomasi costs, restructured (round 4) --------------------------------------------------------------------
 // computeC_BTAD / computeC_BTSD (mgm_costvolume.h:82-135) look at three samples of each image per cell -- but the interval a
 // sample spans depends on its own image alone: k_bt_spans writes the two ends once per sample (2*nch planes per image, same
@@ -588,9 +512,7 @@ __global__ void __launch_bounds__(256) k_ncc_stats(const float *__restrict__ u, 
 // One wavefront per pixel, lane l takes the labels l, l+64, ...; a workgroup of four waves walks PXB consecutive pixels of
 // one image row with the 2*hw+1 rows of both images around it in LDS (conflict-free: consecutive lanes read consecutive
 // words; the left window is a broadcast read).
-constexpr int kNccPxb = 32;       // pixels of a row per workgroup
-constexpr int kNccMaxHw = 3;      // windows up to 7x7 (CENSUS_NCC_WIN <= 7); wider ones take the general kernel
-constexpr int kNccMaxL = 1024;    // LDS: (PXB + L + 2*hw) floats per row and channel
+// (kNccPxb pixels of a row per workgroup, windows up to kNccMaxHw, kNccMaxL labels: mgm_fillplan.h)
 template <int HW>
 __global__ void __launch_bounds__(256) k_cost_ncc(const CostParams P)
 {
@@ -665,133 +587,102 @@ __global__ void __launch_bounds__(256) k_cost_ncc(const CostParams P)
     }
 }
 
-template <int FN>
-static void launch_btx(const CostParams &p, long long nw, hipStream_t s)
+// ---- launch_cost: from a choice to its instance ---------------------------------------------------------------------------
+template <int HW>
+static hipError_t launch_ncc(const CostParams &p, const CostKernelChoice &k, hipStream_t s)
 {
-    if (p.nx % 4) hipLaunchKernelGGL((k_cost_btx<FN, false>), dim3((unsigned)nw), dim3(256), 0, s, p);
-    else hipLaunchKernelGGL((k_cost_btx<FN, true>), dim3((unsigned)nw), dim3(256), 0, s, p);
+    hipLaunchKernelGGL(k_ncc_stats, dim3(k.pre_grid_u), dim3(256), 0, s, p.u, p.nx, p.ny, p.nch, p.hwin, p.ncc_u);
+    hipLaunchKernelGGL(k_ncc_stats, dim3(k.pre_grid_v), dim3(256), 0, s, p.v, p.vnx, p.vny, p.nch, p.hwin, p.ncc_v);
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_cost_ncc<HW>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_cost_ncc<HW>, dim3(k.grid), dim3(256), k.lds, s, p);
+    return hipGetLastError();
+}
+template <int FN>
+static hipError_t launch_btx(const CostParams &p, const CostKernelChoice &k, hipStream_t s)
+{
+    if (k.pre == CostPre::BtSpans) {  // (the Birchfield-Tomasi instances: the spans of both images first)
+        hipLaunchKernelGGL(k_bt_spans, dim3(k.pre_grid_u), dim3(256), 0, s, p.u, p.nx, p.ny, p.nch, p.ncc_u);
+        hipLaunchKernelGGL(k_bt_spans, dim3(k.pre_grid_v), dim3(256), 0, s, p.v, p.vnx, p.vny, p.nch, p.ncc_v);
+    }
+    if (k.W4) hipLaunchKernelGGL((k_cost_btx<FN, true>), dim3(k.grid), dim3(256), 0, s, p);
+    else hipLaunchKernelGGL((k_cost_btx<FN, false>), dim3(k.grid), dim3(256), 0, s, p);
+    return hipGetLastError();
+}
+template <int CB, bool SD>
+static hipError_t launch_diffx(const CostParams &p, const CostKernelChoice &k, hipStream_t s)
+{
+    switch (k.NCH) {
+    case 1: hipLaunchKernelGGL((k_cost_diffx<CB, 1, SD>), dim3(k.grid), dim3(256), 0, s, p); break;
+    case 3: hipLaunchKernelGGL((k_cost_diffx<CB, 3, SD>), dim3(k.grid), dim3(256), 0, s, p); break;
+    case 0: hipLaunchKernelGGL((k_cost_diffx<CB, 0, SD>), dim3(k.grid), dim3(256), 0, s, p); break;
+    default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
 }
 template <int L>
-static void launch_census8x(const CostParams &p, dim3 grid, unsigned tb, hipStream_t s)
+static hipError_t launch_census8x(const CostParams &p, const CostKernelChoice &k, hipStream_t s)
 {
-    if (p.nx % 4) hipLaunchKernelGGL((k_cost_census8x<L, false>), grid, dim3(256), 0, s, p.cu, p.cv, p.nx, p.ny, p.vnx, p.vny, p.dmin, tb, p.C8, p.Lreal);
-    else hipLaunchKernelGGL((k_cost_census8x<L, true>), grid, dim3(256), 0, s, p.cu, p.cv, p.nx, p.ny, p.vnx, p.vny, p.dmin, tb, p.C8, p.Lreal);
+    if (k.W4) hipLaunchKernelGGL((k_cost_census8x<L, true>), dim3(k.grid), dim3(256), 0, s, p.cu, p.cv, p.nx, p.ny, p.vnx, p.vny, p.dmin, k.tb, p.C8, p.Lreal);
+    else hipLaunchKernelGGL((k_cost_census8x<L, false>), dim3(k.grid), dim3(256), 0, s, p.cu, p.cv, p.nx, p.ny, p.vnx, p.vny, p.dmin, k.tb, p.C8, p.Lreal);
+    return hipGetLastError();
 }
-// Launches the restructured kernel that serves `p`, if there is one (*taken), else leaves the volume to the general kernel.
-hipError_t launch_cost_fast(const CostParams &p, hipStream_t s, bool *taken, const char **which)
+template <int LPL>
+static hipError_t launch_census8(const CostParams &p, const CostKernelChoice &k, hipStream_t s)
 {
-    *taken = true;
-    const char *unused = nullptr;
-    const char *&name = which ? *which : unused;
-    const long long npix = (long long)p.nx * p.ny;
-    if (p.costfn == 3 && p.ncc_u && p.ncc_v && p.C && !p.C8 && !p.rlo && p.hwin >= 1 && p.hwin <= kNccMaxHw && p.L <= kNccMaxL && p.nch <= 4) {
-        const long long vpix = (long long)p.vnx * p.vny;
-        hipLaunchKernelGGL(k_ncc_stats, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, s, p.u, p.nx, p.ny, p.nch, p.hwin, p.ncc_u);
-        hipLaunchKernelGGL(k_ncc_stats, dim3((unsigned)((vpix + 255) / 256)), dim3(256), 0, s, p.v, p.vnx, p.vny, p.nch, p.hwin, p.ncc_v);
-        const int win = 2 * p.hwin + 1;
-        const size_t lds = sizeof(float) * (size_t)p.nch * win * ((kNccPxb + 2 * p.hwin) + (kNccPxb + p.L - 1 + 2 * p.hwin));
-        const dim3 grid((unsigned)(((p.nx + kNccPxb - 1) / kNccPxb) * (long long)p.ny));
-        hipError_t e = hipSuccess;
-        name = "k_cost_ncc";
-        switch (p.hwin) {
-            case 1:
-                e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_cost_ncc<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-                if (e == hipSuccess) hipLaunchKernelGGL(k_cost_ncc<1>, grid, dim3(256), lds, s, p);
-                break;
-            case 2:
-                e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_cost_ncc<2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-                if (e == hipSuccess) hipLaunchKernelGGL(k_cost_ncc<2>, grid, dim3(256), lds, s, p);
-                break;
-            default:
-                e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_cost_ncc<3>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-                if (e == hipSuccess) hipLaunchKernelGGL(k_cost_ncc<3>, grid, dim3(256), lds, s, p);
-                break;
+    hipLaunchKernelGGL(k_cost_census8<LPL>, dim3(k.grid), dim3(256), 0, s, p.cu, p.cv, p.nx, p.ny, p.vnx, p.vny, p.dmin, k.tb, p.C8, p.Lreal);
+    return hipGetLastError();
+}
+
+// Launches the instance `k` names (behind the kernel that prepares its scratch, where the choice has one) and decides nothing: a
+// choice without an instance -- CostFamily::Refused among them -- is hipErrorInvalidValue.
+hipError_t launch_cost(const CostParams &p, const CostKernelChoice &k, hipStream_t s)
+{
+    switch (k.family) {
+    case CostFamily::Ncc:
+        switch (k.HW) {
+        case 1: return launch_ncc<1>(p, k, s);
+        case 2: return launch_ncc<2>(p, k, s);
+        case 3: return launch_ncc<3>(p, k, s);
         }
-        return e != hipSuccess ? e : hipGetLastError();
-    }
-    if (p.costfn >= 4 && p.ncc_u && p.ncc_v && p.C && !p.C8 && !p.rlo && p.L % 4 == 0) {
-        const long long vpix = (long long)p.vnx * p.vny;
-        hipLaunchKernelGGL(k_bt_spans, dim3((unsigned)((npix * p.nch + 255) / 256)), dim3(256), 0, s, p.u, p.nx, p.ny, p.nch, p.ncc_u);
-        hipLaunchKernelGGL(k_bt_spans, dim3((unsigned)((vpix * p.nch + 255) / 256)), dim3(256), 0, s, p.v, p.vnx, p.vny, p.nch, p.ncc_v);
-        long long nw = ((long long)((p.nx + 3) / 4) * p.ny + 3) / 4;
-        if (nw > 256 * 64) nw = 256 * 64;
-        if (nw < 1) nw = 1;
-        name = p.nx % 4 ? "k_cost_btx_bt" : "k_cost_btx_bt_w4";
-        if (p.costfn == 5) launch_btx<5>(p, nw, s);
-        else launch_btx<4>(p, nw, s);
-        return hipGetLastError();
-    }
-    // differences / multi-word census without a compact form: fp32 volume only (see mgm_costvolume_build_dev)
-    if (p.costfn <= 2 && p.C && !p.C8 && !p.rlo && p.L % 4 == 0) {
-        long long nw = ((long long)((p.nx + 3) / 4) * p.ny + 3) / 4;
-        if (nw > 256 * 64) nw = 256 * 64;
-        if (nw < 1) nw = 1;
-        name = p.costfn == 2 ? (p.nx % 4 ? "k_cost_btx_census" : "k_cost_btx_census_w4") : (p.nx % 4 ? "k_cost_btx_diff" : "k_cost_btx_diff_w4");
-        if (p.costfn == 0) launch_btx<0>(p, nw, s);
-        else if (p.costfn == 1) launch_btx<1>(p, nw, s);
-        else launch_btx<2>(p, nw, s);
-        return hipGetLastError();
-    }
-    // (k_cost_diffx takes truncDist = +INF or a non-negative number, sign bit clear; anything else goes to k_cost below)
-    if (!p.C && p.C8 && (p.costfn == 0 || p.costfn == 1) && !p.rlo && npix < 0x7fffffffll && c8_supported(p.L) &&
-        (p.cbytes == 1 || p.cbytes == 2) && p.L * p.cbytes <= 1024 && p.trunc >= 0.0f && !__builtin_signbit(p.trunc)) {
-        name = p.cbytes == 2 ? (p.nch == 1 || p.nch == 3 ? "k_cost_diffx_2b" : "k_cost_diffx_2b_anych")
-                             : (p.nch == 1 || p.nch == 3 ? "k_cost_diffx_1b" : "k_cost_diffx_1b_anych");
-        if (p.cbytes == 2) p.costfn == 1 ? launch_diffx<2, true>(p, s) : launch_diffx<2, false>(p, s);
-        else p.costfn == 1 ? launch_diffx<1, true>(p, s) : launch_diffx<1, false>(p, s);
-        return hipGetLastError();
-    }
-    if (!p.C && p.C8 && p.costfn == 2 && p.nch == 1 && c8_supported(p.L)) {
-        const unsigned tb = p.trunc == __builtin_huge_valf() ? 255u : (unsigned)p.trunc;
-        long long nb = (npix + 3) / 4;
-        if (nb > 256 * 32) nb = 256 * 32;
-        const dim3 block(256);
-        if (npix < 0x7fffffffll) {  // (every compact label count is a multiple of 16)
-            long long nw = ((long long)((p.nx + 3) / 4) * p.ny * 4 * p.L / 4096 + 3) / 4 + 1;
-            if (nw > 256 * 32) nw = 256 * 32;
-            const dim3 gridw((unsigned)nw);
-            name = p.nx % 4 ? "k_cost_census8x" : "k_cost_census8x_w4";
-            switch (p.L) {
-                case 64: launch_census8x<64>(p, gridw, tb, s); break;
-                case 128: launch_census8x<128>(p, gridw, tb, s); break;
-                case 192: launch_census8x<192>(p, gridw, tb, s); break;
-                case 256: launch_census8x<256>(p, gridw, tb, s); break;
-                case 384: launch_census8x<384>(p, gridw, tb, s); break;
-                case 512: launch_census8x<512>(p, gridw, tb, s); break;
-                case 768: launch_census8x<768>(p, gridw, tb, s); break;
-                default: launch_census8x<1024>(p, gridw, tb, s); break;
-            }
-            return hipGetLastError();
+        break;
+    case CostFamily::BtxBt:
+    case CostFamily::BtxDiff:
+    case CostFamily::BtxCensus:
+        switch (k.FN) {
+        case 0: return launch_btx<0>(p, k, s);
+        case 1: return launch_btx<1>(p, k, s);
+        case 2: return launch_btx<2>(p, k, s);
+        case 4: return launch_btx<4>(p, k, s);
+        case 5: return launch_btx<5>(p, k, s);
         }
-        if ((p.L == 64 || p.L == 128 || p.L == 256 || p.L == 512) && npix < 0x7fffffffll && p.Lreal == p.L) {
-            long long nw = (npix * p.L / 1024 + 3) / 4 + 1;
-            if (nw > 256 * 32) nw = 256 * 32;
-            const dim3 gridw((unsigned)nw);
-            name = "k_cost_census8w";
-            switch (p.L) {
-                case 64: hipLaunchKernelGGL(k_cost_census8w<64>, gridw, block, 0, s, p.cu, p.cv, p.nx, p.ny, p.vnx, p.vny, p.dmin, tb, p.C8); break;
-                case 128: hipLaunchKernelGGL(k_cost_census8w<128>, gridw, block, 0, s, p.cu, p.cv, p.nx, p.ny, p.vnx, p.vny, p.dmin, tb, p.C8); break;
-                case 256: hipLaunchKernelGGL(k_cost_census8w<256>, gridw, block, 0, s, p.cu, p.cv, p.nx, p.ny, p.vnx, p.vny, p.dmin, tb, p.C8); break;
-                default: hipLaunchKernelGGL(k_cost_census8w<512>, gridw, block, 0, s, p.cu, p.cv, p.nx, p.ny, p.vnx, p.vny, p.dmin, tb, p.C8); break;
-            }
-            return hipGetLastError();
+        break;
+    case CostFamily::Diffx:
+        switch (2 * k.CB + k.SD) {
+        case 2: return launch_diffx<1, false>(p, k, s);
+        case 3: return launch_diffx<1, true>(p, k, s);
+        case 4: return launch_diffx<2, false>(p, k, s);
+        case 5: return launch_diffx<2, true>(p, k, s);
         }
-        const dim3 grid((unsigned)nb);
-        name = "k_cost_census8";
-        switch (p.L / 64) {
-            case 1: hipLaunchKernelGGL(k_cost_census8<1>, grid, block, 0, s, p.cu, p.cv, p.nx, p.ny, p.vnx, p.vny, p.dmin, tb, p.C8, p.Lreal); break;
-            case 2: hipLaunchKernelGGL(k_cost_census8<2>, grid, block, 0, s, p.cu, p.cv, p.nx, p.ny, p.vnx, p.vny, p.dmin, tb, p.C8, p.Lreal); break;
-            case 3: hipLaunchKernelGGL(k_cost_census8<3>, grid, block, 0, s, p.cu, p.cv, p.nx, p.ny, p.vnx, p.vny, p.dmin, tb, p.C8, p.Lreal); break;
-            case 4: hipLaunchKernelGGL(k_cost_census8<4>, grid, block, 0, s, p.cu, p.cv, p.nx, p.ny, p.vnx, p.vny, p.dmin, tb, p.C8, p.Lreal); break;
-            case 6: hipLaunchKernelGGL(k_cost_census8<6>, grid, block, 0, s, p.cu, p.cv, p.nx, p.ny, p.vnx, p.vny, p.dmin, tb, p.C8, p.Lreal); break;
-            case 8: hipLaunchKernelGGL(k_cost_census8<8>, grid, block, 0, s, p.cu, p.cv, p.nx, p.ny, p.vnx, p.vny, p.dmin, tb, p.C8, p.Lreal); break;
-            case 12: hipLaunchKernelGGL(k_cost_census8<12>, grid, block, 0, s, p.cu, p.cv, p.nx, p.ny, p.vnx, p.vny, p.dmin, tb, p.C8, p.Lreal); break;
-            default: hipLaunchKernelGGL(k_cost_census8<16>, grid, block, 0, s, p.cu, p.cv, p.nx, p.ny, p.vnx, p.vny, p.dmin, tb, p.C8, p.Lreal); break;
+        break;
+    case CostFamily::Census8x:
+        switch (k.LN) {
+#define X(n) case 64 * n: return launch_census8x<64 * n>(p, k, s);
+            MGM_LABEL_BLOCKS(X)
+#undef X
         }
-        return hipGetLastError();
+        break;
+    case CostFamily::Census8:
+        switch (k.LN) {
+#define X(n) case n: return launch_census8<n>(p, k, s);
+            MGM_LABEL_BLOCKS(X)
+#undef X
+        }
+        break;
+    case CostFamily::General: return launch_cost_general(p, k.grid, s);
+    case CostFamily::Refused: break;
     }
-    *taken = false;
-    return hipSuccess;
+    return hipErrorInvalidValue;
 }
 
 }  // namespace mgm

@@ -243,9 +243,9 @@ struct CostParams {
     // interval every sample spans (k_bt_spans), 2*nch planes per image.
     float *ncc_u, *ncc_v;
 };
-// (*which, if wanted: the name of the kernel that took the volume -- what the timing table lists next to "k_cost")
-hipError_t launch_cost(const CostParams &p, hipStream_t s, const char **which = nullptr);
-hipError_t launch_cost_fast(const CostParams &p, hipStream_t s, bool *taken, const char **which = nullptr);  // (mgm_cost_fast.hip; called by launch_cost)
+// the instance plan_cost_kernel (mgm_fillplan.h) chose for the volume `p` describes (mgm_cost_fast.hip: a table that decides nothing)
+hipError_t launch_cost(const CostParams &p, const CostKernelChoice &k, hipStream_t s);
+hipError_t launch_cost_general(const CostParams &p, unsigned grid, hipStream_t s);  // (mgm_cost.hip; called by launch_cost)
 hipError_t launch_filter2d(const float *u, int nx, int ny, int nch, const float *taps, int fnx, int fny, float *out,
                            hipStream_t s);
 hipError_t launch_weights(const float *u, int nx, int ny, int nch, float aP, float aThresh, float *w8,

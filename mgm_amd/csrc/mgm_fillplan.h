@@ -2,7 +2,8 @@
 // (FillRequest), everything decided before the first launch comes out as a plan (plan_fill: the refusal, the scratch of the
 // inputs, the first attempt), and "this attempt came back with this flag word" gives the next attempt (fill_step, rel_next_format).
 // Plain C++17, standard headers only: no device, no context, no environment -- mgm_volume.hip fills the request, launches the
-// attempts and commits the last one to the volume; tests/test_fillplan.py runs the policy on the host.
+// attempts and commits the last one to the volume; tests/test_fillplan.py runs the policy on the host.  Which K2 kernel writes an
+// attempt is decided here as well (plan_cost_kernel, at the end): launch_cost is a table from its choice to an instance.
 #pragma once
 #include <cmath>
 #include <cstddef>
@@ -13,10 +14,14 @@
 
 namespace mgm {
 
+// The label counts that have compact forms, in blocks of 64 labels: one list for padded_labels and the instances of the census kernels.
+#define MGM_LABEL_BLOCKS(X) X(1) X(2) X(3) X(4) X(6) X(8) X(12) X(16)
 // The label count the pass kernels run `L` labels at (151 -> 192 slots, ...); 0: beyond their largest.
 inline int padded_labels(int L)
 {
-    for (int lp : {64, 128, 192, 256, 384, 512, 768, 1024})
+#define X(n) 64 * n,
+    for (int lp : {MGM_LABEL_BLOCKS(X)})
+#undef X
         if (lp >= L) return lp;
     return 0;
 }
@@ -33,6 +38,16 @@ inline int compact_cost_bytes(int costfn, int nch, bool diff_wide, int labels)
 {
     return (costfn == 2 || (costfn == 0 && nch == 1 && !diff_wide) || labels > 512) ? 1 : 2;
 }
+
+// What the restructured K2 kernels ask of a volume, beyond their cost function and target -- the predicates plan_cost_kernel
+// chooses by and plan_fill reserves scratch and attempts the padded layout by.
+// k_cost_diffx: truncDist = +INF or a non-negative number with a clear sign bit (min(e, truncDist) is v_min_f32 there), and
+// pixel groups that index in 32 bits
+inline bool diffx_takes(float trunc, long long npix) { return trunc >= 0.0f && !std::signbit(trunc) && npix < 0x7fffffffll; }
+// k_cost_ncc reads the window statistics of k_ncc_stats: dense volumes of up to four channels (its window and label limits:
+// kNccMaxHw, kNccMaxL); k_cost_btx the sample spans of k_bt_spans: dense volumes
+inline bool ncc_stats_serve(bool ragged, int nch) { return !ragged && nch <= 4; }
+inline bool bt_spans_serve(bool ragged) { return !ragged; }
 
 // What a volume remembers of its earlier fillings.
 struct FillMemory {
@@ -110,12 +125,12 @@ inline FillPlan plan_fill(const FillRequest &q)
         p.inputs = p.pre == 2 ? FillInputs::Sobelx : FillInputs::Gblur;
         p.bytes_u = sizeof(float) * npu * q.nch, p.bytes_v = sizeof(float) * npv * q.nch;
         if (p.pre == 3) p.bytes_tmp = p.bytes_u > p.bytes_v ? p.bytes_u : p.bytes_v;
-    } else if (p.costfn == 3 && !q.ragged && q.nch <= 4) {
+    } else if (p.costfn == 3 && ncc_stats_serve(q.ragged, q.nch)) {
         // clipped NCC on the plain images: the per-pixel window statistics are computed once (k_ncc_stats), in the census
         // buffers, which this combination leaves free
         p.inputs = FillInputs::NccStats;
         p.bytes_u = sizeof(float) * npu * (2 * q.nch + 1), p.bytes_v = sizeof(float) * npv * (2 * q.nch + 1);
-    } else if (p.costfn >= 4 && !q.ragged) {
+    } else if (p.costfn >= 4 && bt_spans_serve(q.ragged)) {
         // Birchfield-Tomasi on the plain images: the interval every sample spans is computed once (k_bt_spans), likewise
         p.inputs = FillInputs::BtSpans;
         p.bytes_u = sizeof(float) * npu * 2 * q.nch, p.bytes_v = sizeof(float) * npv * 2 * q.nch;
@@ -132,7 +147,7 @@ inline FillPlan plan_fill(const FillRequest &q)
     // min(popcount, trunc) in integers (k_cost_census8*, k_cost_census_rel): every cost has a compact form and none is NaN BY
     // CONSTRUCTION -- nothing to read back, a refilled volume costs no synchronisation
     const bool census_fits = census1 && is_byte_code(p.trunc);
-    const bool diff_may_fit = diff && p.trunc >= 0.0f && !std::signbit(p.trunc) && (long long)q.nx * q.ny < 0x7fffffffll;  // (what k_cost_diffx takes)
+    const bool diff_may_fit = diff && diffx_takes(p.trunc, (long long)q.nx * q.ny);
     const bool compact = q.c8 && c8_supported(q.L);
     const int cb = compact_cost_bytes(p.costfn, q.nch, q.mem.diff_wide, q.L);
     const bool twin = compact && (census1 || (diff && tried));
@@ -246,6 +261,136 @@ inline bool rel_next_format(unsigned flag, bool hull_current, int *slots, int *c
     if (s > 128 || b > 4 || !hull_current) return false;
     *slots = s, *cb = b;
     return true;
+}
+
+// ---- which K2 kernel writes an attempt ----------------------------------------------------------------------------------------
+// Everything the choice depends on (mgm_volume.hip: cost_request builds it from the attempt, run_attempts sets the pointers it
+// stands for): the restructured kernels of mgm_cost_fast.hip each take one family of volumes, the general k_cost (mgm_cost.hip)
+// whatever is left -- ragged volumes, prefiltered NCC / Birchfield-Tomasi, label counts that are not multiples of four --, and
+// nothing but the former writes a padded layout.  A RelDirect attempt is not K2's (k_cost_census_rel).
+constexpr int kNccPxb = 32;     // k_cost_ncc: pixels of a row per workgroup
+constexpr int kNccMaxHw = 3;    // windows up to 7x7 (CENSUS_NCC_WIN <= 7); wider ones take the general kernel
+constexpr int kNccMaxL = 1024;  // LDS: (PXB + L + 2*hw) floats per row and channel
+
+struct CostKernelRequest {
+    int costfn, nch, nx, ny, vnx, vny;  // the cost function (0 ad, 1 sd, 2 census, 3 ncc, 4 btad, 5 btsd) and what it reads
+    int L, Lreal;                       // label slots of the layout being written; the labels among them
+    int cbytes, hwin;
+    float trunc;
+    bool f32, compact;  // an fp32 target exists; a compact target exists
+    bool ragged;
+    bool scratch;       // the per-image scratch of the window statistics / sample spans exists (FillInputs::NccStats, BtSpans)
+};
+enum class CostFamily { Refused, Ncc, BtxBt, BtxDiff, BtxCensus, Diffx, Census8x, Census8, General };
+enum class CostPre { None, NccStats, BtSpans };  // the kernel that runs on either image first
+struct CostInstance {
+    CostFamily family;
+    int FN, W4;       // k_cost_btx<FN, W4>; W4 of k_cost_census8x
+    int CB, SD, NCH;  // k_cost_diffx<CB, NCH, SD>: NCH 1, 3 or 0 = any
+    int LN;           // k_cost_census8x<L, W4>: the label count; k_cost_census8<LPL>: labels per lane
+    int HW;           // k_cost_ncc<HW>
+};
+struct CostKernelChoice : CostInstance {
+    CostPre pre;
+    unsigned pre_grid_u, pre_grid_v;
+    unsigned grid;
+    size_t lds;        // dynamic LDS bytes (k_cost_ncc)
+    unsigned tb;       // the census kernels' truncation as a byte
+    const char *name;  // what the timing table lists next to "k_cost"
+};
+
+// The instances launch_cost has, family by family -- the planner returns one of these or Refused.
+constexpr CostInstance kCostInstances[] = {
+    {CostFamily::Ncc, 0, 0, 0, 0, 0, 0, 1}, {CostFamily::Ncc, 0, 0, 0, 0, 0, 0, 2}, {CostFamily::Ncc, 0, 0, 0, 0, 0, 0, 3},
+    {CostFamily::BtxBt, 4, 0}, {CostFamily::BtxBt, 4, 1}, {CostFamily::BtxBt, 5, 0}, {CostFamily::BtxBt, 5, 1},
+    {CostFamily::BtxDiff, 0, 0}, {CostFamily::BtxDiff, 0, 1}, {CostFamily::BtxDiff, 1, 0}, {CostFamily::BtxDiff, 1, 1},
+    {CostFamily::BtxCensus, 2, 0}, {CostFamily::BtxCensus, 2, 1},
+    {CostFamily::Diffx, 0, 0, 1, 0, 1}, {CostFamily::Diffx, 0, 0, 1, 0, 3}, {CostFamily::Diffx, 0, 0, 1, 0, 0},
+    {CostFamily::Diffx, 0, 0, 1, 1, 1}, {CostFamily::Diffx, 0, 0, 1, 1, 3}, {CostFamily::Diffx, 0, 0, 1, 1, 0},
+    {CostFamily::Diffx, 0, 0, 2, 0, 1}, {CostFamily::Diffx, 0, 0, 2, 0, 3}, {CostFamily::Diffx, 0, 0, 2, 0, 0},
+    {CostFamily::Diffx, 0, 0, 2, 1, 1}, {CostFamily::Diffx, 0, 0, 2, 1, 3}, {CostFamily::Diffx, 0, 0, 2, 1, 0},
+#define X(n) {CostFamily::Census8x, 0, 0, 0, 0, 0, 64 * n}, {CostFamily::Census8x, 0, 1, 0, 0, 0, 64 * n}, {CostFamily::Census8, 0, 0, 0, 0, 0, n},
+    MGM_LABEL_BLOCKS(X)
+#undef X
+    {CostFamily::General},
+};
+
+// The name of an instance in the timing table: the family, and the template arguments the tests tell instances apart by.
+inline const char *cost_kernel_name(const CostInstance &k)
+{
+    switch (k.family) {
+    case CostFamily::Ncc: return "k_cost_ncc";
+    case CostFamily::BtxBt: return k.W4 ? "k_cost_btx_bt_w4" : "k_cost_btx_bt";
+    case CostFamily::BtxDiff: return k.W4 ? "k_cost_btx_diff_w4" : "k_cost_btx_diff";
+    case CostFamily::BtxCensus: return k.W4 ? "k_cost_btx_census_w4" : "k_cost_btx_census";
+    case CostFamily::Diffx: return k.CB == 2 ? (k.NCH ? "k_cost_diffx_2b" : "k_cost_diffx_2b_anych") : (k.NCH ? "k_cost_diffx_1b" : "k_cost_diffx_1b_anych");
+    case CostFamily::Census8x: return k.W4 ? "k_cost_census8x_w4" : "k_cost_census8x";
+    case CostFamily::Census8: return "k_cost_census8";
+    case CostFamily::General:
+    case CostFamily::Refused: break;  // (a refusal is the general kernel's: it is the one that cannot write the layout)
+    }
+    return "k_cost_general";
+}
+
+inline CostKernelChoice plan_cost_kernel(const CostKernelRequest &q)
+{
+    CostKernelChoice c{};
+    const long long npix = (long long)q.nx * q.ny, vpix = (long long)q.vnx * q.vny;
+    const long long ngrp = ((long long)q.nx + 3) / 4 * q.ny;  // groups of four pixels of a row (widened first: nx + 3 may not fit an int)
+    const bool f32_alone = q.f32 && !q.compact && !q.ragged, compact_alone = !q.f32 && q.compact;
+    const auto at_most = [](long long n, long long cap) { return n > cap ? cap : n; };
+    const long long nbtx = at_most((ngrp + 3) / 4, 256 * 64);  // k_cost_btx: a wavefront per group, at least one workgroup
+    if (q.costfn == 3 && q.scratch && f32_alone && ncc_stats_serve(q.ragged, q.nch) && q.hwin >= 1 && q.hwin <= kNccMaxHw && q.L <= kNccMaxL) {
+        c.family = CostFamily::Ncc, c.HW = q.hwin;
+        c.pre = CostPre::NccStats, c.pre_grid_u = (unsigned)((npix + 255) / 256), c.pre_grid_v = (unsigned)((vpix + 255) / 256);
+        c.lds = sizeof(float) * (size_t)q.nch * (2 * q.hwin + 1) * ((kNccPxb + 2 * q.hwin) + (kNccPxb + q.L - 1 + 2 * q.hwin));
+        c.grid = (unsigned)(((long long)q.nx + kNccPxb - 1) / kNccPxb * q.ny);
+    } else if ((q.costfn == 4 || q.costfn == 5) && q.scratch && f32_alone && bt_spans_serve(q.ragged) && q.L % 4 == 0) {
+        c.family = CostFamily::BtxBt, c.FN = q.costfn, c.W4 = q.nx % 4 == 0;
+        c.pre = CostPre::BtSpans, c.pre_grid_u = (unsigned)((npix * q.nch + 255) / 256), c.pre_grid_v = (unsigned)((vpix * q.nch + 255) / 256);
+        c.grid = (unsigned)(nbtx < 1 ? 1 : nbtx);
+    } else if (q.costfn >= 0 && q.costfn <= 2 && f32_alone && q.L % 4 == 0) {
+        // differences / census over several descriptor words without a compact form: the fp32 volume alone
+        c.family = q.costfn == 2 ? CostFamily::BtxCensus : CostFamily::BtxDiff, c.FN = q.costfn, c.W4 = q.nx % 4 == 0;
+        c.grid = (unsigned)(nbtx < 1 ? 1 : nbtx);
+    } else if (compact_alone && (q.costfn == 0 || q.costfn == 1) && !q.ragged && diffx_takes(q.trunc, npix) && c8_supported(q.L) &&
+               (q.cbytes == 1 || q.cbytes == 2) && q.L * q.cbytes <= 1024) {
+        c.family = CostFamily::Diffx, c.CB = q.cbytes, c.SD = q.costfn == 1, c.NCH = (q.nch == 1 || q.nch == 3) ? q.nch : 0;
+        c.grid = (unsigned)at_most((ngrp * 4 * q.L * q.cbytes / 4096 + 3) / 4 + 1, 256 * 32);
+    } else if (compact_alone && q.costfn == 2 && q.nch == 1 && c8_supported(q.L)) {
+        // four pixels per lane where the groups index in 32 bits, else one wavefront per pixel (every compact label count is a multiple of 64)
+        c.tb = q.trunc == __builtin_huge_valf() ? 255u : (unsigned)q.trunc;
+        if (npix < 0x7fffffffll) {
+            c.family = CostFamily::Census8x, c.LN = q.L, c.W4 = q.nx % 4 == 0;
+            c.grid = (unsigned)at_most((ngrp * 4 * q.L / 4096 + 3) / 4 + 1, 256 * 32);
+        } else {
+            c.family = CostFamily::Census8, c.LN = q.L / 64;
+            c.grid = (unsigned)at_most((npix + 3) / 4, 256 * 32);
+        }
+    } else if (q.Lreal == q.L) {
+        c.family = CostFamily::General;
+        c.grid = (unsigned)((npix + 3) / 4);
+    }  // (else Refused: only the restructured kernels write a padded layout)
+    bool exists = false;
+    for (const CostInstance &k : kCostInstances)
+        exists |= k.family == c.family && k.FN == c.FN && k.W4 == c.W4 && k.CB == c.CB && k.SD == c.SD && k.NCH == c.NCH && k.LN == c.LN && k.HW == c.HW;
+    if (!exists) c = CostKernelChoice{};
+    c.name = cost_kernel_name(c);
+    return c;
+}
+
+// The request of one attempt of a planned filling (not of a RelDirect one: that is k_cost_census_rel's).
+inline CostKernelRequest cost_request(const FillRequest &q, const FillPlan &p, const FillAttempt &a)
+{
+    CostKernelRequest r{};
+    r.costfn = p.costfn, r.nch = p.nch, r.nx = q.nx, r.ny = q.ny, r.vnx = q.vnx, r.vny = q.vny;
+    r.L = a.form == FillForm::Padded ? a.slots : q.L, r.Lreal = q.L;
+    r.cbytes = a.cbytes, r.hwin = q.census_win / 2, r.trunc = p.trunc;
+    r.f32 = a.form == FillForm::General;
+    r.compact = a.form == FillForm::Padded || a.form == FillForm::CompactOnly || (r.f32 && a.cbytes != 0);
+    r.ragged = q.ragged;
+    r.scratch = p.inputs == FillInputs::NccStats || p.inputs == FillInputs::BtSpans;
+    return r;
 }
 
 }  // namespace mgm

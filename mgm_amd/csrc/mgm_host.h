@@ -305,7 +305,7 @@ struct TimeScope {  // brackets one kernel launch with events when timing is on
     mgm_ctx *c;
     Timing t{};
     bool on;
-    const char *kernel = nullptr;  // which kernel a dispatcher chose (launch_cost): listed after `name` with the same time
+    const char *kernel = nullptr;  // which kernel was chosen for it (plan_cost_kernel): listed after `name` with the same time
     TimeScope(mgm_ctx *ctx, const char *name) : c(ctx), on(ctx->timing)
     {
         if (!on) return;

@@ -345,8 +345,8 @@ static int prepare_inputs(mgm_ctx *c, const FillPlan &plan, const mgm_img *u, co
 }
 
 // Stage 4: the attempts, from the plan's first one to the one that stands.  Each: room for its target, a clear flag word, the
-// launch, the flag word read back where the attempt says so, and fill_step's verdict.
-static int run_attempts(mgm_ctx *c, mgm_cv *cv, const FillPlan &plan, const CostParams &p, FillAttempt *last, FillMemory *mem)
+// kernel plan_cost_kernel chooses for it, the flag word read back where the attempt says so, and fill_step's verdict.
+static int run_attempts(mgm_ctx *c, mgm_cv *cv, const FillRequest &req, const FillPlan &plan, const CostParams &p, FillAttempt *last, FillMemory *mem)
 {
     int r;
     for (FillAttempt a = plan.first;;) {
@@ -385,8 +385,11 @@ static int run_attempts(mgm_ctx *c, mgm_cv *cv, const FillPlan &plan, const Cost
                 t.kernel = "k_cost_census_rel";
                 HIPCHK(c, launch_cost_census_rel(p.cu, p.cv, p.nx, p.ny, p.vnx, p.vny, p.dmin, p.L, p.trunc, p.rlo, p.rhi, a.slots, cv->relbuf, cv->rel_records(),
                                                  flag, c->stream));
-            } else
-                HIPCHK(c, launch_cost(q, c->stream, &t.kernel));
+            } else {
+                const CostKernelChoice k = plan_cost_kernel(cost_request(req, plan, a));
+                t.kernel = k.name;
+                HIPCHK(c, launch_cost(q, k, c->stream));  // (a refused choice: hipErrorInvalidValue)
+            }
         }
         unsigned word = 0u;
         if (a.readback) {
@@ -468,7 +471,7 @@ static int costvolume_fill(mgm_ctx *c, const mgm_img *u, const mgm_img *v, int d
 
     FillAttempt last{};
     FillMemory mem = q.mem;
-    if ((r = run_attempts(c, cv, plan, p, &last, &mem))) return r;
+    if ((r = run_attempts(c, cv, q, plan, p, &last, &mem))) return r;
     commit_fill(cv, q, plan, last, mem);
     if (last.form == FillForm::General && plan.gather_cb) return gather_rel(c, cv, plan.gather_cb);
     return MGM_OK;

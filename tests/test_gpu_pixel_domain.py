@@ -506,8 +506,8 @@ def test_at_size_three_channel_u16_ad(big_oracle):
 
 # ---- the table --------------------------------------------------------------------------------------------------------------
 # every kernel that reads pixels, or what those kernels wrote, must have been entered with these classes
-# every cost kernel launch_cost can choose for an image of fewer than 2^31 pixels (k_cost_census8w and k_cost_census8 cannot be
-# reached: launch_cost_fast takes them only for images of 2^31 pixels and more, every smaller one goes to k_cost_census8x)
+# every cost kernel plan_cost_kernel can choose for an image of fewer than 2^31 - 1 pixels (only k_cost_census8 cannot be
+# reached: it takes single-word census volumes of 2^31 - 1 pixels and more, every smaller one goes to k_cost_census8x)
 COST_KERNELS = ["k_cost_diffx_1b", "k_cost_diffx_1b_anych", "k_cost_diffx_2b", "k_cost_diffx_2b_anych", "k_cost_btx_diff",
                 "k_cost_btx_diff_w4", "k_cost_btx_census", "k_cost_btx_census_w4", "k_cost_btx_bt", "k_cost_btx_bt_w4", "k_cost_ncc",
                 "k_cost_census8x", "k_cost_census8x_w4", "k_cost_general"]
