@@ -273,6 +273,12 @@ int mgm_debug_download_lmin(mgm_ctx *ctx, int slot, int pass, float *out);
  * pruned one (fall-back cases, MGM_HIP_WTA_PRUNE=0) or nothing was counted. */
 int mgm_debug_wta_stats(mgm_ctx *ctx, unsigned long long *pixels, unsigned long long *chunks);
 
+/* Test/diagnostic aid: the pass kernel instance the context's LAST aggregation launched, as a kernel trace spells it --
+ * "k_pass2<4, true, false, 2, 1, 1, true, true, true, false>", "k_pass<16, false, true, 4>",
+ * "k_pass_rel<true, false, 3, 4, 1, false>", or "k_pass_exact" -- written into buf[cap] (truncated to fit, always terminated).
+ * MGM_ERR_INVALID before the context's first aggregation and after mgm_ctx_trim. */
+int mgm_debug_last_pass_kernel(mgm_ctx *ctx, char *buf, int cap);
+
 /* Diagnostic (tools/bimodal_probe.py): the rate, in GB/s, at which the store pattern of the pass kernels -- `nstreams`
  * volumes at the stride of the context's last aggregation, written side by side -- lands on the Lr workspace where the
  * allocator placed it.  MGM_ERR_INVALID before the context's first aggregation. */

@@ -31,7 +31,7 @@ ABI_SYMBOLS = [
     "mgm_multi_create", "mgm_multi_destroy", "mgm_multi_size", "mgm_multi_ctx", "mgm_multi_last_error", "mgm_multi_plan",
     "mgm_multi_aggregate", "mgm_multi_transport", "mgm_img_device", "mgm_cv_device", "mgm_aggregate_passes_at_dev",
     "mgm_ctx_set_workspace_limit", "mgm_ctx_mem_info", "mgm_ctx_set_pipeline", "mgm_img_update", "mgm_debug_probe_workspace", "mgm_ctx_set_placement_tries",
-    "mgm_debug_wta_stats", "mgm_debug_download_lmin",
+    "mgm_debug_wta_stats", "mgm_debug_download_lmin", "mgm_debug_last_pass_kernel",
     "mgm_multiscale_levels", "mgm_zoom_out_dev", "mgm_ranges_zoom_out_dev", "mgm_ranges_from_coarse_dev", "mgm_multiscale_pair_dev",
 ]
 
@@ -93,6 +93,7 @@ def load_library():
     L.mgm_debug_probe_workspace.argtypes = [vp, i, C.POINTER(f)]
     L.mgm_ctx_set_placement_tries.argtypes = [vp, i]
     L.mgm_debug_wta_stats.argtypes = [vp, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]
+    L.mgm_debug_last_pass_kernel.argtypes = [vp, cp, i]
     L.mgm_img_dims.argtypes = [vp, C.POINTER(i), C.POINTER(i), C.POINTER(i)]
     L.mgm_img_device_ptr.argtypes = [vp]
     L.mgm_img_device_ptr.restype = vp
@@ -540,6 +541,12 @@ class Context:
         px, ch = C.c_ulonglong(0), C.c_ulonglong(0)
         self._chk(self.lib.mgm_debug_wta_stats(self.h, C.byref(px), C.byref(ch)))
         return px.value, ch.value
+
+    def last_pass_kernel(self):
+        """The pass kernel instance the context's last aggregation launched, as a kernel trace spells it."""
+        buf = C.create_string_buffer(128)
+        self._chk(self.lib.mgm_debug_last_pass_kernel(self.h, buf, len(buf)))
+        return buf.value.decode()
 
     def selftest_div3(self):
         n = C.c_ulonglong(0)

@@ -464,6 +464,17 @@ int mgm_debug_wta_stats(mgm_ctx *c, unsigned long long *pixels, unsigned long lo
     return MGM_OK;
 }
 
+int mgm_debug_last_pass_kernel(mgm_ctx *c, char *buf, int cap)
+{
+    if (int jr = pipe_join(c)) return jr;  // (pipelined context: run what has been deferred first)
+    if (!c || !buf || cap < 1) return fail(c, MGM_ERR_INVALID, "mgm_debug_last_pass_kernel: null argument");
+    if (!c->last.batch && !c->rel_last.batch) return fail(c, MGM_ERR_INVALID, "mgm_debug_last_pass_kernel: no aggregation to report");
+    const PassKernelChoice &k = c->last.batch ? c->last.kernel : c->rel_last.kernel;
+    if (k.family == kPassRefuse) snprintf(buf, (size_t)cap, "k_pass_exact");  // (a dense run without a planned instance)
+    else pass_kernel_name(k, buf, (size_t)cap);
+    return MGM_OK;
+}
+
 // ---- self-tests -------------------------------------------------------------------
 // Diagnostic: the rate (GB/s) at which the store pattern of the pass kernels lands on the context's Lr workspace as it is
 // placed now -- `nstreams` volumes at the last aggregation's stride written side by side (tools/bimodal_probe.py).

@@ -42,7 +42,7 @@ struct PassParams {
     unsigned *qticket;  // xcdq: the eight queues' ticket counters + the count of workgroups that have left
     int xcdq;                 // 1: per-XCD work queues (k_pass2, XCDQ)
     int subv;                 // volumes per wave (1; 2 at 128 labels, 4 at 64: k_pass2<..., SUBV>); work items then address groups of volumes
-    int wg_per_cu;            // 1 or 2 workgroups per compute unit (second build; see launch2_c8)
+    int wg_per_cu;            // 1 or 2 workgroups per compute unit (second build; plan_dense)
     int deep;                 // 1: the build with deeper DMA rings (k_pass2, DEEP; compact unweighted kernels)
     int oneb;                 // 1: the queue kernels built for one band per CU (k_pass2, ONEB: no 64-VGPR cap)
     int cbytes;               // bytes per compact cost of PassVolume::C8 (1 or 2)
@@ -140,11 +140,9 @@ hipError_t launch_rel_gather(const float *C, const float *rlo, const float *rhi,
 hipError_t launch_cost_census_rel(const uint32_t *cu, const uint32_t *cv, int nx, int ny, int vnx, int vny, int dmin, int L, float trunc, const float *rlo,
                                   const float *rhi, int slots, uint8_t *rel8, int *relb, unsigned *flag, hipStream_t s);
 hipError_t launch_rel_expand(const uint8_t *rel8, const int *relb, long long npix, int L, int dmin, int slots, int cb, float *C, hipStream_t s);
-hipError_t launch_pass_rel(const RelParams &p, int ntasks, bool fh, bool pube, int wg_per_cu, hipStream_t s);
-int pass_rel_lines();
+struct PassKernelChoice;  // (mgm_planner.h: the instance plan_dense / plan_rel chose)
+hipError_t launch_pass_rel(const RelParams &p, const PassKernelChoice &c, int ntasks, hipStream_t s);
 int pass_rel_phases();  // words per work item of phase clocks behind the timeline words (0: not a -DMGM_REL_PHASES=1 build)
-int pass_rel_hand_floats(bool one_slab, int slots, bool fh2);
-size_t pass_rel_lds_bytes(bool one_slab, int slots, int cb, bool fh2, bool diag);
 struct WtaRelParams {
     const uint8_t *c8;
     const int *base;
@@ -185,16 +183,16 @@ struct ExactParams {
 hipError_t launch_pass_exact(const ExactParams &p, hipStream_t s);
 
 // launchers (one per translation unit)
-hipError_t launch_pass(const PassParams &p, int ntasks, int R, bool fh, int wmode, hipStream_t s);
+hipError_t launch_pass(const PassParams &p, const PassKernelChoice &c, int ntasks, hipStream_t s);
 int pass_ns(bool fh, bool weighted);  // slabs per hand-off slot
 int pass_lpl(int L);                  // disparities per lane the pass kernel is instantiated for
 // second build (LDS-DMA loader waves); pass2_lines(L) = lines per band, 0 if L is not supported by it
 int pass2_lines(int L, bool c8);
 bool pass2_devtools();  // built with -DMGM_P2_DEV=1 (MGM_HIP_DEBUG_STATS / MGM_HIP_XFLAGS are honoured)
 bool pass2_timeline();  // built with -DMGM_P2_TIMELINE=1 (MGM_HIP_TIMELINE is honoured)
-hipError_t launch_pass2(const PassParams &p, int ntasks, bool fh, int wmode, hipStream_t s);
+hipError_t launch_pass2(const PassParams &p, const PassKernelChoice &c, int ntasks, hipStream_t s);
 template <int LPL>
-hipError_t launch_pass2_lpl(const PassParams &p, int ntasks, bool fh, int wmode, hipStream_t s);
+hipError_t launch_pass2_lpl(const PassParams &p, const PassKernelChoice &c, int ntasks, hipStream_t s);
 hipError_t launch_compact(const float *C, long long n, uint8_t *C8, int cbytes, unsigned *bad8, hipStream_t s);
 hipError_t launch_nanscan(const float *C, long long n, unsigned *flag, hipStream_t s);
 hipError_t launch_pad(const float *C, long long npix, int L, int LP, float *Cp, uint8_t *C8p, int cbytes, unsigned *bad8, hipStream_t s);

@@ -35,6 +35,22 @@ struct PassGeom {
                           // same step (form 1 with 2 or 3 neighbours: every neighbour sits on the line before); wmax: hand-off slots per line
 };
 
+// The workgroup of the range-proportional kernel (k_pass_rel), for the kernel and the planner alike: 4 compute waves of four lines
+// each + a loader wave; a 4-deep LDS ring per line; 8 slots in each of the rings the loader fills (costs, records, weights, the
+// previous band's slabs); 160 KB of LDS per CU.
+constexpr int kRelWaves = 4, kRelLines = 16, kRelRing = 4, kRelStage = 8, kLdsBytes = 160 * 1024;
+// floats per hand-off slot: a lane's worth of guard words + the values + another guard (one slab: FH, or the producer publishes E),
+// else two slabs; update_cost2_trunclinear (fh2): + the forward and backward passes; + the header's 4
+constexpr int rel_hand_floats(bool one_slab, int slots, bool fh2) { return (fh2 ? 3 * slots + 2 * (slots / 16) : (one_slab ? slots + 2 * (slots / 16) : 2 * slots)) + 4; }
+// LDS bytes of a workgroup: the lines' rings, the hand ring (a second one with anti-diagonal passes), records and weights, the cost
+// pieces, the loader's words, the ticket, the lines' state
+constexpr long long rel_lds_bytes(bool one_slab, int slots, int cb, bool fh2, bool diag)
+{
+    const long long HS = rel_hand_floats(one_slab, slots, fh2);
+    return 4 * (kRelLines * kRelRing * HS + (diag ? 2 : 1) * kRelStage * HS + 2 * kRelStage * kRelLines * 4) + (long long)kRelStage * kRelLines * slots * cb +
+           4 * (kRelStage + 4) + 16 + 4 * kRelLines * 24;
+}
+
 // One launch of the pass kernel may aggregate several cost volumes of identical geometry (the
 // left->right and right->left volumes of a stereo pair, consecutive pairs): work items are then (volume, pass,
 // band), and the long dependency chains of one volume's column passes are hidden behind the other

@@ -129,6 +129,7 @@ struct DenseRun {
     int batch = 0;         // slots: the volumes of the launch
     int L = 0, Lk = 0;     // labels of that aggregation, and the label stride its kernels ran with (>= L)
     bool wrote_min = false;  // the launch wrote the chunk minima of its Lr volumes (mgm_ctx::lmin)
+    PassKernelChoice kernel = {};  // the instance that ran (family kPassRefuse: k_pass_exact, which has one)
     bool pad_c8 = false;   // a padded launch (Lk > L) read compact padded copies of its volumes ...
     int pad_cb = 1;        // ... of this many bytes per cost ...
     const uint8_t *pad_ptr[kMaxBatch] = {};  // ... here: the context's pad8 buffers, or the volumes' own padded copies (mgm_cv::p8)
@@ -167,6 +168,7 @@ struct DenseRun {
 struct RelRun {
     int batch = 0, ndir = 0;
     int slots = 0;  // label slots per pixel of volume 0's copy at that launch (the Lr stride mgm_debug_download_lr reads at)
+    PassKernelChoice kernel = {};  // the instance that ran
     long long stride = 0;
     const mgm_cv *cvs[kMaxBatch] = {};
     unsigned long long gens[kMaxBatch] = {};

@@ -266,50 +266,25 @@ int pass_lpl(int L)
     return lpl <= 12 ? 12 : (lpl <= 16 ? 16 : (lpl <= 24 ? 24 : 32));  // 513..2048 labels: bands of four lines
 }
 
-template <int LPL, bool FH, bool WEIGHTED, int R>
-static hipError_t launch_one(const PassParams &p, int ntasks, hipStream_t s)
+// A table from the planner's choice (plan_dense, mgm_planner.h) to its instance: decides nothing, and has no instance for what
+// pass_instance denies.
+hipError_t launch_pass(const PassParams &p, const PassKernelChoice &c, int ntasks, hipStream_t s)
 {
-    constexpr int LP = LPL * 64;
-    constexpr int NS = (WEIGHTED && !FH) ? 2 : 1;
-    const size_t shmem = sizeof(float) * (R * 2 * NS * LP + R * 2) + 16;
-    auto kern = k_pass<LPL, FH, WEIGHTED, R>;
-    if (shmem > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(kern, dim3(ntasks), dim3(R * 64), shmem, s, p);
-    return hipGetLastError();
-}
-
-template <int LPL, int R>
-static hipError_t launch_lpl(const PassParams &p, int ntasks, bool fh, int wmode, hipStream_t s)
-{
-    if (!wmode) return fh ? launch_one<LPL, true, false, R>(p, ntasks, s) : launch_one<LPL, false, false, R>(p, ntasks, s);
-    return fh ? launch_one<LPL, true, true, R>(p, ntasks, s) : launch_one<LPL, false, true, R>(p, ntasks, s);
-}
-
-hipError_t launch_pass(const PassParams &p, int ntasks, int R, bool fh, int wmode, hipStream_t s)
-{
-    const int lpl = pass_lpl(p.L);
-    if (R == 4)  // more than 512 labels (any label count up to 2048): the slabs of a line need most of a SIMD's registers
-        switch (lpl) {
-            case 12: return launch_lpl<12, 4>(p, ntasks, fh, wmode, s);
-            case 16: return launch_lpl<16, 4>(p, ntasks, fh, wmode, s);
-            case 24: return launch_lpl<24, 4>(p, ntasks, fh, wmode, s);
-            case 32: return launch_lpl<32, 4>(p, ntasks, fh, wmode, s);
-            default: return hipErrorInvalidValue;
-        }
-    if (R != 16) return hipErrorInvalidValue;
-    switch (lpl) {
-        case 1: return launch_lpl<1, 16>(p, ntasks, fh, wmode, s);
-        case 2: return launch_lpl<2, 16>(p, ntasks, fh, wmode, s);
-        case 3: return launch_lpl<3, 16>(p, ntasks, fh, wmode, s);
-        case 4: return launch_lpl<4, 16>(p, ntasks, fh, wmode, s);
-        case 6: return launch_lpl<6, 16>(p, ntasks, fh, wmode, s);
-        case 8: return launch_lpl<8, 16>(p, ntasks, fh, wmode, s);
-        default: return hipErrorInvalidValue;
-    }
+    if (c.family != kPassFirst) return hipErrorInvalidValue;
+    // (the values in this order: the compiler emits the instances in the reverse of it, which is the order they have always had in the
+    // object -- two of them, k_pass<1, *, false, 16>, come out with other registers in another)
+    return lift<kR, 4>(c.R, [&](auto R) { return lift<32, 24, 16, 12, 8, 6, 4, 3, 2, 1>(c.LPL, [&](auto LPL) { return lift<1, 0>(c.WEIGHTED, [&](auto W) { return lift<0, 1>(c.FH, [&](auto FH) {
+        if constexpr (pass_instance(LPL(), R())) {
+            auto kern = k_pass<LPL(), FH() != 0, W() != 0, R()>;
+            if (c.lds > 48 * 1024) {
+                hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, c.lds);
+                if (e != hipSuccess) return e;
+            }
+            hipLaunchKernelGGL(kern, dim3(ntasks), dim3(c.block), c.lds, s, p);
+            return hipGetLastError();
+        } else
+            return hipErrorInvalidValue;
+    }); }); }); });
 }
 
 }  // namespace mgm

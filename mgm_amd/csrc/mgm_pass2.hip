@@ -1079,7 +1079,7 @@ __device__ __forceinline__ void pass2_item(const PassParams &P, const int ticket
 // order, so the earliest unfinished item of the launch is always at the head of its queue with all it needs finished),
 // and the last workgroup to leave checks that every queue was worked off -- a queue without workgroups raises the
 // watchdog word instead of leaving lines unwritten.
-// ONEB: the build for launches that run ONE band per CU (chain-bound: mgm_api.hip, wg_per_cu == 1).  The compact
+// ONEB: the build for launches that run ONE band per CU (chain-bound: plan_dense, wg_per_cu == 1).  The compact
 // unweighted kernels are otherwise capped at 64 VGPRs so that two bands fit a CU, and under that cap every FH instance
 // with the queue loop spilled 9-14 VGPRs (40-52 bytes of scratch per lane) and ~50 SGPRs -- scratch traffic and
 // v_readlane restores on the critical chain of exactly the launches that are bound by the length of a step.
@@ -1128,106 +1128,32 @@ __global__ void __launch_bounds__((Plan<LPL, 1, true, C8>::NC + Plan<LPL, 1, tru
 }
 
 // ---- launcher (one translation unit per LPL: -DMGM_P2_LPL=n) -----------------------
-template <int LPL, bool FH, bool WEIGHTED, int MGM, int C8, int SUBV = 1, bool DEEP = false, bool XCDQ = false, bool ONEB = false, bool W2 = false>
-static hipError_t launch2_c8(const PassParams &p, int ntasks, hipStream_t s)
-{
-    using PL = typename P2Lds<LPL, FH, WEIGHTED, MGM, C8, DEEP, W2>::PL;
-    size_t shmem = sizeof(float) * (size_t)PL::lds_floats(PL::D);
-    // Occupancy is chosen per launch through the LDS request: the compact unweighted kernels are built for two
-    // workgroups per CU (<= 64 VGPRs, < 80 KB of LDS).  Two bands per CU hide each other's barrier and LDS stalls --
-    // right when the launch is throughput-bound (a batch of volumes); a single volume is bound by the chain of
-    // bands, where the doubled step latency costs more than it gives, so it asks for > half the LDS and runs alone.
-    if (p.wg_per_cu < 2 && shmem < 81 * 1024) shmem = 81 * 1024;
-    auto kern = k_pass2<LPL, FH, WEIGHTED, MGM, C8, SUBV, DEEP, XCDQ, ONEB, W2>;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(ntasks), dim3((PL::NC + PL::NL) * 64), shmem, s, p);
-    return hipGetLastError();
-}
-
-template <int LPL, bool FH, bool WEIGHTED, int MGM>
-static hipError_t launch2_one(const PassParams &p, int ntasks, hipStream_t s)
-{
-    // (The kernels with per-XCD queues do not exist in development builds: with the timers compiled in, this compiler
-    // fails on some of their instances -- "Illegal instruction detected: Operand has incorrect register class",
-    // V_CMP_NE_U32 on src_shared_base.  The host does not ask for them there, mgm_api.hip.)
-    if constexpr (LPL == 4 && !WEIGHTED && !(FH && MGM == 2)) {  // several volumes per wave (128 / 64 labels)
-        if (p.subv > 1 && p.xcdq) return hipErrorInvalidValue;  // (no gain measured there: cfg2 x 4..16, cfg5 x 4..16 within noise)
-        if (p.subv == 2 && p.vol[0].C8) {
-            return p.deep ? launch2_c8<LPL, FH, WEIGHTED, MGM, true, 2, true>(p, ntasks, s) : launch2_c8<LPL, FH, WEIGHTED, MGM, true, 2>(p, ntasks, s);
-        }
-        if (p.subv == 4 && p.vol[0].C8) {
-            return p.deep ? launch2_c8<LPL, FH, WEIGHTED, MGM, true, 4, true>(p, ntasks, s) : launch2_c8<LPL, FH, WEIGHTED, MGM, true, 4>(p, ntasks, s);
-        }
-    }
-    if (p.subv > 1) return hipErrorInvalidValue;
-    if constexpr (!WEIGHTED && !(FH && MGM == 2) && LPL <= 8)
-        if (p.vol[0].C8 && p.cbytes == 2) {  // two bytes per cost (round 4): the kernels with deep rings only
-            if (!p.deep) return hipErrorInvalidValue;
-            if constexpr (!MGM_P2_DEV) {
-                if (p.xcdq && p.oneb) return launch2_c8<LPL, FH, WEIGHTED, MGM, 2, 1, true, true, true>(p, ntasks, s);
-                if (p.xcdq) return launch2_c8<LPL, FH, WEIGHTED, MGM, 2, 1, true, true, false>(p, ntasks, s);
-            }
-            if (p.xcdq) return hipErrorInvalidValue;
-            return launch2_c8<LPL, FH, WEIGHTED, MGM, 2, 1, true>(p, ntasks, s);
-        }
-    if (p.vol[0].C8 && p.cbytes == 2) return hipErrorInvalidValue;
-    if constexpr (!WEIGHTED && !(FH && MGM == 2))
-        if (p.vol[0].C8 && p.deep) {
-            if constexpr (!MGM_P2_DEV) {
-                // (the Hirschmueller launches with queues run one band per CU unless told otherwise, the FH ones up to a
-                // load/chain of 1.5: mgm_api.hip)
-                if (p.xcdq && p.oneb) return launch2_c8<LPL, FH, WEIGHTED, MGM, true, 1, true, true, true>(p, ntasks, s);
-                if (p.xcdq) return launch2_c8<LPL, FH, WEIGHTED, MGM, true, 1, true, true, false>(p, ntasks, s);
-            }
-            if (p.xcdq) return hipErrorInvalidValue;
-            return launch2_c8<LPL, FH, WEIGHTED, MGM, true, 1, true>(p, ntasks, s);
-        }
-    if (p.vol[0].C8) return launch2_c8<LPL, FH, WEIGHTED, MGM, true>(p, ntasks, s);
-    return launch2_c8<LPL, FH, WEIGHTED, MGM, false>(p, ntasks, s);
-}
-
-template <int LPL, bool FH, bool WEIGHTED>
-static hipError_t launch2_mgm(const PassParams &p, int ntasks, hipStream_t s)
-{
-    switch (p.MGM) {
-        case 1: return launch2_one<LPL, FH, WEIGHTED, 1>(p, ntasks, s);
-        case 2: return launch2_one<LPL, FH, WEIGHTED, 2>(p, ntasks, s);
-        case 3: return launch2_one<LPL, FH, WEIGHTED, 3>(p, ntasks, s);
-        case 4: return launch2_one<LPL, FH, WEIGHTED, 4>(p, ntasks, s);
-        default: return hipErrorInvalidValue;
-    }
-}
-
+// A table from the planner's choice (plan_dense, mgm_planner.h) to its instance.  Nothing is decided here: the instances are
+// those pass2_instance admits for this build (a development build has no queue and no W2 kernels), and a choice that names
+// none of them is hipErrorInvalidValue -- the planner refuses such a launch before it gets here.
 #ifndef MGM_P2_LPL
 #error "compile with -DMGM_P2_LPL=<1|2|3|4|6|8|12|16>"
 #endif
-// two-valued weights (wmode 2): the compact kernels with deep rings and per-XCD queues, one band per CU
-template <int LPL, bool FH>
-static hipError_t launch2_w2(const PassParams &p, int ntasks, hipStream_t s)
-{
-    if constexpr (LPL <= 4 && !MGM_P2_DEV) {
-        if (!p.vol[0].C8 || !p.deep || !p.xcdq || p.subv > 1 || !p.vol[0].wsel) return hipErrorInvalidValue;
-        switch (p.MGM) {
-            case 1: return launch2_c8<LPL, FH, false, 1, true, 1, true, true, true, true>(p, ntasks, s);
-            case 2: return launch2_c8<LPL, FH, false, 2, true, 1, true, true, true, true>(p, ntasks, s);
-            case 3: return launch2_c8<LPL, FH, false, 3, true, 1, true, true, true, true>(p, ntasks, s);
-            case 4: return launch2_c8<LPL, FH, false, 4, true, 1, true, true, true, true>(p, ntasks, s);
-            default: return hipErrorInvalidValue;
-        }
-    }
-    return hipErrorInvalidValue;
-}
-
 template <>
-hipError_t launch_pass2_lpl<MGM_P2_LPL>(const PassParams &p, int ntasks, bool fh, int wmode, hipStream_t s)
+hipError_t launch_pass2_lpl<MGM_P2_LPL>(const PassParams &p, const PassKernelChoice &c, int ntasks, hipStream_t s)
 {
     constexpr int LPL = MGM_P2_LPL;
-    if (wmode == 2) return fh ? launch2_w2<LPL, true>(p, ntasks, s) : launch2_w2<LPL, false>(p, ntasks, s);
-    if (!wmode) return fh ? launch2_mgm<LPL, true, false>(p, ntasks, s) : launch2_mgm<LPL, false, false>(p, ntasks, s);
-    if constexpr (LPL >= 12) return hipErrorInvalidValue;  // (768 / 1024 labels: the weighted kernels' rings do not fit the LDS; first build)
-    else return fh ? launch2_mgm<LPL, true, true>(p, ntasks, s) : launch2_mgm<LPL, false, true>(p, ntasks, s);
+    if (c.family != kPassSecond || c.LPL != LPL) return hipErrorInvalidValue;
+    return lift<0, 1>(c.FH, [&](auto FH) { return lift<0, 1>(c.WEIGHTED, [&](auto W) { return lift<1, 2, 3, 4>(c.MGM, [&](auto MGM) { return lift<0, 1, 2>(c.C8, [&](auto C8) {
+    return lift<1, 2, 4>(c.SUBV, [&](auto SUBV) { return lift<0, 1>(c.DEEP, [&](auto DEEP) { return lift<0, 1>(c.XCDQ, [&](auto XCDQ) { return lift<0, 1>(c.ONEB, [&](auto ONEB) {
+    return lift<0, 1>(c.W2, [&](auto W2) {
+        if constexpr (pass2_instance(MGM_P2_DEV != 0, LPL, FH(), W(), MGM(), C8(), SUBV(), DEEP(), XCDQ(), ONEB(), W2())) {
+            using PL = typename P2Lds<LPL, FH() != 0, W() != 0, MGM(), C8(), DEEP() != 0, W2() != 0>::PL;
+            // (the choice's floor: a launch that runs one band per CU asks for more than half the LDS, plan_dense)
+            const size_t shmem = std::max(sizeof(float) * (size_t)PL::lds_floats(PL::D), (size_t)c.lds);
+            auto kern = k_pass2<LPL, FH() != 0, W() != 0, MGM(), C8(), SUBV(), DEEP() != 0, XCDQ() != 0, ONEB() != 0, W2() != 0>;
+            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
+            if (e != hipSuccess) return e;
+            hipLaunchKernelGGL(kern, dim3(ntasks), dim3((PL::NC + PL::NL) * 64), shmem, s, p);
+            return hipGetLastError();
+        } else
+            return hipErrorInvalidValue;
+    }); }); }); }); }); }); }); }); });
 }
 
 }  // namespace mgm

@@ -1,6 +1,7 @@
 // mgm_pass2_dispatch.hip -- picks the per-LPL object of the second K3 build
 // (mgm_pass2.hip is compiled once per LPL with -DMGM_P2_LPL=n).
 #include "mgm_device.h"
+#include "mgm_planner.h"
 
 #ifndef MGM_P2_C8_NL
 #define MGM_P2_C8_NL 1
@@ -32,17 +33,12 @@ int pass2_lines(int L, bool c8)
     return 0;
 }
 
-hipError_t launch_pass2(const PassParams &p, int ntasks, bool fh, int wmode, hipStream_t s)
+hipError_t launch_pass2(const PassParams &p, const PassKernelChoice &c, int ntasks, hipStream_t s)
 {
-    switch (p.subv > 1 ? 4 : (p.L % 64 ? 0 : p.L / 64)) {
-        case 1: return launch_pass2_lpl<1>(p, ntasks, fh, wmode, s);
-        case 2: return launch_pass2_lpl<2>(p, ntasks, fh, wmode, s);
-        case 3: return launch_pass2_lpl<3>(p, ntasks, fh, wmode, s);
-        case 4: return launch_pass2_lpl<4>(p, ntasks, fh, wmode, s);
-        case 6: return launch_pass2_lpl<6>(p, ntasks, fh, wmode, s);
-        case 8: return launch_pass2_lpl<8>(p, ntasks, fh, wmode, s);
-        case 12: return launch_pass2_lpl<12>(p, ntasks, fh, wmode, s);
-        case 16: return launch_pass2_lpl<16>(p, ntasks, fh, wmode, s);
+    switch (c.LPL) {
+#define X(n) case n: return launch_pass2_lpl<n>(p, c, ntasks, s);
+        X(1) X(2) X(3) X(4) X(6) X(8) X(12) X(16)
+#undef X
         default: return hipErrorInvalidValue;
     }
 }

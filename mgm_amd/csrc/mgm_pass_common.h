@@ -7,9 +7,22 @@
 // finite cost, mgm_costvolume.h:414-421).  Nothing here may rely on NaN
 // semantics.
 #pragma once
+#include <type_traits>
+
 #include "mgm_device.h"
+#include "mgm_planner.h"  // PassKernelChoice and the statement of which instances are built
 
 namespace mgm {
+
+// How the launchers turn an integer of the planner's choice into a template argument: f(std::integral_constant) for the value among
+// Vs..., hipErrorInvalidValue for any other.  They decide nothing; what to instantiate is pass*_instance's (mgm_planner.h).
+template <int... Vs, class F>
+static hipError_t lift(int v, F f)
+{
+    hipError_t e = hipErrorInvalidValue;
+    (void)((v == Vs && ((e = f(std::integral_constant<int, Vs>{})), true)) || ...);
+    return e;
+}
 
 constexpr int PF = 4;                    // prefetch depth (steps)
 constexpr int CH = 8;                    // pixels per inter-band progress publication

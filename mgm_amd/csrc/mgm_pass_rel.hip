@@ -33,11 +33,12 @@ namespace mgm {
 #ifndef MGM_REL_PHASES
 #define MGM_REL_PHASES 0  // 1 (development build, MGM_REL_DEFINES=-DMGM_REL_PHASES=1): per work item, the clocks every wave spent computing /
 #endif                    // publishing / at the step barrier, and the loader issuing / waiting for its DMAs / at the barrier (with MGM_HIP_TIMELINE)
-constexpr int NW = 4;        // compute waves of a workgroup (+ 1 loader wave)
-constexpr int GL = 4;        // scan lines per wave: lane groups of 16 lanes, 4 label slots per lane
-constexpr int RR = NW * GL;  // lines per band
-constexpr int RD4 = 4;   // ring slots per line
-constexpr int SD = 8;    // slots of the rings the loader wave fills (costs, records, weights, the previous band's slabs)
+constexpr int NW = kRelWaves;  // compute waves of a workgroup (+ 1 loader wave)   (mgm_geom.h: the planner sizes the LDS request by these)
+constexpr int GL = 4;          // scan lines per wave: lane groups of 16 lanes, 4 label slots per lane
+constexpr int RR = kRelLines;  // lines per band
+constexpr int RD4 = kRelRing;  // ring slots per line
+constexpr int SD = kRelStage;  // slots of the rings the loader wave fills (costs, records, weights, the previous band's slabs)
+static_assert(RR == NW * GL, "a band is every wave's lines");
 
 typedef __attribute__((address_space(3))) void *rel_lds_vptr;
 typedef const __attribute__((address_space(1))) void *rel_glb_vptr;
@@ -893,63 +894,23 @@ __global__ void __launch_bounds__((NW + 1) * 64) k_pass_rel(const RelParams P)
         }
 }
 
-template <bool FH, bool PUBE, int NK, int SPL, int CB, bool FH2 = false>
-static hipError_t launch_rel_one(const RelParams &p, int ntasks, int wg_per_cu, hipStream_t s)
+// A table from the planner's choice (plan_rel, mgm_planner.h) to its instance: the instances are those pass_rel_instance admits, the
+// LDS request (rel_lds_bytes, mgm_geom.h, with the floor that sets the workgroups per CU) is the choice's.
+hipError_t launch_pass_rel(const RelParams &p, const PassKernelChoice &c, int ntasks, hipStream_t s)
 {
-    constexpr int NS = (FH || PUBE) ? 1 : 2;
-    constexpr int SLOTS = 16 * SPL;
-    constexpr int HS = (FH2 ? 3 * SLOTS + 2 * SPL : (NS == 1 ? SLOTS + 2 * SPL : NS * SLOTS)) + 4;
-    size_t shmem = sizeof(float) * ((size_t)RR * RD4 * HS + (size_t)(p.diag_any ? 2 : 1) * SD * HS + 2 * SD * RR * 4) + (size_t)SD * RR * SLOTS * CB + sizeof(unsigned) * (SD + 4) + 16 + sizeof(int) * RR * 24;
-    // Occupancy through the LDS request, as for the second build: wg_per_cu workgroups (of 4 compute waves: one per SIMD) share a
-    // CU -- one for a launch bound by its chains of bands, more for a batch (throughput)
-    if (wg_per_cu >= 1) {
-        const size_t want = (size_t)(160 * 1024) / (size_t)(wg_per_cu + 1) + 1024;  // more than a (wg_per_cu + 1)-th of the LDS
-        if (shmem < want) shmem = want;
-    }
-    auto kern = k_pass_rel<FH, PUBE, NK, SPL, CB, FH2>;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(ntasks), dim3((NW + 1) * 64), shmem, s, p);
-    return hipGetLastError();
+    if (c.family != kPassRel) return hipErrorInvalidValue;
+    return lift<0, 1>(c.FH, [&](auto FH) { return lift<0, 1>(c.PUBE, [&](auto PUBE) { return lift<0, 1, 2, 3, 4>(c.NK, [&](auto NK) { return lift<4, 8>(c.SPL, [&](auto SPL) {
+    return lift<1, 2, 4>(c.CB, [&](auto CB) { return lift<0, 1>(c.FH2, [&](auto FH2) {
+        if constexpr (pass_rel_instance(FH(), PUBE(), NK(), SPL(), CB(), FH2())) {
+            auto kern = k_pass_rel<FH() != 0, PUBE() != 0, NK(), SPL(), CB(), FH2() != 0>;
+            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, c.lds);
+            if (e != hipSuccess) return e;
+            hipLaunchKernelGGL(kern, dim3(ntasks), dim3((NW + 1) * 64), c.lds, s, p);
+            return hipGetLastError();
+        } else
+            return hipErrorInvalidValue;
+    }); }); }); }); }); });
 }
-template <int SPL, int CB>
-static hipError_t launch_rel_fmt(const RelParams &p, int ntasks, bool fh, bool pube, int wg_per_cu, hipStream_t s)
-{
-    if (fh) {
-        if constexpr (SPL == 4 && CB == 1)  // (the one-after-the-other build is kept for the form round 5 measured, as an A/B switch)
-            if (!p.fh_multi) return launch_rel_one<true, false, 0, SPL, CB>(p, ntasks, wg_per_cu, s);
-        if (p.fh2) {  // update_cost2_trunclinear (TSGM = 2, no weights)
-            if constexpr (SPL == 8 && CB == 4) return hipErrorInvalidValue;  // (its rings + the cost pieces exceed the LDS: the host keeps this one on the dense hull)
-            else return launch_rel_one<true, false, 2, SPL, CB, true>(p, ntasks, wg_per_cu, s);
-        }
-        switch (p.MGM) {
-        case 1: return launch_rel_one<true, false, 1, SPL, CB>(p, ntasks, wg_per_cu, s);
-        case 2: return launch_rel_one<true, false, 2, SPL, CB>(p, ntasks, wg_per_cu, s);
-        case 3: return launch_rel_one<true, false, 3, SPL, CB>(p, ntasks, wg_per_cu, s);
-        default: return launch_rel_one<true, false, 4, SPL, CB>(p, ntasks, wg_per_cu, s);
-        }
-    }
-    return pube ? launch_rel_one<false, true, 0, SPL, CB>(p, ntasks, wg_per_cu, s) : launch_rel_one<false, false, 0, SPL, CB>(p, ntasks, wg_per_cu, s);
-}
-// pube: unit weights with Hirschmueller potentials (the producer publishes E); wg_per_cu: workgroups per CU (0: what fits);
-// p.slots (64 / 128) and p.cb (1 / 2): the volumes' range-proportional format
-hipError_t launch_pass_rel(const RelParams &p, int ntasks, bool fh, bool pube, int wg_per_cu, hipStream_t s)
-{
-    if (p.slots == 128)
-        return p.cb == 4 ? launch_rel_fmt<8, 4>(p, ntasks, fh, pube, wg_per_cu, s)
-                         : (p.cb == 2 ? launch_rel_fmt<8, 2>(p, ntasks, fh, pube, wg_per_cu, s) : launch_rel_fmt<8, 1>(p, ntasks, fh, pube, wg_per_cu, s));
-    return p.cb == 4 ? launch_rel_fmt<4, 4>(p, ntasks, fh, pube, wg_per_cu, s)
-                     : (p.cb == 2 ? launch_rel_fmt<4, 2>(p, ntasks, fh, pube, wg_per_cu, s) : launch_rel_fmt<4, 1>(p, ntasks, fh, pube, wg_per_cu, s));
-}
-int pass_rel_lines() { return RR; }
 int pass_rel_phases() { return MGM_REL_PHASES ? 16 : 0; }
-// (one slab: a lane's worth of guard words + the values + another guard + the header's 4; fh2: + the forward and backward passes)
-// LDS bytes of a workgroup (launch_rel_one's request): with anti-diagonal passes a second hand ring -- the host asks before it plans them
-size_t pass_rel_lds_bytes(bool one_slab, int slots, int cb, bool fh2, bool diag)
-{
-    const size_t HS = (size_t)pass_rel_hand_floats(one_slab, slots, fh2);
-    return sizeof(float) * ((size_t)RR * RD4 * HS + (size_t)(diag ? 2 : 1) * SD * HS + 2 * SD * RR * 4) + (size_t)SD * RR * slots * cb + sizeof(unsigned) * (SD + 4) + 16 + sizeof(int) * RR * 24;
-}
-int pass_rel_hand_floats(bool one_slab, int slots, bool fh2) { return (fh2 ? 3 * slots + 2 * (slots / 16) : (one_slab ? slots + 2 * (slots / 16) : 2 * slots)) + 4; }
 
 }  // namespace mgm

@@ -85,8 +85,10 @@ static int cache_put(mgm_ctx *c, PlanCache<Req, Plan> &cache, const Req &req, Pl
     return MGM_OK;
 }
 
-static int plan_error(mgm_ctx *c, int err)
+// `launch`: the launch a plan without a kernel instance used to fail at (its message names the call as it always has)
+static int plan_error(mgm_ctx *c, int err, const char *launch)
 {
+    if (err == kPlanNoKernel) return hipfail(c, hipErrorInvalidValue, launch);
     if (err == kPlanNotCanonical) return fail(c, MGM_ERR_INTERNAL, "pass table does not reduce to canonical form");
     if (err == kPlanTooManyBands) return fail(c, MGM_ERR_UNSUPPORTED, "image side exceeds 65536 pixels");
     return fail(c, MGM_ERR_INTERNAL, "two-valued weights: the launch plan lost its queues");
@@ -95,23 +97,25 @@ static int plan_error(mgm_ctx *c, int err)
 // "this was the context's last aggregation": what mgm_wta_windowed_dev / mgm_debug_download_lr / the winner search of a later
 // call find (DenseRun, RelRun: mgm_host.h).  pad8: the padded compact copies of a padded launch (per volume), or nullptr;
 // minima: the launch wrote the chunk minima of its Lr volumes.
+// kernel: the instance that ran (nullptr: k_pass_exact)
 static void remember_dense(mgm_ctx *c, const mgm_cv *const *Cs, int nb, long long nvol, long long lr_stride, int nslots, int Lreal, int Lk, int pad_cb,
-                           const uint8_t *const *pad8, bool minima)
+                           const uint8_t *const *pad8, bool minima, const PassKernelChoice *kernel)
 {
     c->rel_last.clear();  // (an earlier range-proportional aggregation of the same volume is no longer the context's last)
     DenseRun &d = c->last;
     d = DenseRun{};
     d.nvol = nvol, d.stride = lr_stride, d.ndir = nslots, d.batch = nb, d.L = Lreal, d.Lk = Lk;
     d.wrote_min = minima;
+    if (kernel) d.kernel = *kernel;
     d.pad_c8 = pad8 != nullptr, d.pad_cb = pad_cb;
     for (int v = 0; v < nb; v++) d.pad_ptr[v] = pad8 ? pad8[v] : nullptr, d.cvs[v] = Cs[v], d.gens[v] = Cs[v]->gen;
 }
-static void remember_rel(mgm_ctx *c, const mgm_cv *const *Cs, int nb, int NDIR, long long stride)
+static void remember_rel(mgm_ctx *c, const mgm_cv *const *Cs, int nb, int NDIR, long long stride, const PassKernelChoice &kernel)
 {
     c->last.clear();  // (the dense Lr workspace no longer belongs to these volumes)
     RelRun &d = c->rel_last;
     d = RelRun{};
-    d.batch = nb, d.ndir = NDIR, d.stride = stride, d.slots = Cs[0]->rel_slots;
+    d.batch = nb, d.ndir = NDIR, d.stride = stride, d.slots = Cs[0]->rel_slots, d.kernel = kernel;
     for (int v = 0; v < nb; v++) d.cvs[v] = Cs[v], d.gens[v] = Cs[v]->gen;
 }
 
@@ -275,7 +279,7 @@ static int run_passes_exact(mgm_ctx *c, const mgm_cv *const *Cs, const mgm_img *
         TimeScope t(c, "k_pass_exact");
         HIPCHK(c, launch_pass_exact(p, c->stream));
     }
-    remember_dense(c, Cs, nb, nvol, lr_stride, nslots, L, L, 1, nullptr, false);
+    remember_dense(c, Cs, nb, nvol, lr_stride, nslots, L, L, 1, nullptr, false, nullptr);
     return MGM_OK;
 }
 
@@ -428,9 +432,13 @@ int run_passes(mgm_ctx *c, const mgm_cv *const *Cs, const mgm_img *const *w8s, i
     const bool show = tune_num("show_plan", 0) != 0;  // development aid: what the launch heuristics decided
     const auto *e = c->dense_plans.find(q);
     DensePlan fresh;
-    if (!e && (fresh = plan_dense(q)).err) return plan_error(c, fresh.err);
+    if (!e && (fresh = plan_dense(q)).err)
+        return plan_error(c, fresh.err, fresh.R2 ? "launch_pass2(p, ntasks, fh, w2 ? 2 : (wk ? 1 : 0), c->stream)" : "launch_pass(p, ntasks, R, fh, o.weighted ? 1 : 0, c->stream)");
     if (show) {
         const DensePlan &d = e ? e->plan : fresh;
+        char name[96];
+        pass_kernel_name(d.kernel, name, sizeof name);
+        fprintf(stderr, "[mgm plan] kernel %s\n", name);
         fprintf(stderr, "[mgm plan] %dx%dx%d passes %d..%d x %d volumes: load/chain %.2f, %d wg/cu, deep %d, subv %d, strips %d, xcd queues %d (block %d; xcc ids seen 0x%x)\n", nx, ny, L,
                 first, PEND - 1, nb, d.load_ratio, d.wg_per_cu, d.deep, d.subv, d.any_strips, d.xcdq, d.QK >= (1 << 20) ? 0 : d.QK, (unsigned)c->xcc_mask);
         if (!e)
@@ -440,7 +448,7 @@ int run_passes(mgm_ctx *c, const mgm_cv *const *Cs, const mgm_img *const *w8s, i
     if (!e && (r = cache_put(c, c->dense_plans, q, fresh, &e))) return r;
     if (show) fprintf(stderr, "[mgm plan] table: %d tasks, fnv1a %016llx\n", e->plan.ntasks, e->fnv);
     const DensePlan &plan = e->plan;
-    const int ntasks = plan.ntasks, subv = plan.subv, ngroups = plan.ngroups, Lk = plan.Lk, R2 = plan.R2, R = plan.R, LPk = plan.LPk, maxLL = plan.maxLL;
+    const int ntasks = plan.ntasks, subv = plan.subv, ngroups = plan.ngroups, Lk = plan.Lk, R2 = plan.R2, LPk = plan.LPk, maxLL = plan.maxLL;
     const bool w2 = plan.w2, wk = plan.wk, tags = plan.tags, xcdq = plan.xcdq;
 
     // 4. the workspace; the hand-off region, cleared or tagged
@@ -588,8 +596,8 @@ int run_passes(mgm_ctx *c, const mgm_cv *const *Cs, const mgm_img *const *w8s, i
     // 6. the launch
     {
         TimeScope t(c, R2 ? "k_pass2" : "k_pass");
-        if (R2) HIPCHK(c, launch_pass2(p, ntasks, fh, w2 ? 2 : (wk ? 1 : 0), c->stream));
-        else HIPCHK(c, launch_pass(p, ntasks, R, fh, o.weighted ? 1 : 0, c->stream));
+        if (R2) HIPCHK(c, launch_pass2(p, plan.kernel, ntasks, c->stream));
+        else HIPCHK(c, launch_pass(p, plan.kernel, ntasks, c->stream));
     }
     if (tags) {
         c->hand_key = plan.hand;  // enqueued: every slot of the region will carry this launch's tag
@@ -623,7 +631,7 @@ int run_passes(mgm_ctx *c, const mgm_cv *const *Cs, const mgm_img *const *w8s, i
     if (p.dbg && (r = print_pass_stats(c, p.dbg, (const int2 *)e->buf.p + 8, ntasks, first, PEND))) return r;
 
     // 7. what the context's last aggregation was: this dense one
-    remember_dense(c, Cs, nb, nvol, lr_stride, nslots, Lreal, L, o.cb, (o.padded && o.use_c8) ? pad8 : nullptr, minima);
+    remember_dense(c, Cs, nb, nvol, lr_stride, nslots, Lreal, L, o.cb, (o.padded && o.use_c8) ? pad8 : nullptr, minima, &plan.kernel);
     return MGM_OK;
 }
 
@@ -872,23 +880,28 @@ int run_rel(mgm_ctx *c, const mgm_cv *const *Cs, const mgm_img *const *w8s, int 
     // 2. the request
     RelRequest q{};
     q.nx = nx, q.ny = ny, q.NDIR = NDIR, q.nb = nb, q.MGM = MGM, q.fh = fh ? 1 : 0, q.pube = pube ? 1 : 0, q.fh2 = fh2 ? 1 : 0, q.slots = slots, q.cb = rcb;
-    q.R = pass_rel_lines(), q.HS = pass_rel_hand_floats(fh || pube, slots, fh2);
-    q.diag_fits = pass_rel_lds_bytes(fh || pube, slots, rcb, fh2, true) <= (size_t)160 * 1024 ? 1 : 0;
+    q.R = kRelLines, q.HS = rel_hand_floats(fh || pube, slots, fh2);
+    q.diag_fits = rel_lds_bytes(fh || pube, slots, rcb, fh2, true) <= kLdsBytes ? 1 : 0;
     q.num_cu = c->num_cu;
     q.rel_wg = (int)tune_num("rel_wg", 0), q.rel_prio = (int)tune_num("rel_prio", nb <= 1 ? 5 : 0), q.rel_lag = (int)tune_num("rel_lag", 0);
     q.rel_lagd = (int)tune_num("rel_lagd", 0), q.rel_slots = (int)tune_num("rel_slots", 100), q.rel_slope1 = (int)tune_num("rel_slope1", 1);
     q.rel_swap = (int)tune_num("rel_swap", 1), q.rel_diag = (int)tune_num("rel_diag", 1), q.rel_strips = (int)tune_num("rel_strips", 1);
+    q.rel_multi = tune_num("rel_multi", 1) != 0 ? 1 : 0;
 
     // 3. the plan: the simulated list schedule of the launch (one ticket counter), the context's if it has launched this request before
     const auto *e = c->rel_plans.find(q);
     if (!e) {
         RelPlan fresh = plan_rel(q);
-        if (fresh.err) return plan_error(c, fresh.err);
+        if (fresh.err) return plan_error(c, fresh.err, "launch_pass_rel(p, ntasks, fh, pube, rel_wg, c->stream)");
         if ((r = cache_put(c, c->rel_plans, q, fresh, &e))) return r;
     }
     const RelPlan &plan = e->plan;
     const int ntasks = plan.ntasks, rel_wg = plan.rel_wg;
-    if (tune_num("show_plan", 0)) fprintf(stderr, "[mgm plan] rel table: %d tasks, fnv1a %016llx\n", ntasks, e->fnv);
+    if (tune_num("show_plan", 0)) {
+        char name[96];
+        pass_kernel_name(plan.kernel, name, sizeof name);
+        fprintf(stderr, "[mgm plan] rel table: %d tasks, fnv1a %016llx, kernel %s\n", ntasks, e->fnv, name);
+    }
 
     // 4. the workspace; the hand-off region, cleared or tagged
     const long long stride = npix * slots + lr_pad_floats();
@@ -940,7 +953,7 @@ int run_rel(mgm_ctx *c, const mgm_cv *const *Cs, const mgm_img *const *w8s, int 
     p.P2 = P2;
     // the loader's lead: every step of it is a step of lag per band (round 5: 3 for batches; with the anti-diagonal passes 2 is as good there)
     p.ld = (int)std::min(5LL, std::max(2LL, tune_num("rel_ld", 2)));  // (2 against 3: x 2 7.76 / 7.81 ms, x 4 12.30 / 12.39)
-    p.fh_multi = tune_num("rel_multi", 1) != 0 ? 1 : 0;
+    p.fh_multi = q.rel_multi;
     p.cost2 = (pube && MGM == 2) ? 1 : 0;
     p.fh2 = fh2 ? 1 : 0;
     p.slots = slots;
@@ -959,7 +972,7 @@ int run_rel(mgm_ctx *c, const mgm_cv *const *Cs, const mgm_img *const *w8s, int 
     // 6. the launch
     {
         TimeScope t(c, "k_pass_rel");
-        HIPCHK(c, launch_pass_rel(p, ntasks, fh, pube, rel_wg, c->stream));
+        HIPCHK(c, launch_pass_rel(p, plan.kernel, ntasks, c->stream));
     }
     c->hand_rel_key = plan.hand;  // enqueued: every slot of the region will carry this launch's tag
     HIPCHK(c, hipMemcpyAsync(c->h_words + 1, words + 1, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
@@ -972,7 +985,7 @@ int run_rel(mgm_ctx *c, const mgm_cv *const *Cs, const mgm_img *const *w8s, int 
     }
 
     // 7. what the context's last aggregation was: this one; and the winner search on it
-    remember_rel(c, Cs, nb, NDIR, stride);
+    remember_rel(c, Cs, nb, NDIR, stride, plan.kernel);
     for (int v = 0; v < nb; v++) {
         float *Sout = nullptr;
         if (S) {

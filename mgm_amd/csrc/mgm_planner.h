@@ -9,6 +9,7 @@
 // that ASK for the facts of the device they need, one at a time); tests/test_route_plan.py.
 #pragma once
 #include <algorithm>
+#include <cstdio>
 #include <cstring>
 #include <functional>
 #include <type_traits>
@@ -101,11 +102,12 @@ struct RelRequest {
     int nx, ny, NDIR, nb, MGM;
     int fh, pube, fh2;         // FH potentials; the producer publishes E; update_cost2_trunclinear
     int slots, cb;             // the volumes' range-proportional format
-    int R, HS;                 // lines per band, floats per hand-off slot (pass_rel_lines, pass_rel_hand_floats)
-    int diag_fits;             // a workgroup with the second hand ring of the anti-diagonal passes fits the LDS (pass_rel_lds_bytes)
+    int R, HS;                 // lines per band, floats per hand-off slot (kRelLines, rel_hand_floats)
+    int diag_fits;             // a workgroup with the second hand ring of the anti-diagonal passes fits the LDS (rel_lds_bytes)
     int num_cu;
     // tune values: rel_wg 0 = by the launch's shape; rel_prio as resolved by the caller (default 5 for one volume, else 0)
-    int rel_wg, rel_prio, rel_lag, rel_lagd, rel_slots, rel_slope1, rel_swap, rel_diag, rel_strips;
+    // rel_multi 0: FH on 64 slots of one-byte costs runs the one-after-the-other build (an A/B switch)
+    int rel_wg, rel_prio, rel_lag, rel_lagd, rel_slots, rel_slope1, rel_swap, rel_diag, rel_strips, rel_multi;
 };
 static_assert(std::has_unique_object_representations_v<DenseRequest>, "DenseRequest: integers only, no padding (compared bytewise)");
 static_assert(std::has_unique_object_representations_v<RelRequest>, "RelRequest: integers only, no padding (compared bytewise)");
@@ -313,10 +315,72 @@ inline bool plan_wta_prune(const PruneRequest &q)
     return q.enabled != 0 && kernel_writes && search_reads && q.stride_mod32 == 0;
 }
 
+// ---- which instance of a pass kernel a launch runs ---------------------------------------------------------------------------
+// Decided by plan_dense / plan_rel from their own request and decisions; the launchers (mgm_pass.hip, mgm_pass2.hip,
+// mgm_pass_rel.hip) are tables from a choice to its instance.  tests/test_pass_kernel_plan.py holds the planner against a
+// restatement of the launchers it replaced.
+enum PassFamily { kPassRefuse = 0, kPassFirst, kPassSecond, kPassRel };
+struct PassKernelChoice {
+    int family;  // kPassRefuse: no instance serves the launch (the plan's err is kPlanNoKernel)
+    // the instance's template arguments: k_pass<LPL, FH, WEIGHTED, R>, k_pass2<LPL, FH, WEIGHTED, MGM, C8, SUBV, DEEP, XCDQ, ONEB, W2>
+    // (C8: bytes per compact cost, 0 = fp32 costs), k_pass_rel<FH, PUBE, NK, SPL, CB, FH2>; those an instance does not have are 0
+    int LPL, FH, WEIGHTED, R, MGM, C8, SUBV, DEEP, XCDQ, ONEB, W2, PUBE, NK, SPL, CB, FH2;
+    // dynamic LDS bytes of the launch (the second build: the FLOOR of the request -- what the instance itself needs depends on
+    // the build's macros and stays in mgm_pass2.hip); threads per workgroup (the first build only)
+    int lds, block;
+};
+static_assert(std::has_unique_object_representations_v<PassKernelChoice>, "PassKernelChoice: integers only, no padding");
+
+// The instances that are built, family by family: the planner refuses what these deny, the launchers instantiate exactly what
+// they admit.  `dev`: a development build of the second build (-DMGM_P2_DEV=1), which has no queue and no W2 instances -- with the
+// timers compiled in, the compiler fails on some of them ("Operand has incorrect register class", V_CMP_NE_U32 on src_shared_base).
+constexpr bool pass_instance(int LPL, int R) { return R == 4 ? (LPL == 12 || LPL == 16 || LPL == 24 || LPL == 32) : (R == kR && (LPL == 1 || LPL == 2 || LPL == 3 || LPL == 4 || LPL == 6 || LPL == 8)); }
+constexpr bool pass2_instance(bool dev, int LPL, bool FH, bool WEIGHTED, int MGM, int C8, int SUBV, bool DEEP, bool XCDQ, bool ONEB, bool W2)
+{
+    if (!(LPL == 1 || LPL == 2 || LPL == 3 || LPL == 4 || LPL == 6 || LPL == 8 || LPL == 12 || LPL == 16) || MGM < 1 || MGM > 4) return false;
+    const bool slabs_of_E = !WEIGHTED && !(FH && MGM == 2);  // the unweighted kernels whose slabs do not travel with their minimum
+    // two-valued weights: the compact kernels with deep rings and per-XCD queues, one band per CU, up to 256 labels
+    if (W2) return !dev && LPL <= 4 && !WEIGHTED && C8 == 1 && SUBV == 1 && DEEP && XCDQ && ONEB;
+    if (WEIGHTED && LPL >= 12) return false;  // (768 / 1024 labels: the weighted kernels' rings do not fit the LDS; first build)
+    // several volumes per wave (128 / 64 labels): no queues (no gain measured there: cfg2 x 4..16, cfg5 x 4..16 within noise)
+    if (SUBV != 1) return (SUBV == 2 || SUBV == 4) && LPL == 4 && slabs_of_E && C8 == 1 && !XCDQ && !ONEB;
+    if (ONEB && !XCDQ) return false;
+    if (XCDQ && (dev || !DEEP)) return false;
+    if (DEEP) return slabs_of_E && (C8 == 1 || (C8 == 2 && LPL <= 8));  // deep DMA rings: compact costs
+    return C8 == 0 || C8 == 1;  // (two bytes per cost, round 4: the kernels with deep rings only)
+}
+constexpr bool pass_rel_instance(bool FH, bool PUBE, int NK, int SPL, int CB, bool FH2)
+{
+    if (!(SPL == 4 || SPL == 8) || !(CB == 1 || CB == 2 || CB == 4)) return false;
+    if (!FH) return NK == 0 && !FH2;
+    if (PUBE) return false;
+    // update_cost2_trunclinear: on 128 slots of fp32 costs its rings + the cost pieces exceed the LDS (plan_agg_route keeps that one on the dense hull)
+    if (FH2) return NK == 2 && !(SPL == 8 && CB == 4);
+    // (NK 0: the one-after-the-other build, kept for the form round 5 measured, as an A/B switch -- tune rel_multi=0)
+    return NK == 0 ? (SPL == 4 && CB == 1) : (NK >= 1 && NK <= 4);
+}
+inline bool pass_instance_exists(const PassKernelChoice &k, bool dev)
+{
+    if (k.family == kPassFirst) return pass_instance(k.LPL, k.R);
+    if (k.family == kPassSecond) return pass2_instance(dev, k.LPL, k.FH, k.WEIGHTED, k.MGM, k.C8, k.SUBV, k.DEEP, k.XCDQ, k.ONEB, k.W2);
+    return k.family == kPassRel && pass_rel_instance(k.FH, k.PUBE, k.NK, k.SPL, k.CB, k.FH2);
+}
+// the instance as a kernel trace prints it, e.g. "k_pass2<4, true, false, 2, 1, 1, true, true, true, false>"; returns strlen
+inline int pass_kernel_name(const PassKernelChoice &k, char *buf, size_t cap)
+{
+    auto b = [](int v) { return v ? "true" : "false"; };
+    if (k.family == kPassFirst) return snprintf(buf, cap, "k_pass<%d, %s, %s, %d>", k.LPL, b(k.FH), b(k.WEIGHTED), k.R);
+    if (k.family == kPassSecond)
+        return snprintf(buf, cap, "k_pass2<%d, %s, %s, %d, %d, %d, %s, %s, %s, %s>", k.LPL, b(k.FH), b(k.WEIGHTED), k.MGM, k.C8, k.SUBV, b(k.DEEP), b(k.XCDQ), b(k.ONEB), b(k.W2));
+    if (k.family == kPassRel) return snprintf(buf, cap, "k_pass_rel<%s, %s, %d, %d, %d, %s>", b(k.FH), b(k.PUBE), k.NK, k.SPL, k.CB, b(k.FH2));
+    return snprintf(buf, cap, "refused");
+}
+
 // ---- the dense kernels (k_pass / k_pass2) --------------------------------------------------------------------------------
-enum { kPlanOk = 0, kPlanNotCanonical = 1, kPlanTooManyBands = 2, kPlanLostQueues = 3 };
+enum { kPlanOk = 0, kPlanNotCanonical = 1, kPlanTooManyBands = 2, kPlanLostQueues = 3, kPlanNoKernel = 4 };
 struct DensePlan {
     int err = kPlanOk;
+    PassKernelChoice kernel = {};       // the instance the launch runs (err kPlanNoKernel: none does)
     // the decisions
     int subv = 1, ngroups = 0, Lk = 0;  // volumes per wave, volume groups, label slots of a wave
     int R2 = 0, R = 0;                  // lines per band of the second build (0: the first build runs), of the launch
@@ -483,6 +547,23 @@ inline DensePlan plan_dense(const DenseRequest &q)
     }
     p.xcdq = xcdq;
     p.oneb = (xcdq && p.wg_per_cu < 2 && q.oneb) ? 1 : 0;
+    // The instance: what was decided above, as template arguments.  A combination nothing is built for ends here (a switch that
+    // takes the deep rings from two-byte costs, a label count without an object of the second build) instead of at the launch.
+    PassKernelChoice &kn = p.kernel;
+    kn.LPL = R2 ? (subv > 1 ? 4 : (L % 64 ? 0 : L / 64)) : lpl, kn.FH = fh, kn.WEIGHTED = R2 ? wk : weighted;
+    if (R2) {
+        kn.family = kPassSecond, kn.MGM = MGM, kn.C8 = use_c8 ? (q.cb == 2 ? 2 : 1) : 0, kn.SUBV = subv, kn.DEEP = p.deep, kn.XCDQ = xcdq, kn.W2 = w2;
+        kn.ONEB = w2 ? 1 : p.oneb;  // (the W2 kernels exist as one-band builds only: MGM_HIP_ONEB=0 does not reach them)
+        // Occupancy is chosen per launch through the LDS request: the compact unweighted kernels are built for two
+        // workgroups per CU (<= 64 VGPRs, < 80 KB of LDS).  Two bands per CU hide each other's barrier and LDS stalls --
+        // right when the launch is throughput-bound (a batch of volumes); a single volume is bound by the chain of
+        // bands, where the doubled step latency costs more than it gives, so it asks for > half the LDS and runs alone.
+        kn.lds = p.wg_per_cu < 2 ? 81 * 1024 : 0;
+    } else {
+        kn.family = kPassFirst, kn.R = R;
+        kn.lds = (int)sizeof(float) * (R * 2 * ((weighted && !fh) ? 2 : 1) * LP + R * 2) + 16, kn.block = R * 64;  // (two slabs per slot: weighted Hirschmueller)
+    }
+    if (!pass_instance_exists(kn, q.devtools != 0)) return kn = PassKernelChoice{}, p.err = kPlanNoKernel, p;
     // Two strips per line: the passes without an in-line dependency -- form 1 with 2 or 3 neighbours -- walk their lines
     // from both image edges inwards (mgm_pass2.hip): half the line length in the critical path of a pass, bands that
     // live half as long, for twice the work items, each with its own pipeline ramp and hand-off lag (and 1-2 % of the
@@ -580,6 +661,7 @@ inline DensePlan plan_dense(const DenseRequest &q)
 // ---- the range-proportional kernels (k_pass_rel) -------------------------------------------------------------------------
 struct RelPlan {
     int err = kPlanOk;
+    PassKernelChoice kernel = {};  // the instance the launch runs (err kPlanNoKernel: none does)
     int rel_wg = 1;    // workgroups (4 compute waves + the loader) per CU
     int diag_any = 0;  // some pass walks anti-diagonals
     int swapmask = 0;  // the passes walked with exchanged roles
@@ -647,6 +729,11 @@ inline RelPlan plan_rel(const RelRequest &q)
     }
     p.maxLL = maxLL;
     if (maxbands > kMaxBands) return p.err = kPlanTooManyBands, p;
+    // the instance: the volumes' format, the potentials, how many of a pixel's min-convolutions run side by side
+    PassKernelChoice &kn = p.kernel;
+    kn.family = kPassRel, kn.FH = fh, kn.PUBE = !fh && q.pube, kn.SPL = q.slots == 128 ? 8 : 4, kn.CB = q.cb == 4 ? 4 : (q.cb == 2 ? 2 : 1);
+    if (fh && !(kn.SPL == 4 && kn.CB == 1 && !q.rel_multi)) kn.FH2 = q.fh2 != 0, kn.NK = kn.FH2 ? 2 : (MGM >= 1 && MGM <= 3 ? MGM : 4);
+    if (!pass_instance_exists(kn, false)) return kn = PassKernelChoice{}, p.err = kPlanNoKernel, p;
     // self-validating hand-off slots, one per (volume, pass, band, pixel): written once per launch with the launch's tag (see
     // k_pass_rel); another geometry clears the region (all-ones words) and starts again with tag 0
     p.hand = lay_out_hand(p.g, NDIR, nx, ny, nb, q.HS, q.slots, R);
@@ -657,6 +744,9 @@ inline RelPlan plan_rel(const RelRequest &q)
     // (with the anti-diagonal passes a single launch is no longer one long chain: x 1 6.89 / 6.32 / 6.47 ms at 1 / 2 / 3, x 2 11.5 / 7.82 / 7.76,
     // x 4 22.0 / 13.0 / 12.3; Hirschmueller x 1 5.45 / 4.62 / 4.36)
     const int rel_wg = p.rel_wg = q.rel_wg > 0 ? std::min(q.rel_wg, 6) : (nb <= 1 ? (fh ? 2 : 3) : 3);
+    // Occupancy through the LDS request, as for the second build: rel_wg workgroups (of 4 compute waves: one per SIMD) share a
+    // CU -- one for a launch bound by its chains of bands, more for a batch (throughput): more than a (rel_wg + 1)-th of the LDS
+    kn.lds = (int)std::max(rel_lds_bytes(kn.FH || kn.PUBE, 16 * kn.SPL, kn.CB, kn.FH2 != 0, p.diag_any != 0), (long long)kLdsBytes / (rel_wg + 1) + 1024);
     // the task table: the simulated list schedule of the launch (one ticket counter)
     // (slope of the lock-step diagonal x lines + the lag the MODEL assumes per band.  The tickets are the start order of the
     // simulated schedule, so these constants decide who holds a band slot while it waits: with the hand-off's real ~4 steps on

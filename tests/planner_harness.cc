@@ -22,7 +22,7 @@ RelRequest rel_request(const int *a)
     q.nx = a[0], q.ny = a[1], q.NDIR = a[2], q.nb = a[3], q.MGM = a[4], q.fh = a[5], q.pube = a[6], q.fh2 = a[7], q.slots = a[8], q.cb = a[9];
     q.R = a[10], q.HS = a[11], q.diag_fits = a[12], q.num_cu = a[13];
     q.rel_wg = a[14], q.rel_prio = a[15], q.rel_lag = a[16], q.rel_lagd = a[17], q.rel_slots = a[18], q.rel_slope1 = a[19], q.rel_swap = a[20], q.rel_diag = a[21],
-    q.rel_strips = a[22];
+    q.rel_strips = a[22], q.rel_multi = a[23];
     return q;
 }
 

@@ -26,7 +26,7 @@ CAP = 1 << 18  # tasks of the largest launch below: 16 volumes x 8 passes of 409
 DENSE_FIELDS = ("nx ny L nb first count layout_ndir MGM fh wmode use_c8 cb first_build ragged lines2 lpl ns devtools num_cu xcc_mask "
                 "subv deep wg_per_cu strips xcdq xcdq_k one_queue w2 oneb").split()
 REL_FIELDS = ("nx ny NDIR nb MGM fh pube fh2 slots cb R HS diag_fits num_cu rel_wg rel_prio rel_lag rel_lagd rel_slots rel_slope1 rel_swap "
-              "rel_diag rel_strips").split()
+              "rel_diag rel_strips rel_multi").split()
 DENSE_SCAL = ("err subv ngroups Lk R2 R w2 wk tags NS LPk wg_per_cu deep oneb xcdq nq QK one_queue any_strips maxLL ntasks hand_vstride "
               "h_npass h_groups h_slot_floats h_slots h_R").split()
 REL_SCAL = "err rel_wg diag_any swapmask maxLL ntasks hand_vstride h_npass h_groups h_slot_floats h_slots h_R".split()
@@ -83,14 +83,14 @@ def dense_request(lib, nx, ny, L, nb=1, first=0, count=8, layout_ndir=None, MGM=
 
 
 def rel_request(nx, ny, NDIR=8, nb=1, MGM=3, fh=1, weighted=0, slots=64, cb=1, diag_fits=1, num_cu=256, rel_wg=0, rel_prio=None, rel_lag=0,
-                rel_lagd=0, rel_slots=100, rel_slope1=1, rel_swap=1, rel_diag=1, rel_strips=1):
+                rel_lagd=0, rel_slots=100, rel_slope1=1, rel_swap=1, rel_diag=1, rel_strips=1, rel_multi=1):
     pube = int(not fh and not weighted)
     fh2 = int(bool(fh) and MGM == 2 and not weighted)
     one_slab = bool(fh or pube)
     HS = (3 * slots + 2 * (slots // 16) if fh2 else (slots + 2 * (slots // 16) if one_slab else 2 * slots)) + 4
     return dict(nx=nx, ny=ny, NDIR=NDIR, nb=nb, MGM=MGM, fh=fh, pube=pube, fh2=fh2, slots=slots, cb=cb, R=16, HS=HS, diag_fits=diag_fits,
                 num_cu=num_cu, rel_wg=rel_wg, rel_prio=(5 if nb <= 1 else 0) if rel_prio is None else rel_prio, rel_lag=rel_lag, rel_lagd=rel_lagd,
-                rel_slots=rel_slots, rel_slope1=rel_slope1, rel_swap=rel_swap, rel_diag=rel_diag, rel_strips=rel_strips)
+                rel_slots=rel_slots, rel_slope1=rel_slope1, rel_swap=rel_swap, rel_diag=rel_diag, rel_strips=rel_strips, rel_multi=rel_multi)
 
 
 class Plan:
