@@ -817,6 +817,8 @@ inline WtaChoice plan_wta(const WtaRequest &q)
     if (c.prune) {
         // (what k_wta_pruned is built for, checked where it is launched from: 256 labels, no padding, one-byte compact costs, ...)
         if (q.Lreal != 256 || q.nvol_mod32 != 0) return c;
+        // pw: k_wta_pruned's PPW, groups of eight pixels per wave and turn (a wave takes 8 * pw pixels, so the grid below holds up
+        // to eight times the waves the pixels need: the kernel maps pixels onto whatever grid it is given, the rest end at once)
         const int pw = (q.sw_prune_ppw == 1 || (q.NDIR != 4 && q.NDIR != 8)) ? 1 : 2;
         c.grid = std::min((q.npix + 4 * pw - 1) / (4 * pw), cus * (q.sw_prune_wg > 0 ? q.sw_prune_wg : 64));
         c.family = kWtaPruned, c.PPW = pw, c.MAXD = maxd, c.ALLD = (q.NDIR == 4 || q.NDIR == 8) ? 1 : 0;

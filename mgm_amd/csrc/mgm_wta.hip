@@ -401,194 +401,261 @@ __global__ void __launch_bounds__(256) k_wta_any(const WtaParams P)
 //     LB(d) = sum_fix(m_0(chunk(d)), ..., m_{N-1}(chunk(d)); C(d)) <= sum_fix(L_0(d), ..., L_{N-1}(d); C(d)) = S(d)
 // bit for bit, no epsilon -- as long as both sides are evaluated by the same operations in the same order (sum_fix, below).  The
 // winner needs the exact S only where it can lie:
-//   (a) costs + N*8 minima of the pixel -> LB of every label; a label with C = +INF is out (its S is never finite);
+//   (a) costs + N*8 minima of the pixel -> LB of every chunk: the smallest LB over its labels with a finite cost (a label with
+//       C = +INF is out, its S is never finite).  s - f*c with f = NDIR-1 >= 0 does not rise with c under fp32 rounding, so that is
+//       sum_fix of the minima at the chunk's LARGEST finite cost -- one evaluation per chunk (CPU: tests/test_wta_groups.py);
 //   (b) the chunk with the smallest LB (the lowest one on ties) loads its Lr pieces: best0 = its smallest finite S (+INF: none);
-//   (c) every other chunk with some LB <= best0 loads too, in one round -- best0 can only fall, and `<=` keeps a tie at a lower
-//       label in play; a chunk that stays out has S >= LB > best0 on all its labels;
-//   (d) first strict minimum among the finite S of what was loaded, by rising label; vfit reads S at the winner's neighbours,
-//       from the staged chunks or -- the neighbour lies in a chunk that stayed out -- recomputed from memory;
+//   (c) every other chunk with LB <= best0 loads too -- the set is fixed here, `<=` keeps a tie at a lower label in play; a chunk
+//       that stays out has S >= LB > best0 on all its labels;
+//   (d) first strict minimum among the finite S of what was loaded = the smallest (S, label); vfit recomputes S at the winner
+//       and its two neighbours from memory (lines just read, but for a neighbour in a chunk that stayed out);
 //   (e) nothing finite: NaN label, +INF cost, as in k_wta.
 // On census volumes 1.8-2 of the 8 chunks of a pixel are loaded: 2.4 KB per pixel instead of 8.4.
-template <int MAXD>
-__device__ __forceinline__ void sum_fix(const float (&l)[MAXD][4], const float (&c)[4], int ndir, int fix, float (&S)[4])
+//
+// The layout: a pixel is a GROUP of eight lanes, a wave works on eight consecutive pixels at once (two per DPP row of 16 lanes).
+// Lane (g, j) = (lane >> 3, lane & 7) OWNS chunk j of pixel g in (a): its 32 cost bytes, its minimum of every pass, its bound.
+// In (b) and (c) the group's eight lanes read ONE chunk together, lane j the four labels 4j.. of it: a 128-byte line per pass
+// and group.  (c) is a wave-uniform loop, every group taking its lowest remaining candidate per round; a group with none
+// left sits the round out under the exec mask.  All reductions are three DPP steps inside the group.
+template <int MAXD, int K>
+__device__ __forceinline__ void sum_fix(const float (&l)[MAXD][K], const float (&c)[K], int ndir, int fix, float (&S)[K])
 {
     // S = ((0 + L0) + L1) + ... in pass order, then the over-count term (mgm_core.cc:582-599): k_wta's operations, in its order
 #pragma unroll
-    for (int k = 0; k < 4; k++) S[k] = 0.0f;
+    for (int k = 0; k < K; k++) S[k] = 0.0f;
 #pragma unroll
     for (int p = 0; p < MAXD; p++)
         if (p < ndir) {
 #pragma unroll
-            for (int k = 0; k < 4; k++) S[k] = S[k] + l[p][k];
+            for (int k = 0; k < K; k++) S[k] = S[k] + l[p][k];
         }
     if (fix == 1) {
         const float f = (float)(ndir - 1);
 #pragma unroll
-        for (int k = 0; k < 4; k++) S[k] = S[k] - f * c[k];
+        for (int k = 0; k < K; k++) S[k] = S[k] - f * c[k];
     }
 }
 template <int CTRL>
-__device__ __forceinline__ float dpp_fmin(float v)  // min with the lane CTRL names (every lane has one)
+__device__ __forceinline__ float dpp_f(float v)  // v of the lane CTRL names (every lane has one)
 {
-    return __builtin_fminf(v, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, false)));
+    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, false));
 }
-// PPW: pixels per wave and iteration (their loads go out together).  MAXD: upper bound of NDIR; ALLD: NDIR == MAXD, known at
-// compile time (4 and 8 directions: no test per pass around the loads).
-template <int PPW, int MAXD, bool ALLD>
-__global__ void __launch_bounds__(256) k_wta_pruned(const WtaParams P)
+template <int CTRL>
+__device__ __forceinline__ float dpp_fmin(float v)  // min with the lane CTRL names
 {
+    return __builtin_fminf(v, dpp_f<CTRL>(v));
+}
+// over the eight lanes of a group: quad_perm [1,0,3,2], quad_perm [2,3,0,1], row_half_mirror
+__device__ __forceinline__ float group_fmin(float v)
+{
+    v = dpp_fmin<0xB1>(v);
+    v = dpp_fmin<0x4E>(v);
+    return dpp_fmin<0x141>(v);
+}
+template <int CTRL>
+__device__ __forceinline__ void dpp_take(float &best, int &bi)  // the smaller (S, label) of this lane's and that of the lane CTRL names
+{
+    const float ov = dpp_f<CTRL>(best);
+    const int oi = __builtin_amdgcn_update_dpp(0, bi, CTRL, 0xf, 0xf, false);
+    if (ov < best || (ov == best && oi < bi)) {
+        best = ov;
+        bi = oi;
+    }
+}
+// PPW: groups of eight pixels per wave and iteration (their loads go out together): a wave takes 8 * PPW consecutive pixels per turn
+// of its grid-stride loop.  ND: the number of passes, a compile-time constant (no test per pass around the loads).
+template <int PPW, int ND>
+__device__ __forceinline__ void wta_pruned(const WtaParams &P)
+{
+    constexpr int MAXD = ND;
     constexpr int L = 256;
-    __shared__ float sS[4][PPW][L];
+    constexpr int NONE = 0x7fffffff;
     const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int ch = lane >> 3;   // this lane's chunk
-    const int o0 = lane * 4;    // its first label
-    const int ndir = ALLD ? MAXD : P.NDIR, fix = P.FIX;
+    const int j = lane & 7;      // the chunk this lane owns in (a); its four labels 4j.. of the chunk its group reads in (b), (c)
+    const int gsh = lane & ~7;   // first lane of its group: where the group's byte of a ballot starts
+    const int ndir = ND, fix = P.FIX;
     const long long mstride = P.nvol / 32;  // chunk minima per pass
     unsigned nloaded = 0, npx = 0;          // (mgm_debug_wta_stats) of this wave
-    for (long long g0 = ((long long)blockIdx.x * 4 + wv) * PPW; g0 < P.npix; g0 += (long long)gridDim.x * 4 * PPW) {
-        // (a) costs and minima
-        unsigned cw[PPW];
+    for (long long g0 = ((long long)blockIdx.x * 4 + wv) * (8 * PPW); g0 < P.npix; g0 += (long long)gridDim.x * 4 * 8 * PPW) {
+        long long pix[PPW];
+        bool own[PPW];  // the group's pixel exists (the groups past the last pixel repeat it and write nothing)
+        // (a) the chunk's costs and minima
+        uint4 cq[PPW][2];
         float mn[PPW][MAXD];
 #pragma unroll
         for (int u = 0; u < PPW; u++) {
-            const long long pix = g0 + u < P.npix ? g0 + u : P.npix - 1;
-            cw[u] = *reinterpret_cast<const unsigned *>(P.C8 + pix * L + o0);
+            const long long q = g0 + 8 * u + (lane >> 3);
+            own[u] = q < P.npix;
+            pix[u] = own[u] ? q : P.npix - 1;
+            const uint4 *cp = reinterpret_cast<const uint4 *>(P.C8 + pix[u] * L + j * 32);
+            cq[u][0] = cp[0], cq[u][1] = cp[1];
 #pragma unroll
             for (int p = 0; p < MAXD; p++)
-                if (p < ndir) mn[u][p] = P.Lmin[(long long)p * mstride + pix * (L / 32) + ch];
+                if (p < ndir) mn[u][p] = P.Lmin[(long long)p * mstride + pix[u] * (L / 32) + j];
         }
-        float c[PPW][4], clb[PPW];
+        float clb[PPW];
         int seed[PPW];  // the seed chunk, -1: no label can hold a finite S
 #pragma unroll
         for (int u = 0; u < PPW; u++) {
-            float lm[MAXD][4], LB[4];
+            const unsigned w[8] = {cq[u][0].x, cq[u][0].y, cq[u][0].z, cq[u][0].w, cq[u][1].x, cq[u][1].y, cq[u][1].z, cq[u][1].w};
+            unsigned m = 0;  // the chunk's largest finite cost + 1, 0: none
 #pragma unroll
-            for (int k = 0; k < 4; k++) c[u][k] = c8_decode((cw[u] >> (8 * k)) & 255u);
+            for (int i = 0; i < 8; i++)
 #pragma unroll
-            for (int p = 0; p < MAXD; p++)
+                for (int k = 0; k < 4; k++) m = max(m, (((w[i] >> (8 * k)) & 255u) + 1u) & 255u);  // (255, +INF, wraps to 0)
+            float lm[MAXD][1], LB[1];
+            const float cm[1] = {(float)((int)m - 1)};
 #pragma unroll
-                for (int k = 0; k < 4; k++) lm[p][k] = p < ndir ? mn[u][p] : 0.0f;
-            sum_fix<MAXD>(lm, c[u], ndir, fix, LB);
-            float lb = f_inf();
-#pragma unroll
-            for (int k = 0; k < 4; k++) lb = c[u][k] < f_inf() ? __builtin_fminf(lb, LB[k]) : lb;
-            lb = lb == lb ? lb : -f_inf();  // (never taken: fminf above returns its other operand, so a NaN bound drops out -- S is NaN on that label too)
-            lb = dpp_fmin<0xB1>(lb);   // quad_perm [1,0,3,2]
-            lb = dpp_fmin<0x4E>(lb);   // quad_perm [2,3,0,1]
-            lb = dpp_fmin<0x141>(lb);  // row_half_mirror: all eight lanes hold the chunk's smallest bound
+            for (int p = 0; p < MAXD; p++) lm[p][0] = p < ndir ? mn[u][p] : 0.0f;
+            sum_fix<MAXD>(lm, cm, ndir, fix, LB);
+            const float lb = (m != 0u && LB[0] == LB[0]) ? LB[0] : f_inf();  // (a NaN bound drops out: S is NaN on those labels too)
             clb[u] = lb;
-            const float gmin = wave_min(lb);
-            const unsigned long long at = __builtin_amdgcn_ballot_w64(lb == gmin);
-            seed[u] = gmin < f_inf() ? (int)(__builtin_ctzll(at) >> 3) : -1;
+            const float gmin = group_fmin(lb);
+            const unsigned at = (unsigned)(__builtin_amdgcn_ballot_w64(lb == gmin) >> gsh) & 255u;  // (never 0: gmin is one of them)
+            seed[u] = gmin < f_inf() ? __builtin_ctz(at | 256u) : -1;
         }
-        // (b) the seed chunks.  No lane sits a load out: the lanes of the other chunks fetch the seed chunk's pieces as well (the
-        // same 128 bytes eight times over: one line from memory) and drop them -- straight-line code, no exec-masked branches
-        // around the loads, so the requests of all passes (and pixels) go out back to back
-        float S[PPW][4];
-        bool act[PPW];
-        float best0[PPW];
-        {
+        // The group's eight lanes read chunk ck[u] of their pixel, lane j its labels 4j..: a 128-byte line per pass, the requests of all
+        // passes (and pixels) back to back; S of those four labels.  (Loaded and consumed in one block: what a lane would carry
+        // across a branch it sat out stays live for the whole loop.)
+        auto chunk_S = [&](const int (&ck)[PPW], float (&S)[PPW][4]) {
             float l[PPW][MAXD][4];
+            unsigned cw[PPW];
 #pragma unroll
             for (int u = 0; u < PPW; u++) {
-                const long long pix = g0 + u < P.npix ? g0 + u : P.npix - 1;
-                act[u] = ch == seed[u];
-                const float *q0 = P.Lr + pix * L + (seed[u] > 0 ? seed[u] : 0) * 32 + (lane & 7) * 4;
+                const long long at = pix[u] * L + ck[u] * 32 + j * 4;
+                cw[u] = *reinterpret_cast<const unsigned *>(P.C8 + at);
 #pragma unroll
                 for (int p = 0; p < MAXD; p++)
                     if (p < ndir) {
-                        const float4 q = *reinterpret_cast<const float4 *>(q0 + (long long)p * P.nvol);
+                        const float4 q = *reinterpret_cast<const float4 *>(P.Lr + (long long)p * P.nvol + at);
                         l[u][p][0] = q.x, l[u][p][1] = q.y, l[u][p][2] = q.z, l[u][p][3] = q.w;
                     }
             }
 #pragma unroll
             for (int u = 0; u < PPW; u++) {
-                sum_fix<MAXD>(l[u], c[u], ndir, fix, S[u]);  // (means something in the seed chunk's lanes only)
-                float b = f_inf();
+                float c[4];
 #pragma unroll
-                for (int k = 0; k < 4; k++) b = (act[u] && finite_bits(S[u][k]) && S[u][k] < b) ? S[u][k] : b;
-                best0[u] = wave_min(b);
+                for (int k = 0; k < 4; k++) c[k] = c8_decode((cw[u] >> (8 * k)) & 255u);
+                sum_fix<MAXD>(l[u], c, ndir, fix, S[u]);
+            }
+        };
+        // (b) the seed chunks
+        float best[PPW];
+        int bi[PPW], sck[PPW];
+        unsigned cand[PPW];  // the chunks (c) still has to load, a bit each
+        {
+            float S[PPW][4];
+#pragma unroll
+            for (int u = 0; u < PPW; u++) sck[u] = seed[u] > 0 ? seed[u] : 0;
+            chunk_S(sck, S);
+#pragma unroll
+            for (int u = 0; u < PPW; u++) {
+                best[u] = f_inf();
+                bi[u] = NONE;
+                if (seed[u] >= 0) {
+#pragma unroll
+                    for (int k = 0; k < 4; k++)
+                        if (finite_bits(S[u][k]) && best[u] > S[u][k]) {
+                            best[u] = S[u][k];
+                            bi[u] = seed[u] * 32 + j * 4 + k;
+                        }
+                }
+                const float best0 = group_fmin(best[u]);
+                // (c)'s set, fixed here: lane (g, j) speaks for chunk j of its pixel
+                const bool cd = seed[u] >= 0 && j != seed[u] && clb[u] <= best0;
+                const unsigned long long cdm = __builtin_amdgcn_ballot_w64(cd);
+                cand[u] = (unsigned)(cdm >> gsh) & 255u;
+                const unsigned long long ownm = __builtin_amdgcn_ballot_w64(own[u]);
+                nloaded += (unsigned)__builtin_popcountll(cdm & ownm) + (unsigned)__builtin_popcountll(__builtin_amdgcn_ballot_w64(own[u] && j == seed[u]));
+                npx += (unsigned)__builtin_popcountll(ownm) >> 3;
             }
         }
-        // (c) every other chunk that can still hold the winner loads its own pieces; the rest fetch the seed chunk's again (cached)
-        bool act2[PPW];
-        {
-            float l[PPW][MAXD][4];
+        // (c) while any group has a candidate left: every group loads its lowest one; a group without any sits the round out under
+        // the exec mask (with several pixels per group of lanes: one whose other pixel still has some reads its seed's line again)
+        for (;;) {
+            bool more = false;
 #pragma unroll
-            for (int u = 0; u < PPW; u++) {
-                const long long pix = g0 + u < P.npix ? g0 + u : P.npix - 1;
-                act2[u] = !act[u] && seed[u] >= 0 && clb[u] <= best0[u];
-                const float *q0 = P.Lr + pix * L + (act2[u] ? ch : (seed[u] > 0 ? seed[u] : 0)) * 32 + (lane & 7) * 4;
+            for (int u = 0; u < PPW; u++) more = more || cand[u] != 0u;
+            if (!__builtin_amdgcn_ballot_w64(more)) break;
+            if (more) {
+                int ck[PPW];
+                float S[PPW][4];
 #pragma unroll
-                for (int p = 0; p < MAXD; p++)
-                    if (p < ndir) {
-                        const float4 q = *reinterpret_cast<const float4 *>(q0 + (long long)p * P.nvol);
-                        l[u][p][0] = q.x, l[u][p][1] = q.y, l[u][p][2] = q.z, l[u][p][3] = q.w;
+                for (int u = 0; u < PPW; u++) ck[u] = cand[u] != 0u ? __builtin_ctz(cand[u]) : sck[u];
+                chunk_S(ck, S);
+#pragma unroll
+                for (int u = 0; u < PPW; u++)
+                    if (cand[u] != 0u) {
+#pragma unroll
+                        for (int k = 0; k < 4; k++) {  // (the chunks do not arrive by rising label: the lower label wins a tie)
+                            const int o = ck[u] * 32 + j * 4 + k;
+                            if (finite_bits(S[u][k]) && (S[u][k] < best[u] || (S[u][k] == best[u] && o < bi[u]))) {
+                                best[u] = S[u][k];
+                                bi[u] = o;
+                            }
+                        }
+                        cand[u] &= cand[u] - 1u;
                     }
-            }
-#pragma unroll
-            for (int u = 0; u < PPW; u++) {
-                float S2[4];
-                sum_fix<MAXD>(l[u], c[u], ndir, fix, S2);
-#pragma unroll
-                for (int k = 0; k < 4; k++) S[u][k] = act[u] ? S[u][k] : S2[k];
             }
         }
 #pragma unroll
         for (int u = 0; u < PPW; u++) {
-            if (g0 + u >= P.npix) break;
-            const long long pix = g0 + u;
-            const bool have = act[u] || act2[u];
-            const unsigned long long lmask = __builtin_amdgcn_ballot_w64(have);  // bit 8*c: chunk c was loaded
-            nloaded += (unsigned)__builtin_popcountll(lmask & 0x0101010101010101ull);
-            npx++;
-            // (d) first strict minimum among the finite entries, ascending label
-            float best = f_inf();
-            int bi = 0x7fffffff;
-            if (have) {
-#pragma unroll
-                for (int k = 0; k < 4; k++)
-                    if (finite_bits(S[u][k]) && best > S[u][k]) {
-                        best = S[u][k];
-                        bi = o0 + k;
-                    }
-            }
-            const float gbest = wave_min(best);
-            const unsigned long long who = __builtin_amdgcn_ballot_w64(bi != 0x7fffffff && best == gbest);
-            best = gbest;
-            bi = who ? __builtin_amdgcn_readlane(bi, (int)__builtin_ctzll(who)) : 0x7fffffff;  // (lanes hold rising labels)
-            float outv, outc = best;
-            if (bi == 0x7fffffff) outv = __builtin_nanf("");  // the reference leaves minP uninitialised here
-            else outv = (float)(bi + P.dmin);
+            // (d) first strict minimum among the finite entries by rising label: the group's smallest (S, label)
+            dpp_take<0xB1>(best[u], bi[u]);
+            dpp_take<0x4E>(best[u], bi[u]);
+            dpp_take<0x141>(best[u], bi[u]);
+            const int b = bi[u];
+            float outv, outc = best[u];
+            if (b == NONE) outv = __builtin_nanf("");  // the reference leaves minP uninitialised here
+            else outv = (float)(b + P.dmin);
             if (P.refine == 1) {  // (wave-uniform)
-                if (have) {
+                const bool gate = b != NONE && b - 1 >= 0 && b + 2 <= L - 1;  // mgm_refine.h:58
+                // lanes 0..2 of the group: S at b-1, b, b+1 from memory, by sum_fix's operations in its order (the same float)
+                float a = 0.0f;
+                if (gate && j < 3) {
+                    const long long at = pix[u] * L + (b - 1 + j);
 #pragma unroll
-                    for (int k = 0; k < 4; k++) sS[wv][u][o0 + k] = S[u][k];
+                    for (int p = 0; p < MAXD; p++)
+                        if (p < ndir) a = a + P.Lr[(long long)p * P.nvol + at];
+                    if (fix == 1) a = a - (float)(ndir - 1) * c8_decode(P.C8[at]);
                 }
-                if (bi != 0x7fffffff && bi - 1 >= 0 && bi + 2 <= L - 1) {  // mgm_refine.h:58
-                    auto S_at = [&](int o) -> float {  // (o is wave-uniform)
-                        if ((lmask >> ((o >> 5) * 8)) & 1ull) return sS[wv][u][o];
-                        float a = 0.0f;
-                        for (int p = 0; p < ndir; p++) a = a + P.Lr[(long long)p * P.nvol + pix * L + o];
-                        if (fix == 1) a = a - (float)(ndir - 1) * c8_decode(P.C8[pix * L + o]);
-                        return a;
-                    };
-                    const float v0 = S_at(bi - 1), v1 = S_at(bi), v2 = S_at(bi + 1);
+                const float v1 = dpp_f<0xB1>(a), v2 = dpp_f<0x4E>(a);  // (lane 0 of the group: those of lanes 1 and 2)
+                if (gate) {
                     float vmin, dx;
-                    vfit(v0, v1, v2, vmin, dx);
-                    outv = (float)(bi + P.dmin) + dx;
+                    vfit(a, v1, v2, vmin, dx);
+                    outv = (float)(b + P.dmin) + dx;
                     outc = vmin;
                 }
             }
-            if (lane == 0) {
-                P.out[pix] = outv;
-                P.outcost[pix] = outc;
+            if (j == 0 && own[u]) {
+                P.out[pix[u]] = outv;
+                P.outcost[pix[u]] = outc;
             }
         }
     }
     // one atomic per wave, spread over 64 words 128 bytes apart: one per wave ITERATION on one word (the first version) serialised
     // a million atomics on one address and took the kernel from 1.x to 12 ms
     if (P.stats && lane == 0) atomicAdd(P.stats + (blockIdx.x & 63) * 16, ((unsigned long long)npx << 32) | nloaded);
+}
+// MAXD: upper bound of NDIR (what the planner chooses the instance by); ALLD: NDIR == MAXD.  The other pass counts branch once, at
+// the top, to a body of their own: a test per pass inside one body costs a scalar condition and an address per pass, more than the
+// scalar registers hold.
+template <int PPW, int MAXD, bool ALLD>
+__global__ void __launch_bounds__(256) k_wta_pruned(const WtaParams P)
+{
+    if constexpr (ALLD) {
+        wta_pruned<PPW, MAXD>(P);
+    } else {
+#define ND_CASE(N_)                                         \
+    case N_:                                                \
+        if constexpr (N_ < MAXD) wta_pruned<PPW, N_>(P);    \
+        break;
+        switch (P.NDIR) {  // (wave-uniform; a count the instance is not built for computes nothing: launch_wta never sends one)
+            ND_CASE(1) ND_CASE(2) ND_CASE(3) ND_CASE(4) ND_CASE(5) ND_CASE(6) ND_CASE(7)
+            default: break;
+        }
+#undef ND_CASE
+    }
 }
 
 // The launch tables: from a choice of the planner (plan_wta, mgm_planner.h) to its instance.  Nothing is decided here; a choice
@@ -608,7 +675,7 @@ hipError_t launch_wta(const WtaParams &p, const WtaChoice &c, hipStream_t s)
         return hipGetLastError();                                                                                \
     }
 #define WTA_PRUNED(PPW_, MAXD_, ALLD_)                                                                           \
-    if (c.PPW == PPW_ && c.MAXD == MAXD_ && c.ALLD == ALLD_) {                                                   \
+    if (c.PPW == PPW_ && c.MAXD == MAXD_ && c.ALLD == ALLD_ && p.NDIR >= 1 && (ALLD_ ? p.NDIR == MAXD_ : p.NDIR < MAXD_)) { \
         hipLaunchKernelGGL((k_wta_pruned<PPW_, MAXD_, ALLD_ != 0>), grid, block, 0, s, p);                       \
         return hipGetLastError();                                                                                \
     }
