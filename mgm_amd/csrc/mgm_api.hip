@@ -512,7 +512,7 @@ int mgm_selftest_div3(mgm_ctx *c, unsigned long long *nbad)
     HIPCHK(c, hipSetDevice(c->device));
     int r;
     if ((r = ensure_words(c))) return r;
-    unsigned long long *d = (unsigned long long *)c->words.p + 1;  // (words 2 and 3: scratch; word 1 is the sticky watchdog word)
+    unsigned long long *d = (unsigned long long *)ctrl_word(c, kWordCount64);
     HIPCHK(c, hipMemsetAsync(d, 0, sizeof(unsigned long long), c->stream));
     HIPCHK(c, launch_selftest_div3(d, c->stream));
     HIPCHK(c, hipMemcpyAsync(nbad, d, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
@@ -587,9 +587,7 @@ int mgm_update_ranges_dev(mgm_ctx *c, const mgm_img *outoff, mgm_img *dminI, mgm
     int r;
     if ((r = ensure_words(c))) return r;
     TimeScope t(c, "k_update_ranges");
-    // (the two words of the global minimum / maximum live at the end of the control block, which K3 does not use)
-    HIPCHK(c, launch_update_ranges(outoff->d, outoff->nx, outoff->ny, slack, radius, dminI->d, dmaxI->d,
-                                   (float *)c->words.p + kCtrlWords - 2, c->stream));
+    HIPCHK(c, launch_update_ranges(outoff->d, outoff->nx, outoff->ny, slack, radius, dminI->d, dmaxI->d, (float *)ctrl_word(c, kWordRanges), c->stream));
     return MGM_OK;
 }
 

@@ -105,14 +105,19 @@ int reserve(mgm_ctx *c, Buf &b, size_t bytes)
     return MGM_OK;
 }
 
-// the control words of the pass kernel (and a little scratch for others): zeroed when they come into being -- word 1, the
-// watchdog word, is never reset by a launch (check_watchdog)
-
+// the control words (CtrlWord, mgm_host.h): zeroed when they come into being -- no launch resets the watchdog word (check_watchdog)
 int ensure_words(mgm_ctx *c)
 {
     const void *before = c->words.p;
-    if (int r = reserve(c, c->words, sizeof(unsigned) * ((size_t)kCtrlWords + kPyrWords))) return r;
+    if (int r = reserve(c, c->words, sizeof(unsigned) * (size_t)kCtrlWordsTotal)) return r;
     if (c->words.p != before) HIPCHK(c, hipMemsetAsync(c->words.p, 0, c->words.cap, c->stream));
+    return MGM_OK;
+}
+int read_word(mgm_ctx *c, const unsigned *dev, unsigned *out)
+{
+    HIPCHK(c, hipMemcpyAsync(c->h_words + kHostFlag, dev, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    *out = c->h_words[kHostFlag];
     return MGM_OK;
 }
 
@@ -142,27 +147,31 @@ int refinement_index(const char *n)  // mgm_refine.h:15-35
     return r;
 }
 
-
 // The watchdog word of the pass kernel is STICKY on the device: no launch resets it, a copy of it follows every pass
-// launch into h_words[1], and only the host clears it, once it has seen it set.  A hand-off time-out of one launch is
+// launch into its pinned mirror (watch_launch), and only the host clears it, once it has seen it set.  A hand-off time-out of one launch is
 // therefore reported by whichever call next finds the stream idle (block = false: pass launches look without waiting --
 // nothing on the hot path synchronises for it) or synchronises anyway (block = true), and cannot be overwritten by a
 // later launch's copy.
+int watch_launch(mgm_ctx *c)
+{
+    HIPCHK(c, hipMemcpyAsync(c->h_words + kHostWatchdog, ctrl_word(c, kWordWatchdog), sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
+    c->pending_check = true;
+    return MGM_OK;
+}
 int check_watchdog(mgm_ctx *c, bool block)
 {
     if (!c->pending_check) return MGM_OK;
     if (block) HIPCHK(c, hipStreamSynchronize(c->stream));
     else if (hipStreamQuery(c->stream) != hipSuccess) return MGM_OK;  // still running: the word is looked at later
     c->pending_check = false;
-    if (c->h_words[1] != 0) {
-        c->h_words[1] = 0;
-        if (c->words.p) (void)hipMemsetAsync((unsigned *)c->words.p + 1, 0, sizeof(unsigned), c->stream);
-        c->hand_key = HandLayout{};  // (the launch may have left its hand-off slots half written)
+    if (c->h_words[kHostWatchdog] != 0) {
+        c->h_words[kHostWatchdog] = 0;
+        if (c->words.p) (void)hipMemsetAsync(ctrl_word(c, kWordWatchdog), 0, sizeof(unsigned), c->stream);
+        forget_hand_regions(c);  // (the launch, dense or range-proportional, may have left its hand-off slots half written)
         return fail(c, MGM_ERR_INTERNAL, "pass kernel watchdog: inter-band hand-off timed out");
     }
     return MGM_OK;
 }
-
 
 bool pipe_uses(const mgm_ctx *c, const void *obj)  // is `obj` (a volume or an image) an operand of a deferred call?
 {
@@ -175,6 +184,16 @@ bool pipe_uses(const mgm_ctx *c, const void *obj)  // is `obj` (a volume or an i
     }
     return false;
 }
+
+// the grow-only workspace: what mgm_ctx_trim hands back (the control words stay until the context goes)
+static std::vector<Buf *> workspace_bufs(mgm_ctx *c)
+{
+    std::vector<Buf *> bufs = {&c->lr, &c->hand.buf, &c->hand2, &c->handm, &c->exact_mins, &c->exact_scratch, &c->census_u, &c->census_v, &c->dbg, &c->stmp, &c->ones8,
+                               &c->lr_rel, &c->hand_rel.buf, &c->lmin, &c->wta_stats, &c->wvals};
+    for (int v = 0; v < kMaxBatch; v++) bufs.insert(bufs.end(), {&c->padf[v], &c->pad8[v], &c->wsel[v]});
+    return bufs;
+}
+static void release(Buf &b) { if (b.p) (void)hipFree(b.p), b = Buf{}; }
 
 // ---------------------------------------------------------------------------
 extern "C" {
@@ -198,12 +217,12 @@ int mgm_ctx_create(int device, mgm_ctx **out)
         delete c;
         return MGM_ERR_HIP;
     }
-    if (hipHostMalloc((void **)&c->h_words, 16 * sizeof(unsigned), hipHostMallocDefault) != hipSuccess) {
+    if (hipHostMalloc((void **)&c->h_words, kHostWords * sizeof(unsigned), hipHostMallocDefault) != hipSuccess) {
         (void)hipStreamDestroy(c->stream);
         delete c;
         return MGM_ERR_HIP;
     }
-    memset(c->h_words, 0, 16 * sizeof(unsigned));
+    memset(c->h_words, 0, kHostWords * sizeof(unsigned));
     c->force_build = (int)tune_num("pass_build", 0);
     c->debug_stats = (int)tune_num("debug_stats", 0);
     *out = c;
@@ -216,18 +235,10 @@ int mgm_ctx_destroy(mgm_ctx *c)
     (void)hipSetDevice(c->device);
     (void)pipe_join(c);  // (deferred calls of a pipelined context still write the caller's images)
     (void)hipStreamSynchronize(c->stream);
-    std::vector<Buf *> bufs = {&c->lr, &c->hand, &c->hand2, &c->handm, &c->exact_mins, &c->exact_scratch, &c->words, &c->census_u, &c->census_v, &c->dbg, &c->stmp, &c->ones8,
-                               &c->lr_rel, &c->hand_rel, &c->lmin, &c->wta_stats};  // (the range-proportional kernels' workspace: round 5 forgot it here)
-    for (int v = 0; v < kMaxBatch; v++) {
-        bufs.push_back(&c->padf[v]);
-        bufs.push_back(&c->pad8[v]);
-        bufs.push_back(&c->wsel[v]);
-    }
-    bufs.push_back(&c->wvals);
     c->dense_plans.free_all();
     c->rel_plans.free_all();
-    for (Buf *b : bufs)
-        if (b->p) (void)hipFree(b->p);
+    for (Buf *b : workspace_bufs(c)) release(*b);
+    release(c->words);
     for (auto &t : c->tim) {
         if (t.alias) continue;
         (void)hipEventDestroy(t.a);
@@ -258,24 +269,11 @@ int mgm_ctx_trim(mgm_ctx *c)
     if (!c) return MGM_ERR_INVALID;
     HIPCHK(c, hipSetDevice(c->device));
     if (int r = mgm_ctx_synchronize(c)) return r;
-    std::vector<Buf *> bufs = {&c->lr, &c->hand, &c->hand2, &c->handm, &c->exact_mins, &c->exact_scratch, &c->census_u, &c->census_v, &c->dbg, &c->stmp, &c->ones8,
-                               &c->lr_rel, &c->hand_rel, &c->lmin, &c->wta_stats};
     c->last.clear();
     c->rel_last.clear();
     c->wta_stats_n = 0;
-    c->hand_rel_key = HandLayout{};
-    for (int v = 0; v < kMaxBatch; v++) {
-        bufs.push_back(&c->padf[v]);
-        bufs.push_back(&c->pad8[v]);
-        bufs.push_back(&c->wsel[v]);
-    }
-    bufs.push_back(&c->wvals);
-    for (Buf *b : bufs) {
-        if (b->p) (void)hipFree(b->p);
-        b->p = nullptr;
-        b->cap = 0;
-    }
-    c->hand_key = HandLayout{};
+    for (Buf *b : workspace_bufs(c)) release(*b);
+    forget_hand_regions(c);
     c->dense_plans.free_all();
     c->rel_plans.free_all();
     return MGM_OK;

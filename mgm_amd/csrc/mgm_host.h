@@ -91,6 +91,7 @@ struct Buf {  // grow-only device scratch
     void *p = nullptr;
     size_t cap = 0;
 };
+struct HandRegion { Buf buf; HandTags tags; };  // a region of self-validating hand-off slots and what its words carry (mgm_planner.h)
 
 // The task tables of earlier launches, by the request they were planned for (mgm_planner.h): request -> (plan, device table).
 // Bounded: the oldest entry is dropped (cache_put, mgm_plan.hip, which synchronises before it frees a buffer).  A caller that
@@ -199,10 +200,9 @@ struct mgm_ctx {
     std::string err;
     // workspace
     Buf exact_mins, exact_scratch;  // slab minima / (FH beyond 8192 labels) convolution arrays of the operand-order-faithful pass kernel
-    Buf lr, hand, hand2, handm, words, census_u, census_v, dbg, stmp, ones8;  // hand: self-validating slabs (TAGS); hand2: the other kernels' slots
-    // range-proportional aggregation of ragged volumes (mgm_pass_rel.hip): its Lr volumes [volume][pass][npix][64], hand-off slots,
-    // and what the last such aggregation ran on (mgm_wta_windowed_dev searches it again)
-    Buf lr_rel, hand_rel;
+    Buf lr, hand2, handm, words, census_u, census_v, dbg, stmp, ones8;  // hand2: the slots of the kernels without tags
+    Buf lr_rel;                 // the range-proportional kernels' (mgm_pass_rel.hip) Lr volumes [volume][pass][npix][slots]
+    HandRegion hand, hand_rel;  // self-validating slabs of k_pass2 (TAGS) / of the range-proportional kernels (forget_hand_regions)
     // chunk minima of the dense Lr volumes (k_pass2, CHMIN): one float per 32 of c->lr, written by the last dense launch iff
     // last.wrote_min; the pruned winner search reads them (run_wta).  wta_stats: its two counters' word on the device (timing or
     // debug statistics on), wta_stats_n: searches counted into it since the last aggregation call began (0: none was pruned)
@@ -230,19 +230,13 @@ struct mgm_ctx {
     size_t placed_cap = 0;
     size_t ws_limit = 0;  // mgm_ctx_set_workspace_limit: cap on the Lr + hand-off workspace of one pass launch (0 = none)
     int debug_stats = 0;  // MGM_HIP_DEBUG_STATS=1: per-workgroup timing summary of K3 on stderr
-    unsigned *h_words = nullptr;  // pinned mirror of the control words
+    unsigned *h_words = nullptr;  // pinned mirrors (HostWord below)
     PlanCache<DenseRequest, DensePlan> dense_plans;  // plans + task tables of the dense kernels' launches, by request
     PlanCache<RelRequest, RelPlan> rel_plans;        // ... of the range-proportional kernels'
     int force_build = 0;  // 0 auto, 1 first build only (MGM_HIP_PASS_BUILD=1)
     Buf padf[kMaxBatch], pad8[kMaxBatch];  // padded copies of the cost volumes of a launch whose label count was padded
     Buf wsel[kMaxBatch], wvals;            // two-valued weights (k_pass2, W2): selector words per volume; the value scan's words
     bool pending_check = false;
-    // self-validating hand-off slabs (k_pass2, TAGS): the layout the region was last cleared for (npass 0: unknown -- the next
-    // launch clears it), and the tag of its last launch
-    HandLayout hand_key;
-    HandLayout hand_rel_key;       // the range-proportional kernels' slots (same protocol): layout they were last written for ...
-    unsigned hand_rel_tag = 0;     // ... and the tag they carry
-    unsigned hand_tags[kMaxDirs] = {};  // per pass: the tag its slots carry after its last launch
     int num_cu = 256;  // hipDeviceProp_t::multiProcessorCount
     int xcc_mask = -1;  // XCC ids the workgroups of a launch see (k_xcc_census; -1: not looked yet)
     // timing
@@ -250,11 +244,25 @@ struct mgm_ctx {
     std::vector<Timing> tim;
 };
 
-
 constexpr int kWtaStatSlots = 64;  // the pruned search's counters: one word per 128 bytes, a workgroup adds to slot blockIdx.x % 64
 constexpr size_t kWtaStatBytes = (size_t)kWtaStatSlots * 128;
-constexpr int kCtrlWords = 4 + kMaxBatch * kMaxDirs * kMaxBands;  // ticket, err, flag, pad, prog[volume*8 + pass][maxbands]
-constexpr int kPyrWords = 4;  // behind the control block: the words of mgm_pyramid.hip (minimum / maximum of a coarse map, integer hull)
+// The context's control words (mgm_ctx::words; zeroed when they come into being, ensure_words): who lives where.  Tenants that
+// may be live at the same time have words of their own (the assertions below); only the queue tickets alias the progress words.
+constexpr int kProgWords = kMaxBatch * kMaxDirs * kMaxBands, kQueueTickets = 9;  // prog[volume*8 + pass][band]; the per-XCD queues' tickets of k_pass2
+enum CtrlWord : int {
+    kWordTicket = 0,    // the pass kernels' ticket counter, reset before every launch
+    kWordWatchdog = 1,  // STICKY: set by a hand-off that timed out, cleared by the host alone (check_watchdog)
+    kWordFlag = 3,      // one call's flag or count: set, read back (read_word) and done with before the call returns
+    kWordProg = 4,      // progress words of the kernels without tags; ALIAS: the queue tickets (kernels with tags, which have no progress words)
+    kWordPyr = kWordProg + kProgWords,  // mgm_pyramid.hip: minimum / maximum of a coarse map (2 words), integer hull (2)
+    kWordRanges = kWordPyr + 4,         // mgm_update_ranges_dev: global minimum / maximum (2 words)
+    kWordCount64 = kWordRanges + 2,     // mgm_selftest_div3: one 64-bit counter (2 words)
+    kCtrlWordsTotal = kWordCount64 + 2  // what ensure_words reserves
+};
+static_assert(kWordTicket < kWordWatchdog && kWordWatchdog < kWordFlag && kWordFlag < kWordProg && kQueueTickets <= kProgWords, "control words: one tenant each");
+static_assert(kWordProg % 4 == 0 && kWordCount64 % 2 == 0, "progress words 16-byte aligned, the 64-bit counter 8-byte aligned");
+inline unsigned *ctrl_word(const mgm_ctx *c, CtrlWord w) { return (unsigned *)c->words.p + w; }
+enum HostWord : int { kHostWatchdog = 1, kHostFlag = 3, kHostWords = 16 };  // mgm_ctx::h_words: the mirrors of watch_launch and read_word
 
 // Development switches (A/B timing, tests of the fall-back paths), read once per process; everything is on by default.
 struct DevSwitches {
@@ -302,6 +310,9 @@ int hipfail(mgm_ctx *c, hipError_t e, const char *what);
 hipError_t dev_malloc(void **p, size_t bytes);
 int reserve(mgm_ctx *c, Buf &b, size_t bytes);
 int ensure_words(mgm_ctx *c);
+int read_word(mgm_ctx *c, const unsigned *dev, unsigned *out);  // one device word, through the pinned flag mirror; synchronises
+int watch_launch(mgm_ctx *c);  // after a pass launch: the watchdog word's copy follows it (check_watchdog looks at it later)
+inline void forget_hand_regions(mgm_ctx *c) { hand_forget(c->hand.tags), hand_forget(c->hand_rel.tags); }  // their slots may carry anything: the next launch clears them
 
 struct TimeScope {  // brackets one kernel launch with events when timing is on
     mgm_ctx *c;

@@ -49,12 +49,11 @@ int weights_have_odd_values(mgm_ctx *c, const mgm_img *const *w8s, int nb, long 
 static int ensure_xcc_mask(mgm_ctx *c)
 {
     if (c->xcc_mask >= 0) return MGM_OK;
-    unsigned *words = (unsigned *)c->words.p;
-    HIPCHK(c, hipMemsetAsync(words + 3, 0, sizeof(unsigned), c->stream));
-    HIPCHK(c, launch_xcc_census(words + 3, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->h_words + 3, words + 3, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->xcc_mask = (int)c->h_words[3];
+    unsigned *flag = ctrl_word(c, kWordFlag), mask = 0;
+    HIPCHK(c, hipMemsetAsync(flag, 0, sizeof(unsigned), c->stream));
+    HIPCHK(c, launch_xcc_census(flag, c->stream));
+    if (int r = read_word(c, flag, &mask)) return r;
+    c->xcc_mask = (int)mask;
     return MGM_OK;
 }
 
@@ -309,18 +308,27 @@ static int pad_f32(mgm_ctx *c, const mgm_cv *const *Cs, int nb, long long npix, 
 // padded copies of the costs of all volumes as compact costs of `tb` bytes (mgm_ctx::pad8): *fits = every cost has a code
 static int try_pad(mgm_ctx *c, const mgm_cv *const *Cs, int nb, long long npix, int Lreal, int L, int tb, int *fits)
 {
-    unsigned *words = (unsigned *)c->words.p;
+    unsigned *flag = ctrl_word(c, kWordFlag), misfits = 0;
     int r;
-    HIPCHK(c, hipMemsetAsync(words + 3, 0, sizeof(unsigned), c->stream));
+    HIPCHK(c, hipMemsetAsync(flag, 0, sizeof(unsigned), c->stream));
     for (int v = 0; v < nb; v++) {
         if ((r = ensure_f32(c, Cs[v]))) return r;
         if ((r = reserve(c, c->pad8[v], (size_t)npix * L * tb))) return r;
         TimeScope ts(c, "k_pad");
-        HIPCHK(c, launch_pad(Cs[v]->d, npix, Lreal, L, nullptr, (uint8_t *)c->pad8[v].p, tb, words + 3, c->stream));
+        HIPCHK(c, launch_pad(Cs[v]->d, npix, Lreal, L, nullptr, (uint8_t *)c->pad8[v].p, tb, flag, c->stream));
     }
-    HIPCHK(c, hipMemcpyAsync(c->h_words + 3, words + 3, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    *fits = c->h_words[3] == 0;
+    if ((r = read_word(c, flag, &misfits))) return r;
+    *fits = misfits == 0;
+    return MGM_OK;
+}
+
+// A launch's region of self-validating slots (HandTags): room, its tags, the clear they may ask for.  The caller commits after the enqueue.
+static int begin_hand(mgm_ctx *c, HandRegion &h, size_t bytes, const HandLayout &want, int first, int end, HandStep *step)
+{
+    const void *before = h.buf.p;
+    if (int r = reserve(c, h.buf, bytes)) return r;
+    *step = hand_begin(h.tags, want, first, end, h.buf.p != before);
+    if (step->clear) HIPCHK(c, hipMemsetAsync(h.buf.p, kHandClearByte, bytes, c->stream));
     return MGM_OK;
 }
 
@@ -406,8 +414,7 @@ int run_passes(mgm_ctx *c, const mgm_cv *const *Cs, const mgm_img *const *w8s, i
     if (int r0 = check_watchdog(c, false)) return r0;  // (without waiting: the word is sticky on the device)
     int r;
     if ((r = ensure_words(c))) return r;
-    unsigned *words = (unsigned *)c->words.p;
-    HIPCHK(c, hipMemsetAsync(words, 0, sizeof(unsigned), c->stream));  // the ticket (the progress words: below, where they are used)
+    HIPCHK(c, hipMemsetAsync(ctrl_word(c, kWordTicket), 0, sizeof(unsigned), c->stream));  // (the progress words: below, where they are used)
 
     // 1. the operands, on the device
     DenseOperands o;
@@ -471,36 +478,16 @@ int run_passes(mgm_ctx *c, const mgm_cv *const *Cs, const mgm_img *const *w8s, i
         if ((r = reserve(c, c->lmin, sizeof(float) * ((size_t)lr_stride * nslots * nb / kChunkLabels + 8)))) return r;
         p.min_k = (long long)(uintptr_t)c->lmin.p - (long long)((uintptr_t)c->lr.p >> 5) - 3;
     }
-    // The second build's unweighted kernels hand slabs from band to band that validate themselves (mgm_pass2.hip, TAGS):
-    // one slot per (volume, pass, band, pixel), written once per launch OF THAT PASS with the tag in the sign bits.  A
-    // pass's tag alternates between its consecutive launches over the same slots; a different layout clears the region
-    // first (all-ones words) and starts every pass again with tag 0.  The region is laid out for the passes
-    // [0, layout_ndir) and is this protocol's alone (the other kernels' slots live in `hand2`), so neither a caller that
-    // launches the passes one by one nor one that alternates weighted and unweighted runs makes it be cleared again.
-    float *hand_ptr = nullptr;
+    // (the region with tags is laid out for the passes [0, layout_ndir); the other kernels' slots live in `hand2`)
     if (tags) {
-        const size_t bytes = sizeof(float) * (size_t)ngroups * plan.hand_vstride * LPk;
-        const void *before = c->hand.p;
-        if ((r = reserve(c, c->hand, bytes))) return r;
-        if (c->hand.p != before || c->hand_key != plan.hand) {
-            HIPCHK(c, hipMemsetAsync(c->hand.p, 0xff, bytes, c->stream));
-            c->hand_key = plan.hand;
-            for (int k = 0; k < kMaxDirs; k++) c->hand_tags[k] = 0x80000000u;  // (what the cleared words look like)
-        }
-        for (int k = first; k < PEND; k++) {
-            c->hand_tags[k] ^= 0x80000000u;
-            p.hand_tag[k] = c->hand_tags[k];
-        }
-        // The tags are only good for a launch that really rewrites every slot of its passes: until the pass kernel has
-        // been enqueued the region counts as unknown (the next call clears it), so an error return between here and the
-        // launch cannot leave slots behind that carry the tag of the launch after next.
-        c->hand_key = HandLayout{};
-        hand_ptr = (float *)c->hand.p;
+        HandStep step;
+        if ((r = begin_hand(c, c->hand, sizeof(float) * (size_t)ngroups * plan.hand_vstride * LPk, plan.hand, first, PEND, &step))) return r;
+        for (int k = 0; k < kMaxDirs; k++) p.hand_tag[k] = step.tag[k];
+        p.hand = (float *)c->hand.buf.p;
     } else {
         if ((r = reserve(c, c->hand2, sizeof(float) * (size_t)nb * kMaxDirs * 2 * maxLL * plan.NS * (subv > 1 ? Lk : q.lpl * 64)))) return r;
-        hand_ptr = (float *)c->hand2.p;
-        // progress words of this protocol: [volume*8 + pass][band]
-        HIPCHK(c, hipMemsetAsync(words + 4, 0, sizeof(unsigned) * (size_t)nb * kMaxDirs * kMaxBands, c->stream));
+        p.hand = (float *)c->hand2.p;
+        HIPCHK(c, hipMemsetAsync(ctrl_word(c, kWordProg), 0, sizeof(unsigned) * (size_t)nb * kMaxDirs * kMaxBands, c->stream));
     }
     if ((r = reserve(c, c->handm, sizeof(float) * (size_t)nb * kMaxDirs * 2 * maxLL))) return r;
 
@@ -539,17 +526,16 @@ int run_passes(mgm_ctx *c, const mgm_cv *const *Cs, const mgm_img *const *w8s, i
     p.hand_vstride = plan.hand_vstride;
     p.wg_per_cu = plan.wg_per_cu;
     p.deep = plan.deep;
-    p.hand = hand_ptr;
     p.handm = (float *)c->handm.p;
-    p.ticket = words + 0;
-    p.err = words + 1;
-    p.prog = words + 4;
+    p.ticket = ctrl_word(c, kWordTicket);
+    p.err = ctrl_word(c, kWordWatchdog);
+    p.prog = ctrl_word(c, kWordProg);
     p.tasks = (const int2 *)e->buf.p + 8;  // (behind the header)
     p.xcdq = xcdq ? (plan.one_queue ? 2 : 1) : 0;
     p.oneb = plan.oneb;
     p.cbytes = o.use_c8 ? o.cb : 1;
-    p.qticket = words + 4;  // (the progress words of the other protocol: the kernels with tags do not use them)
-    if (xcdq) HIPCHK(c, hipMemsetAsync(words + 4, 0, 9 * sizeof(unsigned), c->stream));
+    p.qticket = ctrl_word(c, kWordProg);  // (the progress words of the other protocol: the kernels with tags do not use them)
+    if (xcdq) HIPCHK(c, hipMemsetAsync(p.qticket, 0, kQueueTickets * sizeof(unsigned), c->stream));
     p.npix = npix;
     p.nvol = lr_stride;
     p.L = L;
@@ -600,28 +586,27 @@ int run_passes(mgm_ctx *c, const mgm_cv *const *Cs, const mgm_img *const *w8s, i
         else HIPCHK(c, launch_pass(p, plan.kernel, ntasks, c->stream));
     }
     if (tags) {
-        c->hand_key = plan.hand;  // enqueued: every slot of the region will carry this launch's tag
+        hand_commit(c->hand.tags, plan.hand);
         // MGM_HIP_CHECK_TAGS=1 (debug; synchronises): the invariant the tag protocol rests on, checked after the launch --
         // every word of the slots of this launch's passes (all bands but the last, which hands nothing over) carries the
         // launch's tag.  A slot the kernel skipped would keep its OLD tag and validate a stale slab two launches later.
         if (tune_num("check_tags", 0) != 0) {
-            HIPCHK(c, hipMemsetAsync(words + 3, 0, sizeof(unsigned), c->stream));
+            unsigned *flag = ctrl_word(c, kWordFlag), stale = 0;
+            HIPCHK(c, hipMemsetAsync(flag, 0, sizeof(unsigned), c->stream));
             for (int v = 0; v < ngroups; v++)
                 for (int k = first; k < PEND; k++) {
                     const long long nw = (long long)(p.g[k].nbands - 1) * p.g[k].LL * LPk;
                     if (nw <= 0) continue;
-                    HIPCHK(c, launch_check_tags(hand_ptr + ((long long)v * p.hand_vstride + p.g[k].hand_base) * LPk, nw, p.hand_tag[k], words + 3, c->stream));
+                    HIPCHK(c, launch_check_tags(p.hand + ((long long)v * p.hand_vstride + p.g[k].hand_base) * LPk, nw, c->hand.tags.tag[k], flag, c->stream));
                 }
-            HIPCHK(c, hipMemcpyAsync(c->h_words + 3, words + 3, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-            if (c->h_words[3] != 0) {
-                c->hand_key = HandLayout{};
-                return fail(c, MGM_ERR_INTERNAL, "hand-off slots: " + std::to_string(c->h_words[3]) + " words do not carry the launch's tag");
+            if ((r = read_word(c, flag, &stale))) return r;
+            if (stale != 0) {
+                hand_forget(c->hand.tags);
+                return fail(c, MGM_ERR_INTERNAL, "hand-off slots: " + std::to_string(stale) + " words do not carry the launch's tag");
             }
         }
     }
-    HIPCHK(c, hipMemcpyAsync(c->h_words + 1, words + 1, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
-    c->pending_check = true;
+    if ((r = watch_launch(c))) return r;
     if (p.tl_on) {
         char head[96], tail[96];
         snprintf(head, sizeof head, "launch %d %d %d %d %d", nx, ny, L, ntasks, p.wg_per_cu);
@@ -864,7 +849,6 @@ int run_rel(mgm_ctx *c, const mgm_cv *const *Cs, const mgm_img *const *w8s, int 
     HIPCHK(c, hipSetDevice(c->device));
     if (int r0 = check_watchdog(c, false)) return r0;
     if ((r = ensure_words(c))) return r;
-    unsigned *words = (unsigned *)c->words.p;
 
     // 1. the operands (the volumes' copies and the weights' values were resolved by the caller: rel_resolve, weights_have_odd_values)
     const bool fh = use_fh > 0;
@@ -907,23 +891,10 @@ int run_rel(mgm_ctx *c, const mgm_cv *const *Cs, const mgm_img *const *w8s, int 
     const long long stride = npix * slots + lr_pad_floats();
     if ((r = reserve(c, c->lr_rel, sizeof(float) * (size_t)stride * NDIR * nb))) return r;
     RelParams p{};
-    // self-validating hand-off slots, one per (volume, pass, band, pixel): written once per launch with the launch's tag (see
-    // k_pass_rel); another layout clears the region (all-ones words) and starts again with tag 0
-    {
-        const size_t bytes = sizeof(float) * (size_t)nb * plan.hand_vstride * q.HS;
-        const void *before = c->hand_rel.p;
-        if ((r = reserve(c, c->hand_rel, bytes))) return r;
-        if (c->hand_rel.p != before || c->hand_rel_key != plan.hand) {
-            HIPCHK(c, hipMemsetAsync(c->hand_rel.p, 0xff, bytes, c->stream));
-            c->hand_rel_key = plan.hand;
-            c->hand_rel_tag = 0x80000000u;  // (what the cleared words look like)
-        }
-        c->hand_rel_tag ^= 0x80000000u;
-        p.tag = c->hand_rel_tag;
-        // until the launch has been enqueued the region counts as unknown (an error return in between must not leave slots behind
-        // that carry the tag of the launch after next)
-        c->hand_rel_key = HandLayout{};
-    }
+    // (every launch runs all NDIR passes of the layout, so their tags stay in lockstep: the kernel takes one)
+    HandStep step;
+    if ((r = begin_hand(c, c->hand_rel, sizeof(float) * (size_t)nb * plan.hand_vstride * q.HS, plan.hand, 0, NDIR, &step))) return r;
+    p.tag = step.tag[0];
 
     // 5. the kernel's parameters
     for (int v = 0; v < nb; v++) {
@@ -937,9 +908,9 @@ int run_rel(mgm_ctx *c, const mgm_cv *const *Cs, const mgm_img *const *w8s, int 
     for (int k = 0; k < kMaxDirs; k++) p.g[k] = plan.g[k];
     p.hand_vstride = plan.hand_vstride;
     p.diag_any = plan.diag_any;
-    p.hand = (float *)c->hand_rel.p;
-    p.ticket = words + 0;
-    p.err = words + 1;
+    p.hand = (float *)c->hand_rel.buf.p;
+    p.ticket = ctrl_word(c, kWordTicket);
+    p.err = ctrl_word(c, kWordWatchdog);
     p.tasks = (const int2 *)e->buf.p;
     p.npix = npix;
     p.nvol = stride;
@@ -967,16 +938,15 @@ int run_rel(mgm_ctx *c, const mgm_cv *const *Cs, const mgm_img *const *w8s, int 
         HIPCHK(c, hipMemsetAsync(c->dbg.p, 0, sizeof(unsigned long long) * (8 + nph) * (size_t)ntasks, c->stream));
         p.tl = (unsigned long long *)c->dbg.p;
     }
-    HIPCHK(c, hipMemsetAsync(words, 0, sizeof(unsigned), c->stream));
+    HIPCHK(c, hipMemsetAsync(p.ticket, 0, sizeof(unsigned), c->stream));
 
     // 6. the launch
     {
         TimeScope t(c, "k_pass_rel");
         HIPCHK(c, launch_pass_rel(p, plan.kernel, ntasks, c->stream));
     }
-    c->hand_rel_key = plan.hand;  // enqueued: every slot of the region will carry this launch's tag
-    HIPCHK(c, hipMemcpyAsync(c->h_words + 1, words + 1, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
-    c->pending_check = true;
+    hand_commit(c->hand_rel.tags, plan.hand);
+    if ((r = watch_launch(c))) return r;
     if (p.tl) {
         char head[96], tail[96];
         snprintf(head, sizeof head, "launch %d %d %d %d %d", nx, ny, 64, ntasks, rel_wg);

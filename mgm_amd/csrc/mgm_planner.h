@@ -158,6 +158,35 @@ inline HandLayout lay_out_hand(PassGeom *g, int npass, int nx, int ny, int group
     return h;
 }
 
+// ---- the tags of a region of self-validating slots, as a state machine ---------------------------------------------------
+// The second build's unweighted kernels (mgm_pass2.hip, TAGS) and the range-proportional kernels (k_pass_rel) hand slabs from band
+// to band that validate themselves: one slot per (volume, pass, band, pixel), written once per launch OF THAT PASS with the tag
+// in the sign bits.  A pass's tag alternates between its consecutive launches over the same slots; a region that moved or is
+// wanted in another layout is cleared first (all-ones words) and starts every pass again with tag 0.  A region is laid out for
+// the passes [0, layout.npass) and is one protocol's alone, so neither a caller that launches the passes one by one nor one that
+// alternates weighted and unweighted runs makes it be cleared again.  The tags are only good for a launch that really rewrites
+// every slot of its passes: between hand_begin and hand_commit (after the kernel has been enqueued) the layout counts as
+// unknown, so an error return in between cannot leave slots behind that carry the tag of the launch after next; whoever learns
+// that a launch may not have written all its slots (a hand-off time-out), or frees the region, calls hand_forget.
+constexpr unsigned kHandTagBit = 0x80000000u;
+constexpr int kHandClearByte = 0xff;  // what a region is cleared with: its words then have the tag bit set
+struct HandTags {
+    HandLayout layout;            // what the region was last cleared for (npass 0: unknown -- the next launch clears it)
+    unsigned tag[kMaxDirs] = {};  // per pass: the tag its slots carry after its last launch
+};
+struct HandStep { bool clear; unsigned tag[kMaxDirs]; };  // clear the region first; the tags of the launch's passes [first, end) (the others: 0)
+inline HandStep hand_begin(HandTags &t, const HandLayout &want, int first, int end, bool moved)
+{
+    HandStep s{};
+    s.clear = moved || t.layout.npass == 0 || t.layout != want;
+    for (int k = 0; s.clear && k < kMaxDirs; k++) t.tag[k] = kHandTagBit;
+    for (int k = first; k < end; k++) s.tag[k] = t.tag[k] ^= kHandTagBit;
+    t.layout = HandLayout{};
+    return s;
+}
+inline void hand_commit(HandTags &t, const HandLayout &layout) { t.layout = layout; }  // (enqueued: every slot of the launch's passes will carry its tag)
+inline void hand_forget(HandTags &t) { t.layout = HandLayout{}; }
+
 // ---- the launch as a list-scheduling problem, simulated ---------------------------------------------------------------
 // A chain = the bands of one pass (or one strip of it) of one volume, band b READY once band b-1 (of both strips) started
 // `skew` steps earlier; `nqueues` queues of `slots` band slots each, band b of chain k belonging to queue

@@ -184,11 +184,10 @@ hipError_t launch_ranges_hull(const float *lo, const float *hi, long long n, int
 }  // namespace mgm
 
 // ---- host side ----------------------------------------------------------------------------------------------------------
-// The four words this unit owns BEHIND the context's control block (kPyrWords, reserved by ensure_words): the finite
-// minimum / maximum of a coarse map and the integer hull.  No pass launch addresses them.
-static_assert(kPyrWords >= 4, "mgm_pyramid.hip keeps four words behind the control block");
-static unsigned *pyr_mm(mgm_ctx *c) { return (unsigned *)c->words.p + kCtrlWords; }
-static int *pyr_hull(mgm_ctx *c) { return (int *)c->words.p + kCtrlWords + 2; }
+// The four control words this unit owns (kWordPyr, mgm_host.h): the finite minimum / maximum of a coarse map and the
+// integer hull.  No pass launch addresses them.
+static unsigned *pyr_mm(mgm_ctx *c) { return ctrl_word(c, kWordPyr); }
+static int *pyr_hull(mgm_ctx *c) { return (int *)ctrl_word(c, kWordPyr) + 2; }
 
 static int read_hull(mgm_ctx *c, int *hull_min, int *hull_max)
 {

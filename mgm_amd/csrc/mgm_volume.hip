@@ -198,22 +198,21 @@ int c8_resolve(mgm_ctx *c, const mgm_cv *ccv, bool *use)
         cv->nan_state = CopyState::Written;
     }
     if (cv->c8_state == CopyState::Written || cv->nan_state == CopyState::Written) {
-        HIPCHK(c, hipMemcpyAsync(c->h_words + 3, cv->bad8, 4, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (cv->c8_state == CopyState::Written) cv->c8_state = (c->h_words[3] & 1u) ? CopyState::Invalid : CopyState::Valid;
-        if (cv->nan_state == CopyState::Written) cv->nan_state = (c->h_words[3] & 2u) ? CopyState::Invalid : CopyState::Valid;
+        unsigned bad = 0;
+        if (int r = read_word(c, cv->bad8, &bad)) return r;
+        if (cv->c8_state == CopyState::Written) cv->c8_state = (bad & 1u) ? CopyState::Invalid : CopyState::Valid;
+        if (cv->nan_state == CopyState::Written) cv->nan_state = (bad & 2u) ? CopyState::Invalid : CopyState::Valid;
         // an uploaded volume of whole numbers beyond 254 (absolute differences of a colour pair computed elsewhere): the
         // two-byte form, where the pass kernels read it (up to 512 labels) -- k_compact says whether it would fit
-        if (launched && cv->c8_state == CopyState::Invalid && cv->nan_state == CopyState::Valid && !(c->h_words[3] & 8u) && L <= 512 && cv->f32_state) {
+        if (launched && cv->c8_state == CopyState::Invalid && cv->nan_state == CopyState::Valid && !(bad & 8u) && L <= 512 && cv->f32_state) {
             if (int r = c8_alloc(c, cv, 2)) return r;
             HIPCHK(c, hipMemsetAsync(cv->bad8, 0, 4, c->stream));
             {
                 TimeScope t(c, "k_compact");
                 HIPCHK(c, launch_compact(cv->d, n, cv->d8, 2, cv->bad8, c->stream));
             }
-            HIPCHK(c, hipMemcpyAsync(c->h_words + 3, cv->bad8, 4, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-            cv->c8_state = (c->h_words[3] & 1u) ? CopyState::Invalid : CopyState::Valid;
+            if (int r = read_word(c, cv->bad8, &bad)) return r;
+            cv->c8_state = (bad & 1u) ? CopyState::Invalid : CopyState::Valid;
         }
         if (cv->c8_state == CopyState::Invalid && !cv->f32_state)
             return fail(c, MGM_ERR_INTERNAL, "cost volume predicted to fit the compact form does not");
@@ -232,9 +231,8 @@ int rel_resolve(mgm_ctx *c, const mgm_cv *ccv, bool *usable)
         // the flag word of the gathered copy: while it asks for a wider format and rel_next_format (mgm_fillplan.h) has one, the copy is
         // gathered again; what fits none keeps the dense hull
         for (int round = 0; round < 4; round++) {
-            HIPCHK(c, hipMemcpyAsync(c->h_words + 3, cv->rel_flag(), 4, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-            const unsigned f = c->h_words[3];
+            unsigned f = 0;
+            if (int r = read_word(c, cv->rel_flag(), &f)) return r;
             if (f == 0u) {
                 cv->rel_state = CopyState::Valid;
                 break;
@@ -392,12 +390,7 @@ static int run_attempts(mgm_ctx *c, mgm_cv *cv, const FillRequest &req, const Fi
             }
         }
         unsigned word = 0u;
-        if (a.readback) {
-            if (flag != cv->bad8 && (r = ensure_words(c))) return r;
-            HIPCHK(c, hipMemcpyAsync(c->h_words + 3, flag, 4, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-            word = c->h_words[3];
-        }
+        if (a.readback && (r = read_word(c, flag, &word))) return r;
         const FillStep s = fill_step(plan, a, word, *mem);
         *mem = s.mem;
         if (s.done) {
