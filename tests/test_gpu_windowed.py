@@ -6,28 +6,9 @@ import pytest
 
 from helpers import ndiff
 from mgm_amd import synth
+from wta_crafted import numpy_windowed_wta
 
 pytestmark = pytest.mark.gpu
-
-
-def numpy_windowed_wta(S, dmin, lo, hi, NDIR, fix):
-    """first strict minimum of the corrected S over [lo, hi] per pixel; window labels outside the volume hold
-    0 - (NDIR-1)*inf (fix) or 0 (no fix)"""
-    ny, nx, L = S.shape
-    with np.errstate(invalid="ignore"):
-        vout = np.float32(0) - np.float32(NDIR - 1) * np.float32(np.inf) if fix else np.float32(0)
-    out = np.full((ny, nx), np.nan, np.float32)
-    cost = np.full((ny, nx), np.inf, np.float32)
-    for y in range(ny):
-        for x in range(nx):
-            best, arg = np.float32(np.inf), None
-            for d in range(int(lo[y, x]), int(hi[y, x]) + 1):
-                v = S[y, x, d - dmin] if 0 <= d - dmin < L else vout
-                if np.isfinite(v) and best > v:
-                    best, arg = v, d
-            if arg is not None:
-                out[y, x], cost[y, x] = arg, best
-    return out, cost
 
 
 @pytest.mark.parametrize("fix", [1, 0])
