@@ -54,7 +54,7 @@ def _read(path):
 def build(force=False, verbose=False):
     os.makedirs(OBJDIR, exist_ok=True)
     cc = hipcc()
-    headers = [os.path.join(CSRC, "mgm_device.h"), os.path.join(CSRC, "mgm_pass_common.h"), os.path.join(CSRC, "mgm_host.h"), os.path.join(CSRC, "mgm_cost_common.h"),
+    headers = [os.path.join(CSRC, "mgm_device.h"), os.path.join(CSRC, "mgm_pass_common.h"), os.path.join(CSRC, "mgm_lds_dma.h"), os.path.join(CSRC, "mgm_host.h"), os.path.join(CSRC, "mgm_cost_common.h"),
                os.path.join(CSRC, "mgm_geom.h"), os.path.join(CSRC, "mgm_planner.h"), os.path.join(CSRC, "mgm_fillplan.h"),
                os.path.join(HERE, "..", "include", "mgm_hip.h"),
                os.path.abspath(__file__)]

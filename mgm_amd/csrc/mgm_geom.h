@@ -44,11 +44,38 @@ constexpr int kRelWaves = 4, kRelLines = 16, kRelRing = 4, kRelStage = 8, kLdsBy
 constexpr int rel_hand_floats(bool one_slab, int slots, bool fh2) { return (fh2 ? 3 * slots + 2 * (slots / 16) : (one_slab ? slots + 2 * (slots / 16) : 2 * slots)) + 4; }
 // LDS bytes of a workgroup: the lines' rings, the hand ring (a second one with anti-diagonal passes), records and weights, the cost
 // pieces, the loader's words, the ticket, the lines' state
-constexpr long long rel_lds_bytes(bool one_slab, int slots, int cb, bool fh2, bool diag)
+constexpr long long rel_wg_lds_bytes(bool one_slab, int slots, int cb, bool fh2, bool diag)
 {
     const long long HS = rel_hand_floats(one_slab, slots, fh2);
     return 4 * (kRelLines * kRelRing * HS + (diag ? 2 : 1) * kRelStage * HS + 2 * kRelStage * kRelLines * 4) + (long long)kRelStage * kRelLines * slots * cb +
            4 * (kRelStage + 4) + 16 + 4 * kRelLines * 24;
+}
+
+// The build macros of the second build of K3 that its kernels (mgm_pass2.hip, one unit per LPL) and its dispatch unit
+// (mgm_pass2_dispatch.hip) both read -- MGM_P2_DEFINES of a tuning or development build reaches both, and the defaults stand here alone.
+#ifndef MGM_P2_NC
+#define MGM_P2_NC 14       // lines per band (compute waves) with fp32 costs, up to 256 labels
+#endif
+#ifndef MGM_P2_C8_NL
+#define MGM_P2_C8_NL 1     // loader waves with compact costs
+#endif
+#ifndef MGM_P2_C8_NC
+#define MGM_P2_C8_NC (16 - MGM_P2_C8_NL)   // lines per band with compact costs (tuning experiments: 7)
+#endif
+#ifndef MGM_P2_DEV
+#define MGM_P2_DEV 0   // 1: in-kernel timers and experiment switches (development builds: MGM_P2_DEFINES=-DMGM_P2_DEV=1);
+#endif                 // the run-time tests alone cost the issue-bound FH kernel 6 %, so product builds compile them out
+#ifndef MGM_P2_TIMELINE
+#define MGM_P2_TIMELINE 0  // 1: the queue kernels record, per work item, start / end / time waited for the predecessor band / where it
+#endif                     // ran (PassParams::tl; MGM_HIP_TIMELINE=<file>; tools/timeline.py).  Variant builds only: tools/sweep_build.sh tl -DMGM_P2_TIMELINE=1
+// Lines per band of the second build at LPL * 64 labels, 0 = no such unit.  `compact`: compact costs in a form this label count has
+// (c8_supported, mgm_fillplan.h); they need fewer loader waves.  The planner sizes bands by this (pass2_lines) and the kernels their
+// workgroups (Plan::NC, mgm_pass2.hip, which asserts the two equal).
+constexpr int pass2_band_lines(int lpl, bool compact)
+{
+    if (lpl == 1 || lpl == 2 || lpl == 3 || lpl == 4) return compact ? MGM_P2_C8_NC : MGM_P2_NC;
+    if (lpl == 6 || lpl == 8 || lpl == 12 || lpl == 16) return 7;  // (768 / 1024 labels: round 4)
+    return 0;
 }
 
 // One launch of the pass kernel may aggregate several cost volumes of identical geometry (the

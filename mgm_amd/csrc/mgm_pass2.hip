@@ -22,6 +22,8 @@
 //     in-line dependency) as TWO strips from the image edges inwards (see
 //     `strips` in pass2_item), and their workgroups stay and work per-XCD queues
 //     of work items off (see k_pass2, XCDQ).
+// The primitives under this -- LDS-DMA, the counted wait, the opaque LDS reads, the sc1 stores, the tag test -- are
+// mgm_lds_dma.h's, shared with mgm_pass_rel.hip; each carries its rule there.
 //
 // Used when every slab is a whole number of 16-byte DMA pieces (L == 64*LPL,
 // LPL in {1,2,3,4,6,8}); other label counts run padded to the next such count,
@@ -29,33 +31,10 @@
 // penalties -- take the first build.
 #include <type_traits>
 
-#include "mgm_pass_common.h"
+#include "mgm_lds_dma.h"
 
 namespace mgm {
 
-typedef __attribute__((address_space(3))) void *lds_vptr;
-typedef const __attribute__((address_space(1))) void *glb_vptr;
-
-// One 16-byte-per-lane LDS-DMA piece: lane l moves src[l*4 .. l*4+3] to
-// dst_base[l*4 ..] (LDS destination = wave-uniform base + 16*lane).
-template <int AUX>
-__device__ __forceinline__ void dma16(const float *src_lane, float *dst_base)
-{
-    __builtin_amdgcn_global_load_lds((glb_vptr)src_lane, (lds_vptr)dst_base, 16, 0, AUX);
-}
-template <int AUX>
-__device__ __forceinline__ void dma4(const void *src_lane, void *dst_base)
-{
-    __builtin_amdgcn_global_load_lds((glb_vptr)src_lane, (lds_vptr)dst_base, 4, 0, AUX);
-}
-constexpr int AUX_SC1 = 16;  // agent-scope (L1-bypassing) cache policy bit
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt()
-{
-    static_assert(N >= 0 && N <= 63, "vmcnt is a 6-bit counter");
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
 // (timeline words go out through a GLOBAL-address-space pointer made from the integer value, and the switch is an int: a
 // null test of the generic pointer inside the queue kernels trips this compiler -- "Illegal instruction detected: Operand
 // has incorrect register class", V_CMP_NE_U32 on src_shared_base -- as the development timers did, mgm_pass2.hip:launch2_one)
@@ -71,46 +50,7 @@ __device__ __forceinline__ void step_barrier(bool skip = false)
     if (!skip) __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
 }
-// LDS read the compiler must not order against pending LDS-DMA itself (it would
-// drain vmcnt): the landing of the word is guaranteed by the counted wait.
-__device__ __forceinline__ unsigned lds_read_u32_opaque(const unsigned *p)
-{
-    unsigned v;
-    const unsigned a = (unsigned)(uintptr_t)(__attribute__((address_space(3))) const unsigned *)p;
-    asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"(a) : "memory");
-    return v;
-}
-
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ u32x4 lds_read_b128_opaque(const float *p)
-{
-    u32x4 v;
-    const unsigned a = (unsigned)(uintptr_t)(__attribute__((address_space(3))) const float *)p;
-    asm volatile("ds_read_b128 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"(a) : "memory");
-    return v;
-}
-
-// Write-through (sc1) slab store in the widest pieces the slab allows: narrow sc1 stores are one
-// fabric write each, so 4 x dword costs ~6x the time of one dwordx4 (MI355X_MICROARCH.md).
-// Inline asm because clang has no 16-byte agent-scope store; the trailing s_nop keeps the data
-// registers intact until the store has read them.  Not counted by the compiler's vmcnt
-// bookkeeping -- compute waves issue no loads, and every wait on these stores is explicit.
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ void st_sc1_x4(float *p, float a, float b, float c, float d)
-{
-    const f32x4 v = {a, b, c, d};
-    asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(p), "v"(v) : "memory");
-}
-__device__ __forceinline__ void st_sc1_x2(float *p, float a, float b)
-{
-    const f32x2 v = {a, b};
-    asm volatile("global_store_dwordx2 %0, %1, off sc1\n\ts_nop 1" ::"v"(p), "v"(v) : "memory");
-}
-__device__ __forceinline__ void st_sc1_x1(float *p, float a)
-{
-    asm volatile("global_store_dword %0, %1, off sc1\n\ts_nop 1" ::"v"(p), "v"(a) : "memory");
-}
+// A slab as write-through (sc1) stores in the widest pieces it allows (mgm_lds_dma.h: a narrow sc1 store costs what a wide one does)
 template <int LPL>
 __device__ __forceinline__ void store_slab_sc1_wide(float *slab, int lane, const float (&v)[LPL])
 {
@@ -151,24 +91,9 @@ constexpr int sc1_store_count() { return LPL == 3 || LPL == 6 ? 2 : (LPL + 3) / 
 #ifndef MGM_P2_ONEB_WPE
 #define MGM_P2_ONEB_WPE 4       // ... the queue kernels of launches that run ONE band per CU (k_pass2, ONEB)
 #endif
-#ifndef MGM_P2_NC
-#define MGM_P2_NC 14
-#endif
+// (MGM_P2_NC, MGM_P2_C8_NL, MGM_P2_C8_NC, MGM_P2_DEV, MGM_P2_TIMELINE: mgm_geom.h -- the dispatch unit reads them too)
 #ifndef MGM_P2_LDS_KB
 #define MGM_P2_LDS_KB 78
-#endif
-#ifndef MGM_P2_DEV
-#define MGM_P2_DEV 0   // 1: in-kernel timers and experiment switches (development builds: MGM_P2_DEFINES=-DMGM_P2_DEV=1);
-#endif                 // the run-time tests alone cost the issue-bound FH kernel 6 %, so product builds compile them out
-
-#ifndef MGM_P2_TIMELINE
-#define MGM_P2_TIMELINE 0  // 1: the queue kernels record, per work item, start / end / time waited for the predecessor band / where it
-#endif                     // ran (PassParams::tl; MGM_HIP_TIMELINE=<file>; tools/timeline.py).  Variant builds only: tools/sweep_build.sh tl -DMGM_P2_TIMELINE=1
-#ifndef MGM_P2_C8_NL
-#define MGM_P2_C8_NL 1
-#endif
-#ifndef MGM_P2_C8_NC
-#define MGM_P2_C8_NC (16 - MGM_P2_C8_NL)   // lines per band with compact costs (tuning experiments: 7)
 #endif
 #ifndef MGM_P2_MAXD
 #define MGM_P2_MAXD 2   // steps of DMA in flight, the shallow build (throughput-bound launches of many volumes)
@@ -557,8 +482,7 @@ __device__ __forceinline__ void pass2_item(const PassParams &P, const int ticket
                         for (int c = 0; c < IPS; c++)
                             if (c * 64 + lane < LPL * 16) {
                                 const u32x4 v = lds_read_b128_opaque(Hring + vslot * NSLP + q * LP + c * 256 + lane * 4);
-                                // all four sign bits must equal the expected tag
-                                ok = ok && (tag_in ? ((v.x & v.y & v.z & v.w) >> 31) != 0u : ((v.x | v.y | v.z | v.w) >> 31) == 0u);
+                                ok = ok && hand_tagged(v, tag_in);  // all four sign bits must equal the expected tag
                             }
                     if (__builtin_amdgcn_ballot_w64(!ok) == 0ull) break;
                     if (spins == 0) n_slow++;
@@ -1134,6 +1058,18 @@ __global__ void __launch_bounds__((Plan<LPL, 1, true, C8>::NC + Plan<LPL, 1, tru
 #ifndef MGM_P2_LPL
 #error "compile with -DMGM_P2_LPL=<1|2|3|4|6|8|12|16>"
 #endif
+// The planner sizes bands by pass2_lines() = pass2_band_lines (mgm_geom.h), the kernels their workgroups by Plan::NC: one rule,
+// checked for fp32 costs and for compact costs of one and two bytes where this label count has such instances.
+template <int LPL, int C8, bool DEEP>
+constexpr bool plan_lines_agree()
+{
+    if constexpr (pass2_instance(false, LPL, false, false, 1, C8, 1, DEEP, false, false, false))
+        return P2Lds<LPL, false, false, 1, C8, DEEP>::PL::NC == pass2_band_lines(LPL, C8 != 0);
+    else
+        return true;
+}
+static_assert(plan_lines_agree<MGM_P2_LPL, 0, false>() && plan_lines_agree<MGM_P2_LPL, 1, false>() && plan_lines_agree<MGM_P2_LPL, 2, true>(),
+              "Plan::NC and pass2_band_lines (mgm_geom.h) disagree on the lines per band: the planner would size bands for another workgroup");
 template <>
 hipError_t launch_pass2_lpl<MGM_P2_LPL>(const PassParams &p, const PassKernelChoice &c, int ntasks, hipStream_t s)
 {

@@ -24,9 +24,11 @@
 // hand-off through global memory in self-validating slots (the launch's tag in every word's sign bit), work items by atomic ticket.  Not built here (the dense path keeps them): FH with TSGM = 2 without weights
 // (update_cost2_trunclinear and its boundary fix-up), windows wider than 62 labels, costs that are not bytes, P2 = +INF, negative
 // penalties or weights (the tags).  (Round 6: TSGM = 2 without weights, Hirschmueller -- update_cost2 -- runs here, PUBE with halved terms.)
+// The LDS-DMA, the counted waits that retire it, the opaque LDS accesses, the sc1 stores and the tag test are mgm_lds_dma.h's
+// (one copy for this file and mgm_pass2.hip, each with its rule).
 #include <algorithm>
 
-#include "mgm_pass_common.h"
+#include "mgm_lds_dma.h"
 
 namespace mgm {
 
@@ -40,49 +42,6 @@ constexpr int RD4 = kRelRing;  // ring slots per line
 constexpr int SD = kRelStage;  // slots of the rings the loader wave fills (costs, records, weights, the previous band's slabs)
 static_assert(RR == NW * GL, "a band is every wave's lines");
 
-typedef __attribute__((address_space(3))) void *rel_lds_vptr;
-typedef const __attribute__((address_space(1))) void *rel_glb_vptr;
-// LDS-DMA: lane l moves 16 (4) bytes from its own source address to dst_base + 16 l (4 l): no VGPR round trip, so the
-// compiler has nothing to wait for, and the loader retires its loads with COUNTED waits (mgm_pass2.hip does the same)
-template <int AUX>
-__device__ __forceinline__ void rel_dma16(const void *src_lane, void *dst_base)
-{
-    __builtin_amdgcn_global_load_lds((rel_glb_vptr)src_lane, (rel_lds_vptr)dst_base, 16, 0, AUX);
-}
-template <int AUX>
-__device__ __forceinline__ void rel_dma4(const void *src_lane, void *dst_base)
-{
-    __builtin_amdgcn_global_load_lds((rel_glb_vptr)src_lane, (rel_lds_vptr)dst_base, 4, 0, AUX);
-}
-constexpr int REL_SC1 = 16;  // agent-scope (L1-bypassing) cache policy bit
-template <int N>
-__device__ __forceinline__ void rel_wait_vmcnt()
-{
-    static_assert(N >= 0 && N <= 63, "vmcnt is a 6-bit counter");
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-// LDS read the compiler must not order against pending LDS-DMA itself (it would drain vmcnt): the counted wait has made
-// sure the word landed
-__device__ __forceinline__ unsigned rel_lds_read_opaque(const unsigned *p)
-{
-    unsigned v;
-    const unsigned a = (unsigned)(uintptr_t)(__attribute__((address_space(3))) const unsigned *)p;
-    asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"(a) : "memory");
-    return v;
-}
-typedef unsigned rel_u4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ rel_u4 rel_lds_read128_opaque(const float *p)
-{
-    rel_u4 v;
-    const unsigned a = (unsigned)(uintptr_t)(__attribute__((address_space(3))) const float *)p;
-    asm volatile("ds_read_b128 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"(a) : "memory");
-    return v;
-}
-__device__ __forceinline__ void rel_lds_write128_opaque(float *p, rel_u4 v)
-{
-    const unsigned a = (unsigned)(uintptr_t)(__attribute__((address_space(3))) float *)p;
-    asm volatile("ds_write_b128 %0, %1" ::"v"(a), "v"(v) : "memory");
-}
 constexpr int REL_BIAS = 1 << 24;  // a hand-off slot holds base + REL_BIAS: a positive word, its sign bit free for the tag
 
 // ---- the relative copy of a ragged volume ------------------------------------------------------------------------------
@@ -229,19 +188,6 @@ hipError_t launch_rel_expand(const uint8_t *rel8, const int *relb, long long npi
     const long long n = npix * L;
     hipLaunchKernelGGL(k_rel_expand, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, rel8, relb, n, L, dmin, slots, cb, C);
     return hipGetLastError();
-}
-
-// write-through (sc1) stores in 16-byte pieces: narrow sc1 stores are one fabric write each (MI355X_MICROARCH.md, "stores of each
-// flavour"; the second build's hand-off learned it in round 3) -- the band hand-off below leaves as 16 x 16 bytes per slab, not 64 x 4
-typedef float relf4 __attribute__((ext_vector_type(4)));
-typedef float relf2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ void rel_st_sc1_x4(float *p, relf4 v)
-{
-    asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(p), "v"(v) : "memory");
-}
-__device__ __forceinline__ void rel_st_sc1_x2(float *p, relf2 v)
-{
-    asm volatile("global_store_dwordx2 %0, %1, off sc1\n\ts_nop 1" ::"v"(p), "v"(v) : "memory");
 }
 
 // minimum over a row of 16 lanes, in every lane of the row (quad swaps, then the two mirrors: 4 DPP slots, no LDS crossbar)
@@ -440,18 +386,18 @@ __global__ void __launch_bounds__((NW + 1) * 64) k_pass_rel(const RelParams P)
             const int slot = ht & (SD - 1);
 #pragma unroll
             for (int n = 0; n < CI; n++) {
-                rel_dma16<0>(cptr[n], cring + slot * RR * CBY + n * 1024);
+                dma16<0>(cptr[n], cring + slot * RR * CBY + n * 1024);
                 const bool adv = ci[n] >= ca[n] && ci[n] < cb[n];
                 cptr[n] += adv ? istep * CBY : 0;
                 ci[n]++;
             }
             if (weighted) {
-                rel_dma4<0>(wptr, wring + slot * RR * 4);
+                dma4<0>(wptr, wring + slot * RR * 4);
                 const bool adv = wi >= wa && wi < wb;
                 wptr += adv ? istep : 0;
                 wi++;
             }
-            if (lane < RR) rel_dma16<0>(mptr, mring + slot * RR * 4);
+            if (lane < RR) dma16<0>(mptr, mring + slot * RR * 4);
             {
                 const bool adv = mi >= ma && mi < mb;
                 mptr += adv ? istep : 0;
@@ -460,11 +406,11 @@ __global__ void __launch_bounds__((NW + 1) * 64) k_pass_rel(const RelParams P)
             // the previous band's slot of pixel ht, whatever it holds by now: validate() looks at it when its step comes
 #pragma unroll
             for (int n = 0; n < HI; n++)
-                if (lane + 64 * n < NPIECE) rel_dma16<REL_SC1>(hptr + (diag ? (long long)wmax * HS : 0) + 256 * n, hring + slot * HS + 256 * n);
+                if (lane + 64 * n < NPIECE) dma16<AUX_SC1>(hptr + (diag ? (long long)wmax * HS : 0) + 256 * n, hring + slot * HS + 256 * n);
             if (diag)
 #pragma unroll
                 for (int n = 0; n < HI; n++)
-                    if (lane + 64 * n < NPIECE) rel_dma16<REL_SC1>(hptr + 256 * n, hring2 + slot * HS + 256 * n);
+                    if (lane + 64 * n < NPIECE) dma16<AUX_SC1>(hptr + 256 * n, hring2 + slot * HS + 256 * n);
             hptr += (ht < hlast) ? hstep : 0;
             ht++;
         };
@@ -472,7 +418,7 @@ __global__ void __launch_bounds__((NW + 1) * 64) k_pass_rel(const RelParams P)
         // fetching it again until it is; then take the tags off (and the bias off the base) so that the compute waves read it like
         // any ring entry.
         auto validate_one = [&](float *ent, const float *slot) {
-            rel_u4 v[HI];
+            u32x4 v[HI];
             unsigned spins = 0;
             unsigned long long w0 = 0;
             for (;;) {
@@ -480,8 +426,8 @@ __global__ void __launch_bounds__((NW + 1) * 64) k_pass_rel(const RelParams P)
 #pragma unroll
                 for (int n = 0; n < HI; n++)
                     if (lane + 64 * n < NPIECE) {
-                        v[n] = rel_lds_read128_opaque(ent + (lane + 64 * n) * 4);
-                        ok = ok && (tag ? ((v[n].x & v[n].y & v[n].z & v[n].w) >> 31) != 0u : ((v[n].x | v[n].y | v[n].z | v[n].w) >> 31) == 0u);
+                        v[n] = lds_read_b128_opaque(ent + (lane + 64 * n) * 4);
+                        ok = ok && hand_tagged(v[n], tag);
                     }
                 if (__builtin_amdgcn_ballot_w64(!ok) == 0ull) break;
                 if (spins == 0) {
@@ -492,12 +438,12 @@ __global__ void __launch_bounds__((NW + 1) * 64) k_pass_rel(const RelParams P)
                 __builtin_amdgcn_s_sleep(2);
 #pragma unroll
                 for (int n = 0; n < HI; n++)
-                    if (lane + 64 * n < NPIECE) rel_dma16<REL_SC1>(slot + (lane + 64 * n) * 4, ent + 256 * n);
-                rel_wait_vmcnt<0>();
+                    if (lane + 64 * n < NPIECE) dma16<AUX_SC1>(slot + (lane + 64 * n) * 4, ent + 256 * n);
+                wait_vmcnt<0>();
                 if (((++spins) & 255u) == 0) {
-                    if (lane == 0) rel_dma4<REL_SC1>(P.err, hprog);
-                    rel_wait_vmcnt<0>();
-                    const unsigned e = (unsigned)__builtin_amdgcn_readfirstlane((int)rel_lds_read_opaque(hprog));
+                    if (lane == 0) dma4<AUX_SC1>(P.err, hprog);
+                    wait_vmcnt<0>();
+                    const unsigned e = (unsigned)__builtin_amdgcn_readfirstlane((int)lds_read_u32_opaque(hprog));
                     if (spins > (SPIN_LIMIT >> 2) || e != 0) {
                         if (lane == 0) __hip_atomic_store(P.err, 1u, RLX_AGENT);
                         dead = true;
@@ -511,7 +457,7 @@ __global__ void __launch_bounds__((NW + 1) * 64) k_pass_rel(const RelParams P)
                 if (lane + 64 * n < NPIECE) {
                     v[n].x &= 0x7fffffffu, v[n].y &= 0x7fffffffu, v[n].z &= 0x7fffffffu, v[n].w &= 0x7fffffffu;
                     if (lane + 64 * n == HOFF / 4) v[n].y -= (unsigned)REL_BIAS;  // the piece (minimum, base + bias, padding, padding)
-                    rel_lds_write128_opaque(ent + (lane + 64 * n) * 4, v[n]);
+                    lds_write_b128_opaque(ent + (lane + 64 * n) * 4, v[n]);
                 }
         };
         auto validate = [&](int t) {
@@ -534,13 +480,13 @@ __global__ void __launch_bounds__((NW + 1) * 64) k_pass_rel(const RelParams P)
         auto retire = [&]() {  // all but the newest LD - 1 steps of DMA have landed
             const int n = (CI + 1 + (diag ? 2 * HI : HI) + (weighted ? 1 : 0)) * (LD - 1);  // (3 .. 14 instructions per step, 1 .. 4 steps)
             switch (n) {
-#define MGM_REL_W(k) case k: rel_wait_vmcnt<k>(); break;
+#define MGM_REL_W(k) case k: wait_vmcnt<k>(); break;
 #define MGM_REL_W4(k) MGM_REL_W(k) MGM_REL_W(k + 1) MGM_REL_W(k + 2) MGM_REL_W(k + 3)
                 MGM_REL_W(3) MGM_REL_W4(4) MGM_REL_W4(8) MGM_REL_W4(12) MGM_REL_W4(16) MGM_REL_W4(20) MGM_REL_W4(24) MGM_REL_W4(28) MGM_REL_W4(32) MGM_REL_W4(36)
                 MGM_REL_W4(40) MGM_REL_W4(44) MGM_REL_W4(48) MGM_REL_W4(52) MGM_REL_W(56)
 #undef MGM_REL_W4
 #undef MGM_REL_W
-            default: rel_wait_vmcnt<0>(); break;  // (a count not listed: wait for everything -- correct, only slower)
+            default: wait_vmcnt<0>(); break;  // (a count not listed: wait for everything -- correct, only slower)
             }
         };
         // Step s + 1 reads, of the previous band's line(s), the slots of local pixels <= s + 1 where the walk reads the fwd neighbour
@@ -568,7 +514,7 @@ __global__ void __launch_bounds__((NW + 1) * 64) k_pass_rel(const RelParams P)
                 lph[0] += l1 - l0, lph[1] += l2 - l1, lph[2] += l3 - l2;
             }
         }
-        rel_wait_vmcnt<0>();  // (the DMAs beyond the last step)
+        wait_vmcnt<0>();  // (the DMAs beyond the last step)
         if constexpr (MGM_REL_PHASES != 0)
             if (P.tl && lane == 0) {
                 unsigned long long *w = P.tl + (long long)gridDim.x * 8 + (long long)*s_task * 16 + 12;
@@ -688,7 +634,7 @@ __global__ void __launch_bounds__((NW + 1) * 64) k_pass_rel(const RelParams P)
 #pragma unroll
                 for (int k = 0; k < NK; k++) {
                     const float *src = entry(k, i);
-                    const relf4 hdr = *reinterpret_cast<const relf4 *>(src + HOFF);  // (minimum, base, highest slot, -): one unconditional 16-byte read
+                    const f32x4 hdr = *reinterpret_cast<const f32x4 *>(src + HOFF);  // (minimum, base, highest slot, -): one unconditional 16-byte read
                     const float hmin = hdr.x, hbase = hdr.y, hhi = hdr.z;  // (scalars first: __builtin_bit_cast of the vector ELEMENT hdr[1] read element 0)
                     mk[k] = interior ? hmin : 0.0f;
                     const int sh = bp - __builtin_bit_cast(int, hbase);
@@ -796,7 +742,7 @@ __global__ void __launch_bounds__((NW + 1) * 64) k_pass_rel(const RelParams P)
             if (act)
 #pragma unroll
                 for (int h = 0; h < SPL / 4; h++)
-                    reinterpret_cast<relf4 *>(Lrb + pix * SLOTS + SPL * li)[h] = relf4{Lv[4 * h], Lv[4 * h + 1], Lv[4 * h + 2], Lv[4 * h + 3]};
+                    reinterpret_cast<f32x4 *>(Lrb + pix * SLOTS + SPL * li)[h] = f32x4{Lv[4 * h], Lv[4 * h + 1], Lv[4 * h + 2], Lv[4 * h + 3]};
 
             // what this pixel publishes: its raw slab (Hirschmueller: and the neighbour minima), minimum, base -- or (PUBE) E and FAR
             float lmin = Lv[0];
@@ -826,25 +772,25 @@ __global__ void __launch_bounds__((NW + 1) * 64) k_pass_rel(const RelParams P)
                 fh_scan<SPL, false, GL>(Bv, P1, lane, sw);
             }
             const float farv = PUBE ? pubm : f_inf();  // what a disparity this pixel does not have reads as
-            const relf4 far4 = {farv, farv, farv, farv};
-            const relf4 hdr4 = {pubm, __builtin_bit_cast(float, bp), __builtin_bit_cast(float, rh), 0.0f};  // (minimum, base, highest slot of the range)
+            const f32x4 far4 = {farv, farv, farv, farv};
+            const f32x4 hdr4 = {pubm, __builtin_bit_cast(float, bp), __builtin_bit_cast(float, rh), 0.0f};  // (minimum, base, highest slot of the range)
             constexpr int GP = SPL / 4;  // 16-byte pieces of a guard (a lane's worth of words) and of a lane's values
             if (act) {
                 float *ent = ring + (ln * RD4 + (i & (RD4 - 1))) * HS;
 #pragma unroll
                 for (int h = 0; h < GP; h++) {
-                    reinterpret_cast<relf4 *>(ent + GO + SPL * li)[h] = relf4{pubv[4 * h], pubv[4 * h + 1], pubv[4 * h + 2], pubv[4 * h + 3]};
-                    if constexpr (NS == 2) reinterpret_cast<relf4 *>(ent + SLOTS + SPL * li)[h] = relf4{N[4 * h], N[4 * h + 1], N[4 * h + 2], N[4 * h + 3]};
+                    reinterpret_cast<f32x4 *>(ent + GO + SPL * li)[h] = f32x4{pubv[4 * h], pubv[4 * h + 1], pubv[4 * h + 2], pubv[4 * h + 3]};
+                    if constexpr (NS == 2) reinterpret_cast<f32x4 *>(ent + SLOTS + SPL * li)[h] = f32x4{N[4 * h], N[4 * h + 1], N[4 * h + 2], N[4 * h + 3]};
                     if constexpr (FH2) {
-                        reinterpret_cast<relf4 *>(ent + FOFF + SPL * li)[h] = relf4{Fv[4 * h], Fv[4 * h + 1], Fv[4 * h + 2], Fv[4 * h + 3]};
-                        reinterpret_cast<relf4 *>(ent + BOFF + SPL * li)[h] = relf4{Bv[4 * h], Bv[4 * h + 1], Bv[4 * h + 2], Bv[4 * h + 3]};
+                        reinterpret_cast<f32x4 *>(ent + FOFF + SPL * li)[h] = f32x4{Fv[4 * h], Fv[4 * h + 1], Fv[4 * h + 2], Fv[4 * h + 3]};
+                        reinterpret_cast<f32x4 *>(ent + BOFF + SPL * li)[h] = f32x4{Bv[4 * h], Bv[4 * h + 1], Bv[4 * h + 2], Bv[4 * h + 3]};
                     }
                 }
                 if constexpr (GUARD) {  // lanes 0 .. GP-1: the guard before the values, GP .. 2 GP - 1: the one after, 2 GP: the header
                     if (li < 2 * GP + 1)
-                        *reinterpret_cast<relf4 *>(ent + (li < GP ? 4 * li : (li < 2 * GP ? GO + SLOTS + 4 * (li - GP) : HOFF))) = li == 2 * GP ? hdr4 : far4;
+                        *reinterpret_cast<f32x4 *>(ent + (li < GP ? 4 * li : (li < 2 * GP ? GO + SLOTS + 4 * (li - GP) : HOFF))) = li == 2 * GP ? hdr4 : far4;
                 } else {
-                    if (li == 0) *reinterpret_cast<relf2 *>(ent + HOFF) = relf2{pubm, __builtin_bit_cast(float, bp)};
+                    if (li == 0) *reinterpret_cast<f32x2 *>(ent + HOFF) = f32x2{pubm, __builtin_bit_cast(float, bp)};
                 }
             }
             if (to_global) {
@@ -853,26 +799,26 @@ __global__ void __launch_bounds__((NW + 1) * 64) k_pass_rel(const RelParams P)
                     // the hand-off to the next band: write-through 16-byte stores straight from the registers, every word tagged
                     float *dstg = hand_out + (hpub0 + i * hpubs);
                     if (pubs && act) {
-                        auto tagged = [&](relf4 x) {
-                            rel_u4 u = __builtin_bit_cast(rel_u4, x);
+                        auto tagged = [&](f32x4 x) {
+                            u32x4 u = __builtin_bit_cast(u32x4, x);
                             u.x |= tag, u.y |= tag, u.z |= tag, u.w |= tag;
-                            return __builtin_bit_cast(relf4, u);
+                            return __builtin_bit_cast(f32x4, u);
                         };
 #pragma unroll
                         for (int h = 0; h < GP; h++) {
-                            rel_st_sc1_x4(dstg + GO + SPL * li + 4 * h, tagged(relf4{pubv[4 * h], pubv[4 * h + 1], pubv[4 * h + 2], pubv[4 * h + 3]}));
-                            if constexpr (NS == 2) rel_st_sc1_x4(dstg + SLOTS + SPL * li + 4 * h, tagged(relf4{N[4 * h], N[4 * h + 1], N[4 * h + 2], N[4 * h + 3]}));
+                            st_sc1_x4(dstg + GO + SPL * li + 4 * h, tagged(f32x4{pubv[4 * h], pubv[4 * h + 1], pubv[4 * h + 2], pubv[4 * h + 3]}));
+                            if constexpr (NS == 2) st_sc1_x4(dstg + SLOTS + SPL * li + 4 * h, tagged(f32x4{N[4 * h], N[4 * h + 1], N[4 * h + 2], N[4 * h + 3]}));
                             if constexpr (FH2) {
-                                rel_st_sc1_x4(dstg + FOFF + SPL * li + 4 * h, tagged(relf4{Fv[4 * h], Fv[4 * h + 1], Fv[4 * h + 2], Fv[4 * h + 3]}));
-                                rel_st_sc1_x4(dstg + BOFF + SPL * li + 4 * h, tagged(relf4{Bv[4 * h], Bv[4 * h + 1], Bv[4 * h + 2], Bv[4 * h + 3]}));
+                                st_sc1_x4(dstg + FOFF + SPL * li + 4 * h, tagged(f32x4{Fv[4 * h], Fv[4 * h + 1], Fv[4 * h + 2], Fv[4 * h + 3]}));
+                                st_sc1_x4(dstg + BOFF + SPL * li + 4 * h, tagged(f32x4{Bv[4 * h], Bv[4 * h + 1], Bv[4 * h + 2], Bv[4 * h + 3]}));
                             }
                         }
-                        const relf4 hd = {pubm, __builtin_bit_cast(float, bp + REL_BIAS), __builtin_bit_cast(float, rh), 0.0f};
+                        const f32x4 hd = {pubm, __builtin_bit_cast(float, bp + REL_BIAS), __builtin_bit_cast(float, rh), 0.0f};
                         if constexpr (GUARD) {
                             if (li < 2 * GP + 1)
-                                rel_st_sc1_x4(dstg + (li < GP ? 4 * li : (li < 2 * GP ? GO + SLOTS + 4 * (li - GP) : HOFF)), tagged(li == 2 * GP ? hd : far4));
+                                st_sc1_x4(dstg + (li < GP ? 4 * li : (li < 2 * GP ? GO + SLOTS + 4 * (li - GP) : HOFF)), tagged(li == 2 * GP ? hd : far4));
                         } else {
-                            if (li == 0) rel_st_sc1_x4(dstg + HOFF, tagged(hd));
+                            if (li == 0) st_sc1_x4(dstg + HOFF, tagged(hd));
                         }
                     }
                 }
@@ -895,7 +841,7 @@ __global__ void __launch_bounds__((NW + 1) * 64) k_pass_rel(const RelParams P)
 }
 
 // A table from the planner's choice (plan_rel, mgm_planner.h) to its instance: the instances are those pass_rel_instance admits, the
-// LDS request (rel_lds_bytes, mgm_geom.h, with the floor that sets the workgroups per CU) is the choice's.
+// LDS request (rel_wg_lds_bytes, mgm_geom.h, with the floor that sets the workgroups per CU) is the choice's.
 hipError_t launch_pass_rel(const RelParams &p, const PassKernelChoice &c, int ntasks, hipStream_t s)
 {
     if (c.family != kPassRel) return hipErrorInvalidValue;

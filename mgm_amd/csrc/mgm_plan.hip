@@ -865,7 +865,7 @@ int run_rel(mgm_ctx *c, const mgm_cv *const *Cs, const mgm_img *const *w8s, int 
     RelRequest q{};
     q.nx = nx, q.ny = ny, q.NDIR = NDIR, q.nb = nb, q.MGM = MGM, q.fh = fh ? 1 : 0, q.pube = pube ? 1 : 0, q.fh2 = fh2 ? 1 : 0, q.slots = slots, q.cb = rcb;
     q.R = kRelLines, q.HS = rel_hand_floats(fh || pube, slots, fh2);
-    q.diag_fits = rel_lds_bytes(fh || pube, slots, rcb, fh2, true) <= kLdsBytes ? 1 : 0;
+    q.diag_fits = rel_wg_lds_bytes(fh || pube, slots, rcb, fh2, true) <= kLdsBytes ? 1 : 0;
     q.num_cu = c->num_cu;
     q.rel_wg = (int)tune_num("rel_wg", 0), q.rel_prio = (int)tune_num("rel_prio", nb <= 1 ? 5 : 0), q.rel_lag = (int)tune_num("rel_lag", 0);
     q.rel_lagd = (int)tune_num("rel_lagd", 0), q.rel_slots = (int)tune_num("rel_slots", 100), q.rel_slope1 = (int)tune_num("rel_slope1", 1);

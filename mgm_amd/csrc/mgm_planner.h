@@ -103,7 +103,7 @@ struct RelRequest {
     int fh, pube, fh2;         // FH potentials; the producer publishes E; update_cost2_trunclinear
     int slots, cb;             // the volumes' range-proportional format
     int R, HS;                 // lines per band, floats per hand-off slot (kRelLines, rel_hand_floats)
-    int diag_fits;             // a workgroup with the second hand ring of the anti-diagonal passes fits the LDS (rel_lds_bytes)
+    int diag_fits;             // a workgroup with the second hand ring of the anti-diagonal passes fits the LDS (rel_wg_lds_bytes)
     int num_cu;
     // tune values: rel_wg 0 = by the launch's shape; rel_prio as resolved by the caller (default 5 for one volume, else 0)
     // rel_multi 0: FH on 64 slots of one-byte costs runs the one-after-the-other build (an A/B switch)
@@ -775,7 +775,7 @@ inline RelPlan plan_rel(const RelRequest &q)
     const int rel_wg = p.rel_wg = q.rel_wg > 0 ? std::min(q.rel_wg, 6) : (nb <= 1 ? (fh ? 2 : 3) : 3);
     // Occupancy through the LDS request, as for the second build: rel_wg workgroups (of 4 compute waves: one per SIMD) share a
     // CU -- one for a launch bound by its chains of bands, more for a batch (throughput): more than a (rel_wg + 1)-th of the LDS
-    kn.lds = (int)std::max(rel_lds_bytes(kn.FH || kn.PUBE, 16 * kn.SPL, kn.CB, kn.FH2 != 0, p.diag_any != 0), (long long)kLdsBytes / (rel_wg + 1) + 1024);
+    kn.lds = (int)std::max(rel_wg_lds_bytes(kn.FH || kn.PUBE, 16 * kn.SPL, kn.CB, kn.FH2 != 0, p.diag_any != 0), (long long)kLdsBytes / (rel_wg + 1) + 1024);
     // the task table: the simulated list schedule of the launch (one ticket counter)
     // (slope of the lock-step diagonal x lines + the lag the MODEL assumes per band.  The tickets are the start order of the
     // simulated schedule, so these constants decide who holds a band slot while it waits: with the hand-off's real ~4 steps on

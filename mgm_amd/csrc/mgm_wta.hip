@@ -860,17 +860,11 @@ __global__ void __launch_bounds__(256) k_wta_rel(const WtaRelParams P)
                 ci = d;
             }
         }
-        auto take = [&](float ov, int oi) {
-            if (ov < cb || (ov == cb && oi < ci)) {
-                cb = ov;
-                ci = oi;
-            }
-        };
         // butterfly over the row of 16 lanes: quad swaps, then the two mirrors
-        take(__builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, cb), 0xB1, 0xf, 0xf, false)), __builtin_amdgcn_update_dpp(0, ci, 0xB1, 0xf, 0xf, false));
-        take(__builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, cb), 0x4E, 0xf, 0xf, false)), __builtin_amdgcn_update_dpp(0, ci, 0x4E, 0xf, 0xf, false));
-        take(__builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, cb), 0x141, 0xf, 0xf, false)), __builtin_amdgcn_update_dpp(0, ci, 0x141, 0xf, 0xf, false));
-        take(__builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, cb), 0x140, 0xf, 0xf, false)), __builtin_amdgcn_update_dpp(0, ci, 0x140, 0xf, 0xf, false));
+        dpp_take<0xB1>(cb, ci);
+        dpp_take<0x4E>(cb, ci);
+        dpp_take<0x141>(cb, ci);
+        dpp_take<0x140>(cb, ci);
         // (1) the window's disparities below the pixel's own range: all `vout`, the first of them is the candidate
         float best = f_inf();
         int bi = 0x7fffffff;

@@ -542,7 +542,7 @@ def _dense_cases():
     for st in STAGE_INPUT:
         out.append(case("p2_weights3_l128_%s" % st, "k_pass2", 2, 1, st, 128, weights=WEIGHTS3))
         out.append(case("p2_weights2_l128_%s" % st, "k_pass2", 2, 1, st, 128, weights=WEIGHTS2))
-    # W2 (the producer publishes both transforms, mgm_pass2.hip:950-951) wants one-byte costs, <= 256 labels and the queues
+    # W2 (the producer publishes both transforms, mgm_pass2.hip:874-875) wants one-byte costs, <= 256 labels and the queues
     out.append(case("p2_w2_l128_dyadic", "k_pass2", 2, 1, "s3", 128, weights=WEIGHTS2, cls="byte", P1=2.0, nx=96, ny=48, flags=((9, "true"),)))
     out.append(case("p2_w2_l256_sweeps", "k_pass2", 4, 1, "sweeps", 256, weights=WEIGHTS2, cls="byte", P1=0.1, nx=96, ny=48, flags=((9, "true"),)))
     out.append(case("p2_weights3_dyadic_l128", "k_pass2", 2, 1, "s3", 128, weights=WEIGHTS3, cls="byte", P1=2.0))
@@ -648,7 +648,7 @@ def dense_case_counts(c, oracle):
 # ---- k_pass_rel: ragged ranges over an image pair whose `ad` costs form the one-byte class ---------------------------------------
 def rel_case(name, slots, MGM, stage, P1, weights=None, nx=48, ny=32, P2f=20000.0, align=None, rel="2"):
     """rel "2": the range-proportional kernels (k_pass_rel, 16 lanes of slots / 16 slots per pixel); "0": the volume stays on its dense
-    hull and k_pass2 takes it, one label range per wave -- with TSGM 2 and no weights through combine_fh2_ragged (mgm_pass2.hip:865-866;
+    hull and k_pass2 takes it, one label range per wave -- with TSGM 2 and no weights through combine_fh2_ragged (mgm_pass2.hip:789-790;
     mgm_pass_common.h: two stand-alone scans of the neighbour's raw slab, then fh_minconv)."""
     hull, width = ((-60, 0), 21) if slots == 64 else ((-200, 10), 100)
     L = hull[1] - hull[0] + 1

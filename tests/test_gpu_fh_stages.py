@@ -25,7 +25,7 @@ DMIN = fm.DMIN
 BAND = 15  # lines per band of k_pass2 up to 256 labels
 # (family, labels per lane, label ranges per wave) the cases are named for: every case asserts the instance it ran on against its
 # own entry, so this set is reached whenever the file's tests pass, in whatever selection or order they run.  "k_pass2 fh2_ragged":
-# k_pass2 on a ragged volume kept on its dense hull with TSGM 2 and no weights, where combine_fh2_ragged runs (mgm_pass2.hip:865-866)
+# k_pass2 on a ragged volume kept on its dense hull with TSGM 2 and no weights, where combine_fh2_ragged runs (mgm_pass2.hip:789-790)
 DECLARED = ({("k_pass2", lpl, 1) for lpl in (1, 2, 3, 4, 6, 8, 12, 16)} | {("k_pass2", 4, 2), ("k_pass2", 4, 4)}
             | {("k_pass", lpl, 1) for lpl in (4, 12, 24, 32)} | {("k_pass_rel", 4, 4), ("k_pass_rel", 8, 4)}
             | {("k_pass2 fh2_ragged", 1, 1), ("k_pass2 fh2_ragged", 4, 1)})
