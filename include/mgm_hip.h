@@ -317,6 +317,29 @@ int mgm_wta_windowed_dev(mgm_ctx *ctx, const mgm_cv *C, int NDIR, int fix_overco
  * last aggregation with NDIR passes, in any slot of a batch (else MGM_ERR_INVALID).  No synchronisation. */
 int mgm_wta_right_dev(mgm_ctx *ctx, const mgm_cv *C, int NDIR, int fix_overcount, const char *refine,
                       mgm_img *outR, mgm_img *outcostR);
+/* The runner-up search (DESIGN.md "runner-up, confidence, uniqueness"; this library's own mode, the reference has none): a third
+ * search of the corrected aggregated volume S of the context's last aggregation of C.  Per pixel, with o = d - dmin:
+ *   winner     o1 = the first strict minimum among the finite entries of S by rising o (mgm_core.cc:592-609: what mgm_aggregate*
+ *              returns without refinement); out1 = (float)(o1 + dmin), cost1 = S(o1) -- always the unrefined S, never vfit's
+ *              v_min; no finite entry: out1 = NaN, cost1 = +INF
+ *   runner-up  o2 = the first strict minimum among the finite entries with |o - o1| > radius; out2 = (float)(o2 + dmin),
+ *              cost2 = S(o2); no winner or no such entry: out2 = NaN, cost2 = +INF
+ * radius >= 0 (negative: MGM_ERR_INVALID); a radius at or beyond the label count is valid and leaves no runner-up anywhere.
+ * out2 / cost2 (and out1 / cost1, each of which may be NULL) are nx x ny x 1 images of C's size (else MGM_ERR_INVALID).  C must
+ * be a dense volume (built from range images: MGM_ERR_UNSUPPORTED; its last aggregation ran on the range-proportional copy:
+ * MGM_ERR_UNSUPPORTED) of the context's last aggregation with NDIR passes, in any slot of a batch (else MGM_ERR_INVALID).  The
+ * call leaves what the context holds of that aggregation untouched: mgm_wta_windowed_dev / mgm_wta_right_dev give the same maps
+ * before and after it.  No synchronisation. */
+int mgm_wta_runnerup_dev(mgm_ctx *ctx, const mgm_cv *C, int NDIR, int fix_overcount, int radius,
+                         mgm_img *out2, mgm_img *cost2, mgm_img *out1, mgm_img *cost1);
+/* Confidence and uniqueness filter from the two costs of mgm_wta_runnerup_dev, per pixel in float:
+ *   conf = 1.0f - cost1 / cost2      one division, one subtraction, whatever IEEE gives: no runner-up -> 1, no winner
+ *                                    (INF / INF) -> NaN, 0 / 0 -> NaN
+ *   out  = conf < ratio ? NaN : d    (a NaN conf keeps d)
+ * d is any map of that size (the command line passes the refined one).  out and conf may each be NULL, not both; out may be d.
+ * All images are one-channel and of one size, ratio is finite and in [0, 1] (else MGM_ERR_INVALID).  No synchronisation. */
+int mgm_uniqueness_dev(mgm_ctx *ctx, const mgm_img *d, const mgm_img *cost1, const mgm_img *cost2, float ratio,
+                       mgm_img *out, mgm_img *conf);
 /* update_dmin_dmax (mgm.cc:120-158; main() uses slack 3, radius 2) followed by the two
  * remove_nonfinite_values_Img calls (mgm.cc:387-388): dminI/dmaxI are updated in place from the disparity map. */
 int mgm_update_ranges_dev(mgm_ctx *ctx, const mgm_img *outoff, mgm_img *dminI, mgm_img *dmaxI, int slack, int radius);

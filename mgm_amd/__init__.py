@@ -33,6 +33,7 @@ ABI_SYMBOLS = [
     "mgm_ctx_set_workspace_limit", "mgm_ctx_mem_info", "mgm_ctx_set_pipeline", "mgm_img_update", "mgm_debug_probe_workspace", "mgm_ctx_set_placement_tries",
     "mgm_debug_wta_stats", "mgm_debug_download_lmin", "mgm_debug_last_pass_kernel",
     "mgm_multiscale_levels", "mgm_zoom_out_dev", "mgm_ranges_zoom_out_dev", "mgm_ranges_from_coarse_dev", "mgm_multiscale_pair_dev",
+    "mgm_wta_runnerup_dev", "mgm_uniqueness_dev",
 ]
 
 MGM_OK, MGM_ERR_INVALID, MGM_ERR_UNSUPPORTED, MGM_ERR_HIP, MGM_ERR_NOMEM, MGM_ERR_INTERNAL = range(6)
@@ -114,6 +115,8 @@ def load_library():
     L.mgm_costvolume_build_ranged_dev.argtypes = [vp, vp, vp, vp, vp, i, i, cp, cp, f, i, pp]
     L.mgm_wta_windowed_dev.argtypes = [vp, vp, i, i, cp, vp, vp, vp, vp]
     L.mgm_wta_right_dev.argtypes = [vp, vp, i, i, cp, vp, vp]
+    L.mgm_wta_runnerup_dev.argtypes = [vp, vp, i, i, i, vp, vp, vp, vp]
+    L.mgm_uniqueness_dev.argtypes = [vp, vp, vp, vp, f, vp, vp]
     L.mgm_update_ranges_dev.argtypes = [vp, vp, vp, vp, i, i]
     L.mgm_leftright_dev.argtypes = [vp, vp, vp, f, vp]
     L.mgm_backproject_dev.argtypes = [vp, vp, vp, vp, vp]
@@ -356,6 +359,49 @@ class Context:
         outcost = outcost or self.new_image(vnx, ny)
         self._chk(self.lib.mgm_wta_right_dev(self.h, Cv.h, NDIR, fix_overcount, refine.encode() if refine else None, out.h, outcost.h))
         return out, outcost
+
+    def wta_runnerup_dev(self, Cv, NDIR, fix_overcount, radius=1, out2=None, cost2=None, want_first=True):
+        """The runner-up search over the context's last aggregation of Cv (mgm_wta_runnerup_dev): device images
+        (out2, cost2, out1, cost1) -- the best label more than `radius` away from the winner and S there, the unrefined winner
+        and S there (None, None with want_first=False)."""
+        nx, ny, _, _ = Cv.dims
+        mine = []  # the images made here: freed if the call fails
+
+        def new():
+            mine.append(self.new_image(nx, ny))
+            return mine[-1]
+        try:
+            out2 = out2 or new()
+            cost2 = cost2 or new()
+            out1 = new() if want_first else None
+            cost1 = new() if want_first else None
+            self._chk(self.lib.mgm_wta_runnerup_dev(self.h, Cv.h, NDIR, fix_overcount, radius, out2.h, cost2.h,
+                                                    out1.h if want_first else None, cost1.h if want_first else None))
+        except Exception:
+            for im in mine:
+                im.free()
+            raise
+        return out2, cost2, out1, cost1
+
+    def uniqueness_dev(self, d, cost1, cost2, ratio, out=None, want_conf=True):
+        """conf = 1 - cost1 / cost2 and out = NaN where conf < ratio, else d (mgm_uniqueness_dev): device images (out, conf).
+        out: an image to write (d itself is allowed), None for a new one, False for none; conf is None with want_conf=False."""
+        _, ny, nx = d.shape
+        mine = []  # the images made here: freed if the call fails
+        try:
+            if out is None:
+                out = self.new_image(nx, ny)
+                mine.append(out)
+            conf = None
+            if want_conf:
+                conf = self.new_image(nx, ny)
+                mine.append(conf)
+            self._chk(self.lib.mgm_uniqueness_dev(self.h, d.h, cost1.h, cost2.h, ratio, out.h if out else None, conf.h if want_conf else None))
+        except Exception:
+            for im in mine:
+                im.free()
+            raise
+        return (out if out else None), conf
 
     def pair_right_from_left(self, u, v, dmin, dmax, P1=8.0, P2=32.0, NDIR=4, TSGM=4, use_fh=0, fix_overcount=1, aP2=1.0, aThresh=5.0,
                              prefilter="none", distance="ad", truncDist=float("inf"), census_win=3, refine="none", tau=1.0, median=0):

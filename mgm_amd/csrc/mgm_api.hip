@@ -575,6 +575,41 @@ int mgm_wta_right_dev(mgm_ctx *c, const mgm_cv *C, int NDIR, int fix_overcount, 
     return run_wta_right(c, C, slot, NDIR, fix_overcount, ridx, vnx, outR->d, outcostR->d);
 }
 
+int mgm_wta_runnerup_dev(mgm_ctx *c, const mgm_cv *C, int NDIR, int fix_overcount, int radius, mgm_img *out2, mgm_img *cost2, mgm_img *out1,
+                         mgm_img *cost1)
+{
+    if (int jr = pipe_join(c)) return jr;  // (pipelined context: run what has been deferred first)
+    if (!c || !C || !out2 || !cost2) return fail(c, MGM_ERR_INVALID, "mgm_wta_runnerup: null argument");
+    if (radius < 0) return fail(c, MGM_ERR_INVALID, "mgm_wta_runnerup: radius must be >= 0");
+    for (const mgm_img *im : {(const mgm_img *)out2, (const mgm_img *)cost2, (const mgm_img *)out1, (const mgm_img *)cost1})
+        if (im && (im->nx != C->nx || im->ny != C->ny || im->nch != 1))
+            return fail(c, MGM_ERR_INVALID, "mgm_wta_runnerup: image size mismatch (every output is nx x ny x 1, the volume's)");
+    const int L = C->dmax - C->dmin + 1;
+    if (C->rlo) return fail(c, MGM_ERR_UNSUPPORTED, "mgm_wta_runnerup: a ragged volume (built from range images) has no runner-up search here");
+    if (c->rel_last.slot_of(C) >= 0)
+        return fail(c, MGM_ERR_UNSUPPORTED, "mgm_wta_runnerup: the last aggregation of this volume ran on its range-proportional copy");
+    const int slot = c->last.slot_of(C);
+    if (!c->lr.p || slot < 0 || c->last.ndir != NDIR || c->last.L != L)
+        return fail(c, MGM_ERR_INVALID, "mgm_wta_runnerup: this volume was not part of the context's last aggregation with NDIR passes");
+    HIPCHK(c, hipSetDevice(c->device));
+    return run_wta_runnerup(c, C, slot, NDIR, fix_overcount, radius, out2->d, cost2->d, out1 ? out1->d : nullptr, cost1 ? cost1->d : nullptr);
+}
+
+int mgm_uniqueness_dev(mgm_ctx *c, const mgm_img *d, const mgm_img *cost1, const mgm_img *cost2, float ratio, mgm_img *out, mgm_img *conf)
+{
+    if (int jr = pipe_join(c)) return jr;  // (pipelined context: run what has been deferred first)
+    if (!c || !d || !cost1 || !cost2 || (!out && !conf)) return fail(c, MGM_ERR_INVALID, "mgm_uniqueness: null argument (at least one of out, conf)");
+    if (!(ratio >= 0.0f && ratio <= 1.0f)) return fail(c, MGM_ERR_INVALID, "mgm_uniqueness: ratio must be finite and in [0, 1]");
+    for (const mgm_img *im : {d, cost1, cost2, (const mgm_img *)out, (const mgm_img *)conf})
+        if (im && (im->nx != d->nx || im->ny != d->ny || im->nch != 1)) return fail(c, MGM_ERR_INVALID, "mgm_uniqueness: image size mismatch (one channel, one size)");
+    if (conf && (conf == d || conf == cost1 || conf == cost2 || conf == out)) return fail(c, MGM_ERR_INVALID, "mgm_uniqueness: conf must be an image of its own");
+    if (out && (out == cost1 || out == cost2)) return fail(c, MGM_ERR_INVALID, "mgm_uniqueness: out may be d, not a cost map");
+    HIPCHK(c, hipSetDevice(c->device));
+    TimeScope t(c, "k_uniqueness");
+    HIPCHK(c, launch_uniqueness(d->d, cost1->d, cost2->d, (long long)d->nx * d->ny, ratio, out ? out->d : nullptr, conf ? conf->d : nullptr, c->stream));
+    return MGM_OK;
+}
+
 int mgm_update_ranges_dev(mgm_ctx *c, const mgm_img *outoff, mgm_img *dminI, mgm_img *dmaxI, int slack, int radius)
 {
     if (int jr = pipe_join(c)) return jr;  // (pipelined context: run what has been deferred first)

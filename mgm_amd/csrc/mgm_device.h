@@ -106,6 +106,26 @@ struct WtaChoice;  // (mgm_planner.h: what plan_wta / plan_wta_right decided)
 struct WtaRightChoice;
 hipError_t launch_wta_right(const WtaRightParams &p, const WtaRightChoice &c, hipStream_t s);
 
+// the runner-up search over the same Lr volumes (k_wta_runnerup, mgm_wta.hip): per pixel the winner of the plain
+// search and the first strict minimum among the finite entries more than `radius` labels away from it
+struct WtaRunnerupParams {
+    const float *C;      // costs, label stride Lk (read with the over-count fix only) ...
+    const uint8_t *C8;   // ... or their compact copy, cbytes bytes per cost
+    int cbytes;
+    const float *Lr;     // NDIR volumes [npix][Lk], pass p at Lr + p*nvol
+    float *out2, *cost2;  // [npix] the runner-up's label and S there (NaN, +INF: none)
+    float *out1, *cost1;  // [npix] the winner's, unrefined; each may be nullptr
+    long long npix, nvol;
+    int L, Lk;           // labels that exist, label stride (>= L)
+    int NDIR, FIX, dmin;
+    int radius;          // 0 .. L (the host clamps: at L no entry is far enough from any winner)
+};
+struct RunnerupChoice;  // (mgm_planner.h: what plan_wta_runnerup decided)
+hipError_t launch_wta_runnerup(const WtaRunnerupParams &p, const RunnerupChoice &c, hipStream_t s);
+// conf = 1 - cost1 / cost2, out = conf < ratio ? NaN : d (mgm_post.hip); out and conf may each be nullptr, out may be d
+hipError_t launch_uniqueness(const float *d, const float *cost1, const float *cost2, long long n, float ratio, float *out, float *conf,
+                             hipStream_t s);
+
 // ---- ragged volumes in the range-proportional layout (mgm_pass_rel.hip, k_wta_rel): 64 label slots per pixel placed at the
 // pixel's own window, slot k <-> disparity base + k
 struct RelVolume {

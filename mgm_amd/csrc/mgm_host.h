@@ -121,7 +121,7 @@ struct PlanCache {
 };
 
 // What the context's last DENSE aggregation left behind, for whoever searches or downloads it later (the winner search of the same
-// call, mgm_wta_windowed_dev, mgm_wta_right_dev, mgm_lr_device_ptr, mgm_debug_download_*).  Written by the remember stage of
+// call, mgm_wta_windowed_dev, mgm_wta_right_dev, mgm_wta_runnerup_dev, mgm_lr_device_ptr, mgm_debug_download_*).  Written by the remember stage of
 // run_passes (mgm_plan.hip) and by nobody else.
 struct DenseRun {
     long long nvol = 0;    // floats per Lr volume
@@ -370,6 +370,8 @@ bool wta_prune_enabled();  // MGM_HIP_WTA_PRUNE=0 (read at every call) or tune w
 int run_wta(mgm_ctx *c, const mgm_cv *C, long long pix0, long long npix, const float *lr, long long lr_stride, int NDIR, int fix_overcount,
             int ridx, float *out, float *outcost, float *Sout, const float *wlo = nullptr, const float *whi = nullptr, int slot = -1);
 int run_wta_right(mgm_ctx *c, const mgm_cv *C, int slot, int NDIR, int fix_overcount, int ridx, int vnx, float *out, float *outcost);
+int run_wta_runnerup(mgm_ctx *c, const mgm_cv *C, int slot, int NDIR, int fix_overcount, int radius, float *out2, float *cost2, float *out1,
+                     float *cost1);
 // the range-proportional path of ragged volumes (mgm_plan.hip): is this call one it takes?  then the passes + the winner search
 bool rel_enabled();
 int weights_have_odd_values(mgm_ctx *c, const mgm_img *const *w8s, int nb, long long npix, bool *odd, bool *any = nullptr);

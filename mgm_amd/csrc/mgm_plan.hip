@@ -769,6 +769,47 @@ int run_wta_right(mgm_ctx *c, const mgm_cv *C, int slot, int NDIR, int fix_overc
     return MGM_OK;
 }
 
+// The runner-up search over the Lr volumes of slot `slot` of the context's last dense aggregation
+// (mgm_wta_runnerup_dev has checked that C is that volume).  Costs and label stride as run_wta_right takes them.  Reads the
+// context's record of that aggregation and leaves it, the chunk minima and the search statistics as they are.
+int run_wta_runnerup(mgm_ctx *c, const mgm_cv *C, int slot, int NDIR, int fix_overcount, int radius, float *out2, float *cost2, float *out1,
+                     float *cost1)
+{
+    const DenseRun &d = c->last;
+    CostSource src{};
+    src.cbytes = 1;
+    if (fix_overcount == 1) {  // (else the costs are not read)
+        if (int r = cost_source(c, C, slot, &src)) return r;
+        if (src.L != d.Lk) return fail(c, MGM_ERR_INTERNAL, "run_wta_runnerup: the costs' label stride is not the last aggregation's");
+    }
+    WtaRunnerupParams w{};
+    w.C = src.C;
+    w.C8 = src.C8;
+    w.cbytes = src.cbytes;
+    w.Lr = d.lr(c->lr, slot, 0);
+    w.out2 = out2;
+    w.cost2 = cost2;
+    w.out1 = out1;
+    w.cost1 = cost1;
+    w.npix = (long long)C->nx * C->ny;
+    w.nvol = d.stride;
+    w.L = C->dmax - C->dmin + 1;
+    w.Lk = d.Lk;
+    w.NDIR = NDIR;
+    w.FIX = fix_overcount;
+    w.dmin = C->dmin;
+    w.radius = std::min(radius, w.L);  // (at L no entry is far enough from any winner: the same result, and o1 + radius stays small)
+    // MGM_HIP_WTA_RUNNERUP_ANY=1 (read at every call: tests switch it inside one process): the generic kernel everywhere
+    // ... MGM_HIP_WTA_RUNNERUP_WG=<workgroups per CU> (the same): a lower cap of the grid, so that small volumes take several turns
+    const char *ea = getenv("MGM_HIP_WTA_RUNNERUP_ANY"), *ew = getenv("MGM_HIP_WTA_RUNNERUP_WG");
+    const RunnerupChoice choice = plan_wta_runnerup(RunnerupRequest{w.npix, w.L, w.Lk, NDIR, c->num_cu, (ea && atoi(ea) != 0) ? 1 : 0, ew ? std::max(0, atoi(ew)) : 0});
+    TimeScope t(c, "k_wta_runnerup");
+    // (a second name with the same time: which family ran -- tests assert that the forcing switch was honoured)
+    t.kernel = choice.family == kRunnerupAny ? "k_wta_runnerup_any" : "k_wta_runnerup_stream";
+    if (hipError_t e = launch_wta_runnerup(w, choice, c->stream)) return hipfail(c, e, "launch_wta_runnerup(w, c->stream)");
+    return MGM_OK;
+}
+
 // K4-K6 with any refinement of the reference's table: none/vfit are fused into k_wta; parabola, cubic and
 // parabolaOCV (refine.h:6-145) run as a second kernel on the corrected S (the caller's, or a scratch volume).
 int run_wta_refine(mgm_ctx *c, const mgm_cv *C, long long pix0, long long npix, const float *lr, long long lr_stride,

@@ -3,8 +3,8 @@
 // sharing, workgroups per CU, deep rings, per-XCD queues, strips, the hand-off layout, the ticket order and the dealt task
 // table).  Plain C++17, standard headers only: no device, no context, no environment -- mgm_plan.hip fills the requests,
 // caches the plans BY the requests and launches; tests/test_planner.py runs the planner on the host.
-// The winner search is planned here as well (plan_wta, plan_wta_right, plan_wta_rel at the end: which instance, which grid,
-// pruned or not); tests/test_wta_plan.py.
+// The winner search is planned here as well (plan_wta, plan_wta_right, plan_wta_runnerup, plan_wta_rel at the end: which
+// instance, which grid, pruned or not); tests/test_wta_plan.py, tests/test_runnerup_plan.py.
 // ... and which kernels take an aggregation call at all (plan_agg_route, plan_subbatch, plan_dense_kernels behind them: pure functions
 // that ASK for the facts of the device they need, one at a time); tests/test_route_plan.py.
 #pragma once
@@ -804,7 +804,7 @@ inline RelPlan plan_rel(const RelRequest &q)
 
 // ---- the winner search (mgm_wta.hip) ---------------------------------------------------------------------------------------
 // Which kernel instance a search runs on, and on how many workgroups: a function of the request and nothing else.  mgm_plan.hip
-// fills the requests (run_wta, run_wta_right), the launchers of mgm_wta.hip are tables from a choice to its instance, and
+// fills the requests (run_wta, run_wta_right, run_wta_runnerup), the launchers of mgm_wta.hip are tables from a choice to its instance, and
 // tests/test_wta_plan.py holds the planner against a restatement of the launchers it replaced.
 struct WtaRequest {
     long long npix;           // pixels of the call
@@ -927,6 +927,52 @@ inline WtaRightChoice plan_wta_right(const WtaRightRequest &q)
     c.family = kRightStream, c.LPL = lpl, c.PPW = lpl <= 4 ? 2 : 1;
     c.ring = 64;
     while (c.ring < q.L - 1 + 2 * 4 * c.PPW) c.ring *= 2;
+    return c;
+}
+
+// the runner-up search (k_wta_runnerup<LPL, PPW, MAXD> / k_wta_runnerup_any)
+struct RunnerupRequest {
+    long long npix;  // pixels of the call
+    int L, Lk, NDIR, num_cu;    // labels that exist, label stride, passes; compute units of the device (0: unknown)
+    int sw_any, sw_wg_per_cu;   // MGM_HIP_WTA_RUNNERUP_ANY=1: the generic kernel everywhere; MGM_HIP_WTA_RUNNERUP_WG=<workgroups per CU> (0: kRunnerupWgPerCu)
+};
+static_assert(std::has_unique_object_representations_v<RunnerupRequest>, "RunnerupRequest: integers only, no padding");
+enum RunnerupFamily { kRunnerupRefuse = 0, kRunnerupStream, kRunnerupAny };
+struct RunnerupChoice {
+    long long grid;              // workgroups of 256 threads
+    int family, LPL, PPW, MAXD;  // k_wta_runnerup<LPL, PPW, MAXD>; the generic kernel has no arguments (0)
+};
+static_assert(std::has_unique_object_representations_v<RunnerupChoice>, "RunnerupChoice: integers only, no padding");
+constexpr long long kRunnerupWgPerCu = 768;
+inline RunnerupChoice plan_wta_runnerup(const RunnerupRequest &q)
+{
+    RunnerupChoice c{};
+    if (q.npix < 1 || q.L < 1 || q.Lk < q.L || q.NDIR < 1 || q.NDIR > kMaxDirs || q.sw_wg_per_cu < 0) return c;
+    const long long cus = q.num_cu > 0 ? q.num_cu : 256;
+    const int lpl = q.Lk % 64 == 0 ? q.Lk / 64 : 0;
+    // pixels per wave and turn: those of the k_wta instances without a padding lane (plan_wta), whose registers are known to fit
+    int ppw = 0;
+    switch (lpl) {
+        case 1: case 2: ppw = 4; break;
+        case 3: ppw = 2; break;
+        case 4: ppw = 3; break;
+        case 6: case 8: case 12: case 16: ppw = 1; break;
+        default: break;
+    }
+    int per_wave = 1;  // pixels a wave takes per turn of its grid-stride loop
+    if (q.sw_any != 0 || ppw == 0) {  // any other stride (no multiple of 64, beyond 1024 labels), or forced
+        c.family = kRunnerupAny;
+    } else {
+        c.family = kRunnerupStream, c.LPL = lpl, c.PPW = ppw, c.MAXD = kMaxDirs;
+        if (lpl <= 8 && q.NDIR <= 4) c.PPW = 2 * ppw, c.MAXD = 4;  // at most 4 directions: twice the slabs fit the registers
+        per_wave = c.PPW;
+    }
+    // A bounded grid (workgroups of 4 waves), grid-stride beyond it: exactly the waves the pixels need, at most plan_wta's figure
+    // for one pixel per slab per CU -- the kernel reads the volumes exactly as k_wta does.  That figure is k_wta's; it has NOT
+    // been measured for this kernel (the one measurement of it, against k_wta at this cap, is in docs/experiments.md,
+    // "runner-up search").  The switch lowers the cap so that small volumes take several turns of the loop (tests).
+    const long long waves = (q.npix + per_wave - 1) / per_wave;
+    c.grid = std::min((waves + 3) / 4, cus * (q.sw_wg_per_cu > 0 ? q.sw_wg_per_cu : kRunnerupWgPerCu));
     return c;
 }
 

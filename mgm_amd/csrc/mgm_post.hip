@@ -5,6 +5,7 @@
 //   leftright_test     mgm.cc:68-91          |x - (Lx + R[Lx])| > tau, or Lx outside the other image  =>  NaN
 //   back-projection    mgm.cc:433-443        v sampled at x + d (the reference's float index arithmetic), else u
 //   update_dmin_dmax   mgm.cc:120-158        the ranges of the next TSGM_ITER iteration around the current map (k_minmax, k_update_ranges)
+//   uniqueness                 conf = 1 - cost1 / cost2 from the runner-up search, conf < ratio  =>  NaN
 //
 // One thread per pixel; W*H work, nothing here is hot.  Default floating point (NaN-honouring).
 #include "mgm_device.h"
@@ -146,6 +147,31 @@ hipError_t launch_leftright(const float *dx, int nc, int nr, const float *Rdx, i
 {
     const long long n = (long long)nc * nr;
     hipLaunchKernelGGL(k_leftright, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, dx, nc, nr, Rdx, Rnc, threshold, out);
+    return hipGetLastError();
+}
+
+// The uniqueness test on the runner-up search's two costs (this project's own step, the reference has none):
+// conf = 1 - cost1 / cost2 -- one division, one subtraction (this file is built with -ffp-contract=off), whatever IEEE gives:
+// no runner-up (cost2 = +INF) gives 1, no winner (INF / INF) and 0 / 0 give NaN -- and out = conf < ratio ? NaN : d, so a NaN
+// conf keeps d.  Every input is read before anything is written: out may be d.
+__global__ void __launch_bounds__(256) k_uniqueness(const float *d, const float *__restrict__ cost1, const float *__restrict__ cost2,
+                                                    long long n, float ratio, float *out, float *__restrict__ conf)
+{
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float q = cost1[i] / cost2[i];
+    const float cf = 1.0f - q;
+    if (conf) conf[i] = cf;
+    if (out) {
+        const float v = d[i];
+        out[i] = cf < ratio ? __builtin_nanf("") : v;
+    }
+}
+
+hipError_t launch_uniqueness(const float *d, const float *cost1, const float *cost2, long long n, float ratio, float *out, float *conf,
+                             hipStream_t s)
+{
+    hipLaunchKernelGGL(k_uniqueness, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, d, cost1, cost2, n, ratio, out, conf);
     return hipGetLastError();
 }
 

@@ -1201,4 +1201,193 @@ hipError_t launch_wta_right(const WtaRightParams &p0, const WtaRightChoice &c, h
     return hipErrorInvalidValue;
 }
 
+// ---- the runner-up search -------------------------------------------------------------------------------------
+// Per pixel: the winner (o1, S(o1)) exactly as k_wta finds it without refinement -- the first strict minimum among the finite
+// entries by rising o (mgm_core.cc:592-609) -- and the runner-up (o2, S(o2)): the first strict minimum among the finite entries
+// with |o - o1| > radius.  No winner, or no such entry: NaN label, +INF cost.
+// the smaller (S, label) over the wave, in every lane
+__device__ __forceinline__ void wave_take(float &best, int &bi)
+{
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        const float ov = __shfl_xor(best, d);
+        const int oi = __shfl_xor(bi, d);
+        if (ov < best || (ov == best && oi < bi)) {
+            best = ov;
+            bi = oi;
+        }
+    }
+}
+__device__ __forceinline__ void runnerup_emit(const WtaRunnerupParams &P, long long pix, float v1, int o1, float v2, int o2)
+{
+    constexpr int NONE = 0x7fffffff;
+    P.out2[pix] = o2 == NONE ? __builtin_nanf("") : (float)(o2 + P.dmin);
+    P.cost2[pix] = v2;
+    if (P.out1) P.out1[pix] = o1 == NONE ? __builtin_nanf("") : (float)(o1 + P.dmin);
+    if (P.cost1) P.cost1[pix] = v1;
+}
+
+// STREAMING: the volume is read exactly as k_wta reads it -- one wave per pixel, its 64*LPL label slots in registers, every stream
+// a coalesced slab, PPW pixels requested before the first is consumed -- and the slots are scanned twice: for the winner, then,
+// with the winner known to every lane, for the best entry outside its exclusion zone.  Label stride Lk == 64*LPL; slots L..Lk-1
+// are padding and never candidates.  No LDS, no atomics, no barriers: a wave never waits on another.
+template <int LPL, int PPW, int MAXD>
+__global__ void __launch_bounds__(256) k_wta_runnerup(const WtaRunnerupParams P)
+{
+    constexpr int NONE = 0x7fffffff;
+    constexpr int LP = LPL * 64;
+    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int o0 = lane * LPL;
+    const bool c8 = P.C8 != nullptr;
+    // grid-stride over groups of PPW consecutive pixels
+    for (long long g0 = ((long long)blockIdx.x * 4 + wv) * PPW; g0 < P.npix; g0 += (long long)gridDim.x * 4 * PPW) {
+        float c[PPW][LPL], l[MAXD][PPW][LPL];
+#pragma unroll
+        for (int u = 0; u < PPW; u++) {
+            const long long g = g0 + u < P.npix ? g0 + u : P.npix - 1;
+            if (P.FIX != 1) {  // (the costs are not read)
+#pragma unroll
+                for (int k = 0; k < LPL; k++) c[u][k] = 0.0f;
+            } else if (c8 && P.cbytes == 2) {
+                const unsigned short *q = reinterpret_cast<const unsigned short *>(P.C8) + g * LP + o0;
+#pragma unroll
+                for (int k = 0; k < LPL; k++) c[u][k] = c16_decode(q[k]);
+            } else if (c8) {
+                const uint8_t *q = P.C8 + g * LP + o0;
+#pragma unroll
+                for (int k = 0; k < LPL; k++) c[u][k] = c8_decode(q[k]);
+            } else {
+                const float *q = P.C + g * LP + o0;
+#pragma unroll
+                for (int k = 0; k < LPL; k++) c[u][k] = q[k];
+            }
+        }
+#pragma unroll
+        for (int p = 0; p < MAXD; p++) {
+            if (p < P.NDIR) {
+#pragma unroll
+                for (int u = 0; u < PPW; u++) {
+                    const long long g = g0 + u < P.npix ? g0 + u : P.npix - 1;
+                    const float *q = P.Lr + (long long)p * P.nvol + g * LP + o0;
+#pragma unroll
+                    for (int k = 0; k < LPL; k++) l[p][u][k] = q[k];
+                }
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < PPW; u++) {
+            if (g0 + u >= P.npix) break;
+            // S = ((0 + L0) + L1) + ... in pass order, then the over-count term (mgm_core.cc:582-599): k_wta's operations, in its order
+            float S[LPL];
+#pragma unroll
+            for (int k = 0; k < LPL; k++) S[k] = 0.0f;
+#pragma unroll
+            for (int p = 0; p < MAXD; p++) {
+                if (p < P.NDIR) {
+#pragma unroll
+                    for (int k = 0; k < LPL; k++) S[k] = S[k] + l[p][u][k];
+                }
+            }
+            if (P.FIX == 1) {
+                const float f = (float)(P.NDIR - 1);
+#pragma unroll
+                for (int k = 0; k < LPL; k++) S[k] = S[k] - f * c[u][k];
+            }
+            // the winner: first strict minimum among the finite entries, ascending o
+            float v1 = f_inf();
+            int o1 = NONE;
+#pragma unroll
+            for (int k = 0; k < LPL; k++) {
+                const float v = S[k];
+                if (o0 + k < P.L && finite_bits(v) && v1 > v) {
+                    v1 = v;
+                    o1 = o0 + k;
+                }
+            }
+            wave_take(v1, o1);
+            // the runner-up: the same scan over the entries outside [o1 - radius, o1 + radius] (none without a winner)
+            float v2 = f_inf();
+            int o2 = NONE;
+            if (o1 != NONE) {  // (wave-uniform)
+                const int zl = o1 - P.radius, zh = o1 + P.radius;
+#pragma unroll
+                for (int k = 0; k < LPL; k++) {
+                    const float v = S[k];
+                    if (o0 + k < P.L && (o0 + k < zl || o0 + k > zh) && finite_bits(v) && v2 > v) {
+                        v2 = v;
+                        o2 = o0 + k;
+                    }
+                }
+            }
+            wave_take(v2, o2);
+            if (lane == 0) runnerup_emit(P, g0 + u, v1, o1, v2, o2);
+        }
+    }
+}
+
+// Any label count and label stride (strides that are no multiple of 64, more than 1024 labels): one wavefront per pixel, the labels
+// strided over the lanes; the second pass recomputes every entry from memory by the same operations.  Nothing here is tuned.
+__global__ void __launch_bounds__(256) k_wta_runnerup_any(const WtaRunnerupParams P)
+{
+    constexpr int NONE = 0x7fffffff;
+    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const float f = (float)(P.NDIR - 1);
+    for (long long pix = (long long)blockIdx.x * 4 + wv; pix < P.npix; pix += (long long)gridDim.x * 4) {
+        auto S_at = [&](int o) {
+            const long long i = pix * P.Lk + o;
+            float a = 0.0f;
+            for (int p = 0; p < P.NDIR; p++) a = a + P.Lr[(long long)p * P.nvol + i];
+            if (P.FIX == 1)
+                a = a - f * (!P.C8 ? P.C[i] : (P.cbytes == 2 ? c16_decode(reinterpret_cast<const unsigned short *>(P.C8)[i]) : c8_decode(P.C8[i])));
+            return a;
+        };
+        float v1 = f_inf();
+        int o1 = NONE;
+        for (int o = lane; o < P.L; o += 64) {
+            const float v = S_at(o);
+            if (finite_bits(v) && v1 > v) {
+                v1 = v;
+                o1 = o;
+            }
+        }
+        wave_take(v1, o1);
+        float v2 = f_inf();
+        int o2 = NONE;
+        if (o1 != NONE) {  // (wave-uniform)
+            const int zl = o1 - P.radius, zh = o1 + P.radius;
+            for (int o = lane; o < P.L; o += 64) {
+                if (o >= zl && o <= zh) continue;
+                const float v = S_at(o);
+                if (finite_bits(v) && v2 > v) {
+                    v2 = v;
+                    o2 = o;
+                }
+            }
+        }
+        wave_take(v2, o2);
+        if (lane == 0) runnerup_emit(P, pix, v1, o1, v2, o2);
+    }
+}
+
+// from a choice of the planner (plan_wta_runnerup) to its instance; anything else is hipErrorInvalidValue
+hipError_t launch_wta_runnerup(const WtaRunnerupParams &p, const RunnerupChoice &c, hipStream_t s)
+{
+    if (c.grid < 1 || p.radius < 0 || p.L < 1 || p.Lk < p.L || p.npix < 1) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)c.grid), block(256);
+    if (c.family == kRunnerupAny) {
+        hipLaunchKernelGGL(k_wta_runnerup_any, grid, block, 0, s, p);
+        return hipGetLastError();
+    }
+    if (c.family != kRunnerupStream || p.Lk != 64 * c.LPL || p.NDIR > c.MAXD) return hipErrorInvalidValue;
+#define RUNNERUP(LPL_, PPW_, MAXD_)                                                       \
+    if (c.LPL == LPL_ && c.PPW == PPW_ && c.MAXD == MAXD_) {                              \
+        hipLaunchKernelGGL((k_wta_runnerup<LPL_, PPW_, MAXD_>), grid, block, 0, s, p);    \
+        return hipGetLastError();                                                         \
+    }
+    RUNNERUP(1, 8, 4) RUNNERUP(1, 4, 8) RUNNERUP(2, 8, 4) RUNNERUP(2, 4, 8) RUNNERUP(3, 4, 4) RUNNERUP(3, 2, 8) RUNNERUP(4, 6, 4) RUNNERUP(4, 3, 8)
+    RUNNERUP(6, 2, 4) RUNNERUP(6, 1, 8) RUNNERUP(8, 2, 4) RUNNERUP(8, 1, 8) RUNNERUP(12, 1, 8) RUNNERUP(16, 1, 8)
+#undef RUNNERUP
+    return hipErrorInvalidValue;
+}
+
 }  // namespace mgm

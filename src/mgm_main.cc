@@ -313,6 +313,27 @@ static void median_run(mgm_ctx *ctx, Run &r, int radius)
     std::swap(r.dout, r.dspare);
 }
 
+struct ImgHold {  // a device image freed with its scope
+    mgm_ctx *ctx;
+    mgm_img *im = nullptr;
+    ~ImgHold() { mgm_img_free(ctx, im); }
+};
+
+// -c / MGM_UNIQUENESS, right behind the aggregation of `r`: the runner-up search over the Lr volumes the context
+// still holds of that run, then conf = 1 - cost1 / cost2 into *conf (if wanted) and, with ratio != 0, NaN into the run's
+// (refined) map wherever conf < ratio
+static void uniqueness_run(mgm_ctx *ctx, const Opts &o, Run &r, float ratio, int radius, mgm_img **conf)
+{
+    ImgHold out2{ctx}, cost2{ctx}, cost1{ctx};
+    int rc;
+    for (mgm_img **im : {&out2.im, &cost2.im, &cost1.im})
+        if ((rc = mgm_img_create(ctx, r.nx, r.ny, 1, im))) die(ctx, rc, "mgm_img_create");
+    if (conf && (rc = mgm_img_create(ctx, r.nx, r.ny, 1, conf))) die(ctx, rc, "mgm_img_create");
+    if ((rc = mgm_wta_runnerup_dev(ctx, r.C, o.NDIR, o.FIX, radius, out2.im, cost2.im, nullptr, cost1.im))) die(ctx, rc, "mgm_wta_runnerup");
+    if ((rc = mgm_uniqueness_dev(ctx, r.dout, cost1.im, cost2.im, ratio, ratio != 0 ? r.dout : nullptr, conf ? *conf : nullptr)))
+        die(ctx, rc, "mgm_uniqueness");
+}
+
 // iterations 2..TSGM_ITER of main()'s loop (mgm.cc:377-388): the ranges narrow around the previous solution
 // (update_dmin_dmax), the volume -- and with it every scan-line pass -- stays the same, so only the winner search and
 // the refinement are redone, on the Lr volumes the context still holds
@@ -366,6 +387,9 @@ struct Job {
     Opts o{};
     std::string min_file, max_file, nolr_file, f_u, f_v, f_out, f_cost, f_back;
     int nscales = 1;          // -S: levels of the coarse-to-fine driver (1: the single-scale path)
+    std::string conf_file;    // -c: the left->right run's confidence map
+    double uniq = 0;          // MGM_UNIQUENESS: the uniqueness filter's ratio (0: off)
+    int uniq_radius = 1;      // MGM_UNIQUENESS_RADIUS: labels around the winner the runner-up stays away from
     int early = -1;           // >= 0: the command line ends before any work with this code ...
     std::string early_out;    // ... after these lines on stdout
     std::string early_err;    // ... and stderr
@@ -373,7 +397,7 @@ struct Job {
     HostImg u, v, rlo, rhi;
     std::exception_ptr decode_err;
     // results of the device stage
-    HostImg outoff, outcost, syn, nolr;
+    HostImg outoff, outcost, syn, nolr, conf;
     int rc = 0;  // the job's exit code
 };
 
@@ -397,12 +421,18 @@ static void parse_job(Job &j)
                         "options: -r dmin(-30) -R dmax(30) -O NDIR(4) -P1 (8) -P2 (32) -p prefilter(none) -t distance(ad)\n"
                         "         -truncDist (inf) -s subpix(none) -aP1 (1) -aP2 (1) -aThresh (5) -m FILE -M FILE -l FILE\n"
                         "         -S nscales(1): coarse to fine over up to 8 half-size levels (this program's own mode, not the reference's)\n"
+                        "         -c FILE: the left->right run's confidence map, 1 - cost1/cost2 of the winner and the runner-up (own mode)\n"
                         "environment: CENSUS_NCC_WIN=3 TESTLRRL=1 TESTLRRL_TAU=1.0 MEDIAN=0 TSGM=4 TSGM_ITER=1\n"
                         "             TSGM_FIX_OVERCOUNT=1 USE_TRUNCATED_LINEAR_POTENTIALS=0 MGM_DEVICE=0 MGM_DEVICES=0,1,...\n"
                         "             MGM_MS_SLACK=3 MGM_MS_RADIUS=2 (-S: window around the coarser level's disparities)\n"
                         "             MGM_RIGHT_FROM_LEFT=0 (1, with TESTLRRL != 0: no right->left run; the right map is read out of the left run's\n"
                         "              aggregated volume along its diagonals, and stdout has the line `right from left` in place of that run's\n"
                         "              lines; not with -m/-M, -S > 1, TSGM_ITER != 1, several MGM_DEVICES, -s parabola|cubic|parabolaOCV: exit code 2)\n"
+                        "             MGM_UNIQUENESS=0 (r in (0,1]: each run's map is NaN where 1 - cost1/cost2 < r, cost2 the aggregated cost of the\n"
+                        "              best label more than MGM_UNIQUENESS_RADIUS=1 away from the winner; applied right after the run's refinement,\n"
+                        "              before MEDIAN, the left-right test and the -l map; with MGM_RIGHT_FROM_LEFT=1 only the left map is filtered:\n"
+                        "              the right view has no runner-up; -c and MGM_UNIQUENESS not with -m/-M, -S > 1, TSGM_ITER != 1, several\n"
+                        "              MGM_DEVICES: exit code 2)\n"
                         "             (with several MGM_DEVICES, -S / -m -M / TSGM_ITER > 1 run on the first device; in --batch mode a FIRST line\n"
                         "              of that kind brings up one device for the whole batch, a later one leaves the other lines their devices)\n"
                         "resident mode: mgm --batch FILE|-   (one such command line per line of FILE, one device context for all)");
@@ -427,6 +457,11 @@ static void parse_job(Job &j)
     o.truncDist = (float)atof(pick_option(&argc, argv, "truncDist", "inf"));
     j.nolr_file = pick_option(&argc, argv, "l", "");
     j.nscales = atoi(pick_option(&argc, argv, "S", "1"));
+    j.conf_file = pick_option(&argc, argv, "c", "");
+    j.uniq = env_param("MGM_UNIQUENESS", 0);
+    j.uniq_radius = (int)env_param("MGM_UNIQUENESS_RADIUS", 1);
+    if (!(j.uniq >= 0 && j.uniq <= 1)) return early(1, nullptr, "mgm: MGM_UNIQUENESS must be a ratio in [0, 1]\n");
+    if (j.uniq_radius < 0) return early(1, nullptr, "mgm: MGM_UNIQUENESS_RADIUS must be >= 0\n");
     if (j.nscales < 1 || j.nscales > 8) return early(1, nullptr, "mgm: -S nscales must be 1..8\n");
     if (argc > 1) j.f_u = argv[1];
     if (argc > 2) j.f_v = argv[2];
@@ -470,6 +505,7 @@ static void encode_job(Job &j)
     if (j.early >= 0 || j.rc != 0) return;
     try {
         if (!j.nolr_file.empty()) imgio::write(j.nolr_file, j.nolr);
+        if (!j.conf_file.empty()) imgio::write(j.conf_file, j.conf);
         imgio::write(j.f_out, j.outoff);
         if (!j.f_cost.empty()) imgio::write(j.f_cost, j.outcost);
         if (!j.f_back.empty()) imgio::write(j.f_back, j.syn);
@@ -618,6 +654,19 @@ static int device_job(Session &S, Job &j, const std::function<void()> &decoded, 
             return 2;
         }
     }
+    // -c FILE / MGM_UNIQUENESS=r (this program's own mode): the runner-up search of a run right behind its aggregation
+    const bool uq = j.uniq != 0 || !j.conf_file.empty();
+    if (uq) {
+        const char *why = nullptr;
+        if (ranged) why = "range images (-m/-M)";
+        else if (j.nscales > 1) why = "-S > 1";
+        else if (ITER != 1) why = "TSGM_ITER != 1";
+        else if (getenv("MGM_DEVICES") && strchr(getenv("MGM_DEVICES"), ',')) why = "several MGM_DEVICES";
+        if (why) {
+            fprintf(stderr, "mgm: -c / MGM_UNIQUENESS does not combine with %s\n", why);
+            return 2;
+        }
+    }
     try {
         bring_up(S, ITER, ranged, j.nscales > 1);
         sw.mark("context");
@@ -647,6 +696,10 @@ static int device_job(Session &S, Job &j, const std::function<void()> &decoded, 
             fprintf(stderr, "mgm: MGM_RIGHT_FROM_LEFT=1 does not combine with several MGM_DEVICES\n");
             return 2;
         }
+        if (uq && multi) {  // (resident mode: an earlier line brought several devices up)
+            fprintf(stderr, "mgm: -c / MGM_UNIQUENESS does not combine with several MGM_DEVICES\n");
+            return 2;
+        }
         if (rfl && u.ny != v.ny) {
             fprintf(stderr, "mgm: MGM_RIGHT_FROM_LEFT=1 needs two images of one height\n");
             return 2;
@@ -668,6 +721,7 @@ static int device_job(Session &S, Job &j, const std::function<void()> &decoded, 
 
         int rc;
         Run &L = S.L, &R = S.R;
+        ImgHold dconf{ctx};  // -c: the confidence map, until it is downloaded
         const bool both = TESTLRRL != 0;
         if (j.nscales > 1) {
             multiscale_job(S, j, o, plo, phi, ITER, both, (float)TAU, (int)MEDIAN, sw);
@@ -712,6 +766,7 @@ static int device_job(Session &S, Job &j, const std::function<void()> &decoded, 
             else if (!together) aggregate_run(ctx, o, L);
             report_run(o, L);
             iterate_run(ctx, o, L, ITER, o.dmin, o.dmax, plo, phi);
+            if (uq) uniqueness_run(ctx, o, L, (float)j.uniq, j.uniq_radius, j.conf_file.empty() ? nullptr : &dconf.im);
         }
         if (MEDIAN != 0) median_run(ctx, L, (int)MEDIAN);
         if (!j.nolr_file.empty()) j.nolr = download(ctx, L.dout, L.nx, L.ny, 1);
@@ -734,6 +789,7 @@ static int device_job(Session &S, Job &j, const std::function<void()> &decoded, 
                 else if (!together) aggregate_run(ctx, o, R);
                 report_run(o, R);
                 iterate_run(ctx, o, R, ITER, -o.dmax, -o.dmin);
+                if (j.uniq != 0) uniqueness_run(ctx, o, R, (float)j.uniq, j.uniq_radius, nullptr);
             }
             if (MEDIAN != 0) median_run(ctx, R, (int)MEDIAN);
         }
@@ -751,6 +807,7 @@ static int device_job(Session &S, Job &j, const std::function<void()> &decoded, 
         j.outoff = download(ctx, L.dout, L.nx, L.ny, 1);
         sw.mark("device+download");
         if (!j.f_cost.empty()) j.outcost = download(ctx, L.dcost, L.nx, L.ny, 1);
+        if (dconf.im) j.conf = download(ctx, dconf.im, L.nx, L.ny, 1);
         // back-projected image (mgm.cc:433-443)
         if (!j.f_back.empty()) {
             mgm_img *dsyn = nullptr;
@@ -898,7 +955,7 @@ static int run_batch(const char *file)
         for (size_t m = 0; m < k; m++) {
             const Job &e = *jobs[m];
             for (const std::string *in : {&j.f_u, &j.f_v, &j.min_file, &j.max_file})
-                for (const std::string *out : {&e.f_out, &e.f_cost, &e.f_back, &e.nolr_file})
+                for (const std::string *out : {&e.f_out, &e.f_cost, &e.f_back, &e.nolr_file, &e.conf_file})
                     if (!in->empty() && *in == *out) needs[k] = m + 1;
         }
     }
@@ -931,7 +988,7 @@ static int run_batch(const char *file)
                 bad = 1;
             }
             // the job is done: its images go
-            j.u = j.v = j.rlo = j.rhi = j.outoff = j.outcost = j.syn = j.nolr = HostImg();
+            j.u = j.v = j.rlo = j.rhi = j.outoff = j.outcost = j.syn = j.nolr = j.conf = HostImg();
             {
                 std::lock_guard<std::mutex> lk(mu);
                 written = k + 1;
