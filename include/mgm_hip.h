@@ -340,6 +340,21 @@ int mgm_wta_runnerup_dev(mgm_ctx *ctx, const mgm_cv *C, int NDIR, int fix_overco
  * All images are one-channel and of one size, ratio is finite and in [0, 1] (else MGM_ERR_INVALID).  No synchronisation. */
 int mgm_uniqueness_dev(mgm_ctx *ctx, const mgm_img *d, const mgm_img *cost1, const mgm_img *cost2, float ratio,
                        mgm_img *out, mgm_img *conf);
+/* The speckle filter (DESIGN.md "speckle filter"; this library's own step, the reference has none): small islands of disparity go.
+ * d is an nx x ny x 1 map, maxsize >= 0, maxdiff >= 0 (+INF allowed; negative or NaN: MGM_ERR_INVALID as maxsize < 0 is).
+ *   valid pixel  d(p) is finite; NaN and +-INF pixels belong to no component and are copied to out bit for bit
+ *   edge         two 4-neighbours p, q, both valid, are joined iff fabsf(d(p) - d(q)) <= maxdiff: one float subtraction, so -0 and
+ *                +0 are joined and a difference that overflows to +INF is joined under maxdiff = +INF only
+ *   component    a connected component of that graph (chained: a ramp 0, 1, 2, ..., N is ONE component under maxdiff = 1);
+ *                size(p) = the number of pixels of p's component
+ *   out(p)       = valid(p) && size(p) <= maxsize ? NaN : d(p)   (OpenCV's filterSpeckles: a region of exactly maxsize pixels goes;
+ *                maxsize = 0 leaves out == d bit for bit)
+ *   size_map(p)  = (float)size(p) on valid pixels, 0 on the others
+ * 4-connectivity, one channel.  out and size_map may each be NULL, not both; out may be d, size_map must be an image of its own; all
+ * images are one-channel and of one size (else MGM_ERR_INVALID).  More than 2^31 - 1 pixels: MGM_ERR_UNSUPPORTED.  The result
+ * depends on no traversal order and the filter is idempotent.  Scratch: two int32 planes of the map's size, kept by the context
+ * (mgm_ctx_trim releases them).  No synchronisation; the timing table lists the call as k_speckle. */
+int mgm_speckle_dev(mgm_ctx *ctx, const mgm_img *d, int maxsize, float maxdiff, mgm_img *out, mgm_img *size_map);
 /* update_dmin_dmax (mgm.cc:120-158; main() uses slack 3, radius 2) followed by the two
  * remove_nonfinite_values_Img calls (mgm.cc:387-388): dminI/dmaxI are updated in place from the disparity map. */
 int mgm_update_ranges_dev(mgm_ctx *ctx, const mgm_img *outoff, mgm_img *dminI, mgm_img *dmaxI, int slack, int radius);

@@ -33,7 +33,7 @@ ABI_SYMBOLS = [
     "mgm_ctx_set_workspace_limit", "mgm_ctx_mem_info", "mgm_ctx_set_pipeline", "mgm_img_update", "mgm_debug_probe_workspace", "mgm_ctx_set_placement_tries",
     "mgm_debug_wta_stats", "mgm_debug_download_lmin", "mgm_debug_last_pass_kernel",
     "mgm_multiscale_levels", "mgm_zoom_out_dev", "mgm_ranges_zoom_out_dev", "mgm_ranges_from_coarse_dev", "mgm_multiscale_pair_dev",
-    "mgm_wta_runnerup_dev", "mgm_uniqueness_dev",
+    "mgm_wta_runnerup_dev", "mgm_uniqueness_dev", "mgm_speckle_dev",
 ]
 
 MGM_OK, MGM_ERR_INVALID, MGM_ERR_UNSUPPORTED, MGM_ERR_HIP, MGM_ERR_NOMEM, MGM_ERR_INTERNAL = range(6)
@@ -117,6 +117,7 @@ def load_library():
     L.mgm_wta_right_dev.argtypes = [vp, vp, i, i, cp, vp, vp]
     L.mgm_wta_runnerup_dev.argtypes = [vp, vp, i, i, i, vp, vp, vp, vp]
     L.mgm_uniqueness_dev.argtypes = [vp, vp, vp, vp, f, vp, vp]
+    L.mgm_speckle_dev.argtypes = [vp, vp, i, f, vp, vp]
     L.mgm_update_ranges_dev.argtypes = [vp, vp, vp, vp, i, i]
     L.mgm_leftright_dev.argtypes = [vp, vp, vp, f, vp]
     L.mgm_backproject_dev.argtypes = [vp, vp, vp, vp, vp]
@@ -402,6 +403,28 @@ class Context:
                 im.free()
             raise
         return (out if out else None), conf
+
+    def speckle_dev(self, d, maxsize, maxdiff=1.0, out=None, want_size=False):
+        """The speckle filter (mgm_speckle_dev): NaN into every 4-connected component of finite pixels, joined where
+        |d(p) - d(q)| <= maxdiff, of at most maxsize pixels; device images (out, size_map).  out: an image to write (d itself is
+        allowed), None for a new one, False for none; size_map (every pixel's component size, 0 on non-finite pixels) is None
+        without want_size."""
+        _, ny, nx = d.shape
+        mine = []  # the images made here: freed if the call fails
+        try:
+            if out is None:
+                out = self.new_image(nx, ny)
+                mine.append(out)
+            size_map = None
+            if want_size:
+                size_map = self.new_image(nx, ny)
+                mine.append(size_map)
+            self._chk(self.lib.mgm_speckle_dev(self.h, d.h, maxsize, maxdiff, out.h if out else None, size_map.h if want_size else None))
+        except Exception:
+            for im in mine:
+                im.free()
+            raise
+        return (out if out else None), size_map
 
     def pair_right_from_left(self, u, v, dmin, dmax, P1=8.0, P2=32.0, NDIR=4, TSGM=4, use_fh=0, fix_overcount=1, aP2=1.0, aThresh=5.0,
                              prefilter="none", distance="ad", truncDist=float("inf"), census_win=3, refine="none", tau=1.0, median=0):

@@ -644,6 +644,37 @@ int mgm_median_dev(mgm_ctx *c, const mgm_img *in, int radius, mgm_img *out)
     return MGM_OK;
 }
 
+// The speckle filter (mgm_speckle.hip): plan_speckle decides the tile, the grids and the scratch, the four phases are four
+// launches on the context's stream.  "k_speckle" brackets the call in the timing table, each phase is listed inside it under its
+// kernel's name.
+int mgm_speckle_dev(mgm_ctx *c, const mgm_img *d, int maxsize, float maxdiff, mgm_img *out, mgm_img *size_map)
+{
+    if (int jr = pipe_join(c)) return jr;  // (pipelined context: run what has been deferred first)
+    if (!c || !d || (!out && !size_map)) return fail(c, MGM_ERR_INVALID, "mgm_speckle: null argument (at least one of out, size_map)");
+    if (maxsize < 0) return fail(c, MGM_ERR_INVALID, "mgm_speckle: maxsize must be >= 0");
+    if (!(maxdiff >= 0.0f)) return fail(c, MGM_ERR_INVALID, "mgm_speckle: maxdiff must be >= 0 (+INF allowed, NaN not)");
+    for (const mgm_img *im : {d, (const mgm_img *)out, (const mgm_img *)size_map})
+        if (im && (im->nx != d->nx || im->ny != d->ny || im->nch != 1)) return fail(c, MGM_ERR_INVALID, "mgm_speckle: image size mismatch (one channel, one size)");
+    if (size_map && (size_map == d || size_map == out)) return fail(c, MGM_ERR_INVALID, "mgm_speckle: size_map must be an image of its own");
+    const SpeckleChoice choice = plan_speckle(SpeckleRequest{d->nx, d->ny, c->num_cu});
+    if (choice.family == kSpeckleRefuse) return fail(c, MGM_ERR_UNSUPPORTED, "mgm_speckle: more than 2^31 - 1 pixels (pixel indices are int32)");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (int r = reserve(c, c->speckle, (size_t)choice.scratch_bytes)) return r;
+    SpeckleParams p{};
+    p.d = d->d;
+    p.out = out ? out->d : nullptr;
+    p.size_map = size_map ? size_map->d : nullptr;
+    p.parent = (int *)c->speckle.p;
+    p.cnt = p.parent + (size_t)d->nx * d->ny;
+    p.nx = d->nx, p.ny = d->ny, p.maxsize = maxsize, p.maxdiff = maxdiff;
+    TimeScope t(c, "k_speckle");
+    for (int phase = 0; phase < kSpecklePhases; phase++) {
+        TimeScope tp(c, speckle_phase_name(phase));
+        if (hipError_t e = launch_speckle_phase(phase, p, choice, c->stream)) return hipfail(c, e, speckle_phase_name(phase));
+    }
+    return MGM_OK;
+}
+
 int mgm_leftright_dev(mgm_ctx *c, const mgm_img *d, const mgm_img *other, float tau, mgm_img *out)
 {
     if (int jr = pipe_join(c)) return jr;  // (pipelined context: run what has been deferred first)

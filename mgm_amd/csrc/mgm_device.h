@@ -126,6 +126,20 @@ hipError_t launch_wta_runnerup(const WtaRunnerupParams &p, const RunnerupChoice 
 hipError_t launch_uniqueness(const float *d, const float *cost1, const float *cost2, long long n, float ratio, float *out, float *conf,
                              hipStream_t s);
 
+// the speckle filter (mgm_speckle.hip): connected components of the finite pixels under |d(p) - d(q)| <= maxdiff on
+// 4-neighbours; out = NaN on the components of at most maxsize pixels, size_map = the size of every pixel's component
+struct SpeckleParams {
+    const float *d;    // [nx*ny] the map (out may be d: k_speckle_apply reads d[p] before it writes out[p])
+    float *out, *size_map;  // each may be nullptr
+    int *parent, *cnt;      // the scratch planes, nx*ny int32 each; every word of both is written by k_speckle_local
+    int nx, ny, maxsize;
+    float maxdiff;
+};
+struct SpeckleChoice;  // (mgm_planner.h: what plan_speckle decided)
+enum SpecklePhase { kSpeckleLocal = 0, kSpeckleSeams, kSpeckleCount, kSpeckleApply, kSpecklePhases };
+const char *speckle_phase_name(int phase);  // "k_speckle_local", ...
+hipError_t launch_speckle_phase(int phase, const SpeckleParams &p, const SpeckleChoice &c, hipStream_t s);
+
 // ---- ragged volumes in the range-proportional layout (mgm_pass_rel.hip, k_wta_rel): 64 label slots per pixel placed at the
 // pixel's own window, slot k <-> disparity base + k
 struct RelVolume {

@@ -207,6 +207,7 @@ struct mgm_ctx {
     // last.wrote_min; the pruned winner search reads them (run_wta).  wta_stats: its two counters' word on the device (timing or
     // debug statistics on), wta_stats_n: searches counted into it since the last aggregation call began (0: none was pruned)
     Buf lmin, wta_stats;  // (wta_stats: kWtaStatBytes)
+    Buf speckle;          // mgm_speckle_dev: the parent and count planes of its labelling (plan_speckle's scratch_bytes)
     int wta_stats_n = 0;
     DenseRun last;    // the last aggregation, if it was a dense one ...
     RelRun rel_last;  // ... or a range-proportional one (each remember stage clears the other)

@@ -5,6 +5,7 @@
 // caches the plans BY the requests and launches; tests/test_planner.py runs the planner on the host.
 // The winner search is planned here as well (plan_wta, plan_wta_right, plan_wta_runnerup, plan_wta_rel at the end: which
 // instance, which grid, pruned or not); tests/test_wta_plan.py, tests/test_runnerup_plan.py.
+// ... and the speckle filter's tile, grids and scratch (plan_speckle); tests/test_speckle_plan.py.
 // ... and which kernels take an aggregation call at all (plan_agg_route, plan_subbatch, plan_dense_kernels behind them: pure functions
 // that ASK for the facts of the device they need, one at a time); tests/test_route_plan.py.
 #pragma once
@@ -990,6 +991,47 @@ inline WtaRelChoice plan_wta_rel(const WtaRelRequest &q)
 {
     const long long groups = (q.npix + 15) / 16;  // four waves of four pixels per block
     return WtaRelChoice{std::max(1ll, std::min(groups, q.num_cu * 64)), q.slots == 128 ? 8 : 4, q.cb == 4 ? 4 : (q.cb == 2 ? 2 : 1)};
+}
+
+// ---- the speckle filter (mgm_speckle.hip) ------------------------------------------------------------------------
+// Connected-component labelling by tiles: k_speckle_local labels one tile per workgroup in LDS, k_speckle_seams joins the tiles
+// across their right and bottom seams (one thread per pixel pair), k_speckle_count and k_speckle_apply run one thread per pixel.
+// The tile, the four grids and the scratch are decided here and nowhere else; tests/test_speckle_plan.py.
+struct SpeckleRequest {
+    int nx, ny;
+    int num_cu;  // compute units of the device (0: unknown).  The tile is one shape today: the field is part of the request so that a
+                 // tile chosen by the device's width stays this function's decision and the launcher's interface does not change
+};
+static_assert(std::has_unique_object_representations_v<SpeckleRequest>, "SpeckleRequest: integers only, no padding");
+enum SpeckleFamily { kSpeckleRefuse = 0, kSpeckleTiles };
+struct SpeckleChoice {
+    long long scratch_bytes;                                 // `planes` int32 planes of nx*ny
+    long long grid_local, grid_seams, grid_count, grid_apply;  // workgroups of kSpeckleThreads threads, each >= 1
+    int family;
+    int tw, th;      // the tile: tw x th pixels, kSpeckleThreads threads, (tw*th) / kSpeckleThreads pixels per thread
+    int ntx, nty;    // tiles per axis (the last one of an axis may be ragged)
+    int planes;      // int32 planes of the scratch: parent, cnt
+};
+static_assert(std::has_unique_object_representations_v<SpeckleChoice>, "SpeckleChoice: integers only, no padding");
+constexpr int kSpeckleThreads = 256, kSpeckleTileW = 64, kSpeckleTileH = 16, kSpecklePlanes = 2;
+constexpr long long kSpeckleMaxPixels = 2147483647ll;  // pixel indices and component sizes are int32
+inline SpeckleChoice plan_speckle(const SpeckleRequest &q)
+{
+    SpeckleChoice c{};
+    if (q.nx < 1 || q.ny < 1 || (long long)q.nx * q.ny > kSpeckleMaxPixels) return c;
+    const long long npix = (long long)q.nx * q.ny;
+    c.family = kSpeckleTiles;
+    c.tw = kSpeckleTileW, c.th = kSpeckleTileH;
+    c.ntx = (int)(((long long)q.nx + c.tw - 1) / c.tw), c.nty = (int)(((long long)q.ny + c.th - 1) / c.th);  // (nx + tw may pass 2^31)
+    c.planes = kSpecklePlanes;
+    c.scratch_bytes = (long long)c.planes * npix * 4;
+    // pixel pairs across the seams: (ntx - 1) vertical seams of ny pairs, (nty - 1) horizontal seams of nx pairs (a single tile: none,
+    // and a grid of one workgroup whose threads all leave)
+    const long long pairs = (long long)(c.ntx - 1) * q.ny + (long long)(c.nty - 1) * q.nx;
+    c.grid_local = (long long)c.ntx * c.nty;
+    c.grid_seams = std::max(1ll, (pairs + kSpeckleThreads - 1) / kSpeckleThreads);
+    c.grid_count = c.grid_apply = (npix + kSpeckleThreads - 1) / kSpeckleThreads;
+    return c;
 }
 
 // ---- which kernels take an aggregation call ----------------------------------------------------------------------------------

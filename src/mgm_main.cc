@@ -334,6 +334,12 @@ static void uniqueness_run(mgm_ctx *ctx, const Opts &o, Run &r, float ratio, int
         die(ctx, rc, "mgm_uniqueness");
 }
 
+// MGM_SPECKLE=maxsize: the speckle filter, in place, on a job's FINAL left map
+static void speckle_map(mgm_ctx *ctx, mgm_img *d, int maxsize, float maxdiff)
+{
+    if (int rc = mgm_speckle_dev(ctx, d, maxsize, maxdiff, d, nullptr)) die(ctx, rc, "mgm_speckle");
+}
+
 // iterations 2..TSGM_ITER of main()'s loop (mgm.cc:377-388): the ranges narrow around the previous solution
 // (update_dmin_dmax), the volume -- and with it every scan-line pass -- stays the same, so only the winner search and
 // the refinement are redone, on the Lr volumes the context still holds
@@ -390,6 +396,8 @@ struct Job {
     std::string conf_file;    // -c: the left->right run's confidence map
     double uniq = 0;          // MGM_UNIQUENESS: the uniqueness filter's ratio (0: off)
     int uniq_radius = 1;      // MGM_UNIQUENESS_RADIUS: labels around the winner the runner-up stays away from
+    int speckle = 0;          // MGM_SPECKLE: components of the final left map of at most this many pixels go (0: off)
+    float speckle_diff = 1;   // MGM_SPECKLE_DIFF: neighbours are joined up to this difference
     int early = -1;           // >= 0: the command line ends before any work with this code ...
     std::string early_out;    // ... after these lines on stdout
     std::string early_err;    // ... and stderr
@@ -433,6 +441,10 @@ static void parse_job(Job &j)
                         "              before MEDIAN, the left-right test and the -l map; with MGM_RIGHT_FROM_LEFT=1 only the left map is filtered:\n"
                         "              the right view has no runner-up; -c and MGM_UNIQUENESS not with -m/-M, -S > 1, TSGM_ITER != 1, several\n"
                         "              MGM_DEVICES: exit code 2)\n"
+                        "             MGM_SPECKLE=0 (n > 0: the speckle filter -- every 4-connected component of finite pixels of the final left map,\n"
+                        "              neighbours joined where they differ by at most MGM_SPECKLE_DIFF=1, that has at most n pixels becomes NaN; runs\n"
+                        "              last, after MEDIAN and the left-right test and before the back-projected image, with -S on the full-size map\n"
+                        "              only; leaves the -l map, the cost map and stdout as they are; combines with every other mode)\n"
                         "             (with several MGM_DEVICES, -S / -m -M / TSGM_ITER > 1 run on the first device; in --batch mode a FIRST line\n"
                         "              of that kind brings up one device for the whole batch, a later one leaves the other lines their devices)\n"
                         "resident mode: mgm --batch FILE|-   (one such command line per line of FILE, one device context for all)");
@@ -462,6 +474,17 @@ static void parse_job(Job &j)
     j.uniq_radius = (int)env_param("MGM_UNIQUENESS_RADIUS", 1);
     if (!(j.uniq >= 0 && j.uniq <= 1)) return early(1, nullptr, "mgm: MGM_UNIQUENESS must be a ratio in [0, 1]\n");
     if (j.uniq_radius < 0) return early(1, nullptr, "mgm: MGM_UNIQUENESS_RADIUS must be >= 0\n");
+    {  // (strict: a value that is no number is refused, not replaced by the default)
+        const char *sn = getenv("MGM_SPECKLE"), *sd = getenv("MGM_SPECKLE_DIFF");
+        char *end = nullptr;
+        const double n = sn ? strtod(sn, &end) : 0;
+        if (sn && (end == sn || *end || !(n >= 0 && n <= 2147483647.0) || n != std::floor(n)))
+            return early(1, nullptr, "mgm: MGM_SPECKLE must be an integer >= 0 (pixels)\n");
+        const double df = sd ? strtod(sd, &end) : 1;
+        if (sd && (end == sd || *end || !(df >= 0))) return early(1, nullptr, "mgm: MGM_SPECKLE_DIFF must be a number >= 0\n");
+        j.speckle = (int)n;
+        j.speckle_diff = (float)df;
+    }
     if (j.nscales < 1 || j.nscales > 8) return early(1, nullptr, "mgm: -S nscales must be 1..8\n");
     if (argc > 1) j.f_u = argv[1];
     if (argc > 2) j.f_v = argv[2];
@@ -612,6 +635,7 @@ static void multiscale_job(Session &S, Job &j, const Opts &o, const HostImg *plo
                 report_run(o, r);
             }
     sw.mark("enqueue");
+    if (j.speckle > 0) speckle_map(ctx, d.out, j.speckle, j.speckle_diff);  // once, on level 0's final map
     if (!j.nolr_file.empty()) j.nolr = download(ctx, d.nolr, u.nx, u.ny, 1);
     j.outoff = download(ctx, d.out, u.nx, u.ny, 1);
     sw.mark("device+download");
@@ -803,6 +827,8 @@ static int device_job(Session &S, Job &j, const std::function<void()> &decoded, 
             std::swap(L.dout, L.dspare);
             std::swap(R.dout, R.dspare);
         }
+        // MGM_SPECKLE: last, on the final left map (with several devices: `ctx` is the device that holds the gathered map)
+        if (j.speckle > 0) speckle_map(ctx, L.dout, j.speckle, j.speckle_diff);
         sw.mark("enqueue(rest)");
         j.outoff = download(ctx, L.dout, L.nx, L.ny, 1);
         sw.mark("device+download");

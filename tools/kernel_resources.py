@@ -92,8 +92,8 @@ def main():
                 n = re.sub(r"\(.*$", "", n).replace("void mgm::", "").replace("mgm::", "")
                 if a.filter and a.filter not in n:
                     continue
-                lines.append("%-22s %-64s vgpr %3d agpr %3d sgpr %3d  vgpr-spill %3d sgpr-spill %3d scratch %4d B/lane  occupancy %d" %
-                             (tag, n, r["vgpr"], r["agpr"], r["sgpr"], r["vspill"], r["sspill"], r["scratch"], r["occ"]))
+                lines.append("%-22s %-64s vgpr %3d agpr %3d sgpr %3d  vgpr-spill %3d sgpr-spill %3d scratch %4d B/lane  lds %5d B/block  occupancy %d" %
+                             (tag, n, r["vgpr"], r["agpr"], r["sgpr"], r["vspill"], r["sspill"], r["scratch"], r["lds"], r["occ"]))
             if sha:
                 lines.append("%-22s .text %8d bytes  sha256 %s" % ((tag,) + sha))
     hdr = ("# hipcc --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage, flags of mgm_amd/build.py%s\n"
