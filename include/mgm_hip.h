@@ -355,6 +355,26 @@ int mgm_uniqueness_dev(mgm_ctx *ctx, const mgm_img *d, const mgm_img *cost1, con
  * depends on no traversal order and the filter is idempotent.  Scratch: two int32 planes of the map's size, kept by the context
  * (mgm_ctx_trim releases them).  No synchronisation; the timing table lists the call as k_speckle. */
 int mgm_speckle_dev(mgm_ctx *ctx, const mgm_img *d, int maxsize, float maxdiff, mgm_img *out, mgm_img *size_map);
+/* Hole filling (DESIGN.md "hole filling"; this library's own step, the reference has none): every rejected pixel takes a value from
+ * its nearest valid neighbours along 2, 4 or 8 rays.  d is an nx x ny x 1 map, mode "median", "min" or "max", dirs 2, 4 or 8,
+ * maxdist >= 0 (0: no limit).
+ *   valid pixel  d(p) is finite; NaN and +-INF pixels are holes
+ *   directions   0 (+1,0)  1 (-1,0)  2 (0,+1)  3 (0,-1)  4 (+1,+1)  5 (-1,+1)  6 (+1,-1)  7 (-1,-1); dirs takes the first 2, 4 or 8
+ *   candidate    c_k(p) = d(p + t * step_k) for the smallest t >= 1 at which that pixel lies inside the image and is valid; none when
+ *                the ray leaves the image first, or when maxdist > 0 and t > maxdist.  Rays read the ORIGINAL map only and pass
+ *                over other holes
+ *   fill value   of a hole with n >= 1 candidates: order them by value, ascending, with the IEEE comparison, equal values by
+ *                direction index (a stable sort of the candidates in direction order: it decides which of -0 and +0 is written);
+ *                min = v[0], max = v[n-1], median = v[n/2] (the upper median).  No float arithmetic: always one of d's values
+ *   out(p)       = d(p) bit for bit on valid pixels and on holes without a candidate (NaN payloads and +-INF stay), else the fill value
+ *   filled(p)    = 1.0f where a hole received a value, 0.0f elsewhere
+ * One channel; classifying holes into occlusions and mismatches (which needs the other view) is out of scope.  out and filled may
+ * each be NULL, not both; out may be d, filled must be an image of its own; all images are one-channel and of one size; a mode
+ * that is NULL or none of the three names, dirs outside {2, 4, 8}, maxdist < 0: MGM_ERR_INVALID.  More than 2^31 - 1 pixels:
+ * MGM_ERR_UNSUPPORTED.  The result depends on no traversal order; the step is NOT idempotent (a second application may fill what the
+ * first could not reach).  Scratch: dirs float planes of the map's size and the bands' carries, kept by the context (mgm_ctx_trim
+ * releases them).  No synchronisation; the timing table lists the call as k_holes. */
+int mgm_fill_holes_dev(mgm_ctx *ctx, const mgm_img *d, const char *mode, int dirs, int maxdist, mgm_img *out, mgm_img *filled);
 /* update_dmin_dmax (mgm.cc:120-158; main() uses slack 3, radius 2) followed by the two
  * remove_nonfinite_values_Img calls (mgm.cc:387-388): dminI/dmaxI are updated in place from the disparity map. */
 int mgm_update_ranges_dev(mgm_ctx *ctx, const mgm_img *outoff, mgm_img *dminI, mgm_img *dmaxI, int slack, int radius);

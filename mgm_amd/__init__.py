@@ -33,7 +33,7 @@ ABI_SYMBOLS = [
     "mgm_ctx_set_workspace_limit", "mgm_ctx_mem_info", "mgm_ctx_set_pipeline", "mgm_img_update", "mgm_debug_probe_workspace", "mgm_ctx_set_placement_tries",
     "mgm_debug_wta_stats", "mgm_debug_download_lmin", "mgm_debug_last_pass_kernel",
     "mgm_multiscale_levels", "mgm_zoom_out_dev", "mgm_ranges_zoom_out_dev", "mgm_ranges_from_coarse_dev", "mgm_multiscale_pair_dev",
-    "mgm_wta_runnerup_dev", "mgm_uniqueness_dev", "mgm_speckle_dev",
+    "mgm_wta_runnerup_dev", "mgm_uniqueness_dev", "mgm_speckle_dev", "mgm_fill_holes_dev",
 ]
 
 MGM_OK, MGM_ERR_INVALID, MGM_ERR_UNSUPPORTED, MGM_ERR_HIP, MGM_ERR_NOMEM, MGM_ERR_INTERNAL = range(6)
@@ -118,6 +118,7 @@ def load_library():
     L.mgm_wta_runnerup_dev.argtypes = [vp, vp, i, i, i, vp, vp, vp, vp]
     L.mgm_uniqueness_dev.argtypes = [vp, vp, vp, vp, f, vp, vp]
     L.mgm_speckle_dev.argtypes = [vp, vp, i, f, vp, vp]
+    L.mgm_fill_holes_dev.argtypes = [vp, vp, cp, i, i, vp, vp]
     L.mgm_update_ranges_dev.argtypes = [vp, vp, vp, vp, i, i]
     L.mgm_leftright_dev.argtypes = [vp, vp, vp, f, vp]
     L.mgm_backproject_dev.argtypes = [vp, vp, vp, vp, vp]
@@ -425,6 +426,29 @@ class Context:
                 im.free()
             raise
         return (out if out else None), size_map
+
+    def fill_holes_dev(self, d, mode="median", dirs=8, maxdist=0, out=None, want_filled=False):
+        """Hole filling (mgm_fill_holes_dev): every non-finite pixel of d takes the median / min / max of the nearest finite pixels
+        along the first `dirs` (2, 4, 8) of the rays (+1,0) (-1,0) (0,+1) (0,-1) (+1,+1) (-1,+1) (+1,-1) (-1,-1), at most maxdist steps
+        away (0: no limit); rays read the original map.  Device images (out, filled).  out: an image to write (d itself is allowed),
+        None for a new one, False for none; filled (1 where a hole received a value, else 0) is None without want_filled."""
+        _, ny, nx = d.shape
+        mine = []  # the images made here: freed if the call fails
+        try:
+            if out is None:
+                out = self.new_image(nx, ny)
+                mine.append(out)
+            filled = None
+            if want_filled:
+                filled = self.new_image(nx, ny)
+                mine.append(filled)
+            self._chk(self.lib.mgm_fill_holes_dev(self.h, d.h, None if mode is None else str(mode).encode(), dirs, maxdist,
+                                                  out.h if out else None, filled.h if want_filled else None))
+        except Exception:
+            for im in mine:
+                im.free()
+            raise
+        return (out if out else None), filled
 
     def pair_right_from_left(self, u, v, dmin, dmax, P1=8.0, P2=32.0, NDIR=4, TSGM=4, use_fh=0, fix_overcount=1, aP2=1.0, aThresh=5.0,
                              prefilter="none", distance="ad", truncDist=float("inf"), census_win=3, refine="none", tau=1.0, median=0):

@@ -675,6 +675,41 @@ int mgm_speckle_dev(mgm_ctx *c, const mgm_img *d, int maxsize, float maxdiff, mg
     return MGM_OK;
 }
 
+// Hole filling (mgm_holes.hip): plan_holes decides the chunk, the band, the grids and the scratch, every phase is a
+// launch of its own on the context's stream.  "k_holes" brackets the call in the timing table, each phase is listed inside it under
+// its own name (dirs = 2 has no column and no diagonal phases).
+int mgm_fill_holes_dev(mgm_ctx *c, const mgm_img *d, const char *mode, int dirs, int maxdist, mgm_img *out, mgm_img *filled)
+{
+    if (int jr = pipe_join(c)) return jr;  // (pipelined context: run what has been deferred first)
+    if (!c || !d || (!out && !filled)) return fail(c, MGM_ERR_INVALID, "mgm_fill_holes: null argument (at least one of out, filled)");
+    const int m = !mode ? -1 : (!strcmp(mode, "median") ? 0 : (!strcmp(mode, "min") ? 1 : (!strcmp(mode, "max") ? 2 : -1)));
+    if (m < 0) return fail(c, MGM_ERR_INVALID, "mgm_fill_holes: mode must be median, min or max");
+    if (dirs != 2 && dirs != 4 && dirs != 8) return fail(c, MGM_ERR_INVALID, "mgm_fill_holes: dirs must be 2, 4 or 8");
+    if (maxdist < 0) return fail(c, MGM_ERR_INVALID, "mgm_fill_holes: maxdist must be >= 0 (0: no limit)");
+    for (const mgm_img *im : {d, (const mgm_img *)out, (const mgm_img *)filled})
+        if (im && (im->nx != d->nx || im->ny != d->ny || im->nch != 1)) return fail(c, MGM_ERR_INVALID, "mgm_fill_holes: image size mismatch (one channel, one size)");
+    if (filled && (filled == d || filled == out)) return fail(c, MGM_ERR_INVALID, "mgm_fill_holes: filled must be an image of its own");
+    const HolesChoice choice = plan_holes(HolesRequest{d->nx, d->ny, dirs, c->num_cu});
+    if (choice.family == kHolesRefuse) return fail(c, MGM_ERR_UNSUPPORTED, "mgm_fill_holes: more than 2^31 - 1 pixels (pixel coordinates are int32)");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (int r = reserve(c, c->holes, (size_t)choice.scratch_bytes)) return r;
+    HolesParams p{};
+    p.d = d->d;
+    p.out = out ? out->d : nullptr;
+    p.filled = filled ? filled->d : nullptr;
+    p.planes = (float *)c->holes.p;
+    p.cpos = (int *)(p.planes + (size_t)choice.planes * d->nx * d->ny);
+    p.cval = (float *)(p.cpos + choice.carry_words);
+    p.nx = d->nx, p.ny = d->ny, p.dirs = dirs, p.maxdist = maxdist, p.mode = m;
+    TimeScope t(c, "k_holes");
+    for (int phase = 0; phase < kHolesPhases; phase++) {
+        if (!holes_phase_runs(phase, dirs)) continue;
+        TimeScope tp(c, holes_phase_name(phase));
+        if (hipError_t e = launch_holes_phase(phase, p, choice, c->stream)) return hipfail(c, e, holes_phase_name(phase));
+    }
+    return MGM_OK;
+}
+
 int mgm_leftright_dev(mgm_ctx *c, const mgm_img *d, const mgm_img *other, float tau, mgm_img *out)
 {
     if (int jr = pipe_join(c)) return jr;  // (pipelined context: run what has been deferred first)

@@ -140,6 +140,24 @@ enum SpecklePhase { kSpeckleLocal = 0, kSpeckleSeams, kSpeckleCount, kSpeckleApp
 const char *speckle_phase_name(int phase);  // "k_speckle_local", ...
 hipError_t launch_speckle_phase(int phase, const SpeckleParams &p, const SpeckleChoice &c, hipStream_t s);
 
+// hole filling (mgm_holes.hip): per hole (a non-finite pixel) the nearest finite pixel along each of `dirs` rays of
+// the ORIGINAL map, at most maxdist steps away (0: any); out = their median / minimum / maximum, filled = 1 where a hole got a value
+struct HolesParams {
+    const float *d;       // [nx*ny] the map (out may be d: k_holes_apply reads d[p] before it writes out[p], the candidates are finished)
+    float *out, *filled;  // each may be nullptr
+    float *planes;        // scratch: `dirs` candidate planes of nx*ny floats, plane k written at every hole by direction k (NaN: none)
+    int *cpos;            // scratch: the bands' carry-outs of directions 2.., [direction - 2][band][line]: the row of the band's last
+    float *cval;          //          finite pixel in walking order on that line (-1: none) and its value
+    int nx, ny, dirs, maxdist;
+    int mode;             // 0 median (upper), 1 min, 2 max
+};
+struct HolesChoice;  // (mgm_planner.h: what plan_holes decided)
+enum HolesPhase { kHolesRows = 0, kHolesCarry, kHolesWalk, kHolesApply, kHolesPhases };
+const char *holes_phase_name(int phase);  // "k_holes_rows", ...
+// dirs = 2 has no columns and no diagonals: its carry and walk phases launch nothing (the caller skips them: holes_phase_runs)
+inline bool holes_phase_runs(int phase, int dirs) { return dirs > 2 || (phase != kHolesCarry && phase != kHolesWalk); }
+hipError_t launch_holes_phase(int phase, const HolesParams &p, const HolesChoice &c, hipStream_t s);
+
 // ---- ragged volumes in the range-proportional layout (mgm_pass_rel.hip, k_wta_rel): 64 label slots per pixel placed at the
 // pixel's own window, slot k <-> disparity base + k
 struct RelVolume {

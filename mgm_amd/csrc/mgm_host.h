@@ -208,6 +208,7 @@ struct mgm_ctx {
     // debug statistics on), wta_stats_n: searches counted into it since the last aggregation call began (0: none was pruned)
     Buf lmin, wta_stats;  // (wta_stats: kWtaStatBytes)
     Buf speckle;          // mgm_speckle_dev: the parent and count planes of its labelling (plan_speckle's scratch_bytes)
+    Buf holes;            // mgm_fill_holes_dev: the candidate planes and the bands' carries (plan_holes's scratch_bytes)
     int wta_stats_n = 0;
     DenseRun last;    // the last aggregation, if it was a dense one ...
     RelRun rel_last;  // ... or a range-proportional one (each remember stage clears the other)

@@ -6,6 +6,7 @@
 // The winner search is planned here as well (plan_wta, plan_wta_right, plan_wta_runnerup, plan_wta_rel at the end: which
 // instance, which grid, pruned or not); tests/test_wta_plan.py, tests/test_runnerup_plan.py.
 // ... and the speckle filter's tile, grids and scratch (plan_speckle); tests/test_speckle_plan.py.
+// ... and hole filling's chunk, band, grids and scratch (plan_holes); tests/test_holes_plan.py.
 // ... and which kernels take an aggregation call at all (plan_agg_route, plan_subbatch, plan_dense_kernels behind them: pure functions
 // that ASK for the facts of the device they need, one at a time); tests/test_route_plan.py.
 #pragma once
@@ -1031,6 +1032,62 @@ inline SpeckleChoice plan_speckle(const SpeckleRequest &q)
     c.grid_local = (long long)c.ntx * c.nty;
     c.grid_seams = std::max(1ll, (pairs + kSpeckleThreads - 1) / kSpeckleThreads);
     c.grid_count = c.grid_apply = (npix + kSpeckleThreads - 1) / kSpeckleThreads;
+    return c;
+}
+
+// ---- hole filling (mgm_holes.hip) ----------------------------------------------------------------------------------
+// Per direction a running "last valid pixel" along rows, columns and diagonals: k_holes_rows takes a row per wave in chunks of
+// `chunk` pixels (directions 0, 1); k_holes_carry / k_holes_walk take one lane per column or diagonal and one band of `band` rows
+// per workgroup row (directions 2..7: first every band's carry-out, then every band from its carry-in); k_holes_apply runs one
+// thread per pixel.  The chunk, the band, the grids and the scratch are decided here and nowhere else; tests/test_holes_plan.py.
+struct HolesRequest {
+    int nx, ny;
+    int dirs;    // 2, 4 or 8
+    int num_cu;  // compute units of the device (0: unknown).  Chunk and band are one choice per shape today: the field is part of the
+                 // request so that a choice by the device's width stays this function's decision
+};
+static_assert(std::has_unique_object_representations_v<HolesRequest>, "HolesRequest: integers only, no padding");
+enum HolesFamily { kHolesRefuse = 0, kHolesLines };
+struct HolesChoice {
+    long long scratch_bytes;  // 4 * (planes * nx*ny + 2 * carry_words)
+    long long grid_rows;      // k_holes_rows: workgroups of kHolesThreads threads, one wave per (row, direction 0 / 1)
+    long long grid_walk;      // k_holes_carry, k_holes_walk: workgroups along the lines; the launch is grid_walk x nbands x walk_dirs
+    long long grid_apply;     // k_holes_apply: one thread per pixel
+    long long nlines;         // lanes of a band: nx + ny - 1 diagonals (the columns are the first nx of them)
+    long long carry_words;    // words of ONE carry plane (positions int32, values float): walk_dirs * nbands * nlines
+    int family;
+    int chunk;      // pixels of a row that a wave takes at a time
+    int band;       // rows per band
+    int nbands;     // bands (the last one may be ragged); at most `band` of them, see plan_holes
+    int walk_dirs;  // directions 2 .. dirs-1: 0, 2 or 6
+    int planes;     // candidate planes of nx*ny floats: dirs
+};
+static_assert(std::has_unique_object_representations_v<HolesChoice>, "HolesChoice: integers only, no padding");
+constexpr int kHolesThreads = 256, kHolesChunk = 64, kHolesMinBand = 64;  // (the chunk is a wave's width: one pixel per lane)
+constexpr long long kHolesMaxPixels = 2147483647ll;  // pixel coordinates, distances and line indices are int32 / fit 2^32
+inline HolesChoice plan_holes(const HolesRequest &q)
+{
+    HolesChoice c{};
+    if (q.nx < 1 || q.ny < 1 || (long long)q.nx * q.ny > kHolesMaxPixels) return c;
+    if (q.dirs != 2 && q.dirs != 4 && q.dirs != 8) return c;
+    const long long npix = (long long)q.nx * q.ny;
+    c.family = kHolesLines;
+    c.chunk = kHolesChunk;
+    // the band: at least kHolesMinBand rows and at least sqrt(ny), so that there are never more bands than a band has rows -- the
+    // walk kernel looks back over the earlier bands' carry-outs, at most nbands - 1 of them per lane, which then costs no more than
+    // the band's own walk
+    long long b = kHolesMinBand;
+    while (b * b < q.ny) b++;
+    c.band = (int)b;
+    c.nbands = (int)((q.ny + b - 1) / b);
+    c.walk_dirs = q.dirs - 2;
+    c.planes = q.dirs;
+    c.nlines = (long long)q.nx + q.ny - 1;
+    c.carry_words = (long long)c.walk_dirs * c.nbands * c.nlines;
+    c.scratch_bytes = 4 * ((long long)c.planes * npix + 2 * c.carry_words);
+    c.grid_rows = (2ll * q.ny * kHolesChunk + kHolesThreads - 1) / kHolesThreads;
+    c.grid_walk = (c.nlines + kHolesThreads - 1) / kHolesThreads;
+    c.grid_apply = (npix + kHolesThreads - 1) / kHolesThreads;
     return c;
 }
 

@@ -340,6 +340,12 @@ static void speckle_map(mgm_ctx *ctx, mgm_img *d, int maxsize, float maxdiff)
     if (int rc = mgm_speckle_dev(ctx, d, maxsize, maxdiff, d, nullptr)) die(ctx, rc, "mgm_speckle");
 }
 
+// MGM_FILL_HOLES=median|min|max: hole filling, in place, on a job's FINAL left map, after every rejection step
+static void fill_holes_map(mgm_ctx *ctx, mgm_img *d, const std::string &mode, int dirs, int maxdist)
+{
+    if (int rc = mgm_fill_holes_dev(ctx, d, mode.c_str(), dirs, maxdist, d, nullptr)) die(ctx, rc, "mgm_fill_holes");
+}
+
 // iterations 2..TSGM_ITER of main()'s loop (mgm.cc:377-388): the ranges narrow around the previous solution
 // (update_dmin_dmax), the volume -- and with it every scan-line pass -- stays the same, so only the winner search and
 // the refinement are redone, on the Lr volumes the context still holds
@@ -398,6 +404,9 @@ struct Job {
     int uniq_radius = 1;      // MGM_UNIQUENESS_RADIUS: labels around the winner the runner-up stays away from
     int speckle = 0;          // MGM_SPECKLE: components of the final left map of at most this many pixels go (0: off)
     float speckle_diff = 1;   // MGM_SPECKLE_DIFF: neighbours are joined up to this difference
+    std::string fill;         // MGM_FILL_HOLES: median, min or max -- the final left map's holes are filled (empty: off)
+    int fill_dirs = 8;        // MGM_FILL_HOLES_DIRS: 2, 4 or 8 rays
+    int fill_dist = 0;        // MGM_FILL_HOLES_DIST: a candidate is at most this many steps away (0: no limit)
     int early = -1;           // >= 0: the command line ends before any work with this code ...
     std::string early_out;    // ... after these lines on stdout
     std::string early_err;    // ... and stderr
@@ -443,8 +452,14 @@ static void parse_job(Job &j)
                         "              MGM_DEVICES: exit code 2)\n"
                         "             MGM_SPECKLE=0 (n > 0: the speckle filter -- every 4-connected component of finite pixels of the final left map,\n"
                         "              neighbours joined where they differ by at most MGM_SPECKLE_DIFF=1, that has at most n pixels becomes NaN; runs\n"
-                        "              last, after MEDIAN and the left-right test and before the back-projected image, with -S on the full-size map\n"
-                        "              only; leaves the -l map, the cost map and stdout as they are; combines with every other mode)\n"
+                        "              last but for MGM_FILL_HOLES, after MEDIAN and the left-right test and before the back-projected image, with -S\n"
+                        "              on the full-size map only; leaves the -l map, the cost map and stdout as they are; combines with every other mode)\n"
+                        "             MGM_FILL_HOLES=none (median, min or max: hole filling -- every non-finite pixel of the final left map takes the\n"
+                        "              median (the upper one) / minimum / maximum of the nearest finite pixels along the first MGM_FILL_HOLES_DIRS=8\n"
+                        "              (2, 4 or 8) of the rays (+1,0) (-1,0) (0,+1) (0,-1) (+1,+1) (-1,+1) (+1,-1) (-1,-1), each at most\n"
+                        "              MGM_FILL_HOLES_DIST=0 steps away (0: no limit); rays read the unfilled map; a hole that no ray serves stays;\n"
+                        "              runs last, after MGM_SPECKLE, and before the back-projected image, with -S on the full-size map only; leaves\n"
+                        "              the -l map, the cost map, -c's map and stdout as they are; combines with every other mode)\n"
                         "             (with several MGM_DEVICES, -S / -m -M / TSGM_ITER > 1 run on the first device; in --batch mode a FIRST line\n"
                         "              of that kind brings up one device for the whole batch, a later one leaves the other lines their devices)\n"
                         "resident mode: mgm --batch FILE|-   (one such command line per line of FILE, one device context for all)");
@@ -484,6 +499,21 @@ static void parse_job(Job &j)
         if (sd && (end == sd || *end || !(df >= 0))) return early(1, nullptr, "mgm: MGM_SPECKLE_DIFF must be a number >= 0\n");
         j.speckle = (int)n;
         j.speckle_diff = (float)df;
+    }
+    {  // (as strict)
+        const char *fm = getenv("MGM_FILL_HOLES"), *fd = getenv("MGM_FILL_HOLES_DIRS"), *fl = getenv("MGM_FILL_HOLES_DIST");
+        const std::string m = fm ? fm : "";
+        if (!(m.empty() || m == "none" || m == "median" || m == "min" || m == "max"))
+            return early(1, nullptr, "mgm: MGM_FILL_HOLES must be median, min, max or none\n");
+        char *end = nullptr;
+        const double nd = fd ? strtod(fd, &end) : 8;
+        if (fd && (end == fd || *end || !(nd == 2 || nd == 4 || nd == 8))) return early(1, nullptr, "mgm: MGM_FILL_HOLES_DIRS must be 2, 4 or 8\n");
+        const double dist = fl ? strtod(fl, &end) : 0;
+        if (fl && (end == fl || *end || !(dist >= 0 && dist <= 2147483647.0) || dist != std::floor(dist)))
+            return early(1, nullptr, "mgm: MGM_FILL_HOLES_DIST must be an integer >= 0 (steps; 0: no limit)\n");
+        j.fill = m == "none" ? "" : m;
+        j.fill_dirs = (int)nd;
+        j.fill_dist = (int)dist;
     }
     if (j.nscales < 1 || j.nscales > 8) return early(1, nullptr, "mgm: -S nscales must be 1..8\n");
     if (argc > 1) j.f_u = argv[1];
@@ -636,6 +666,7 @@ static void multiscale_job(Session &S, Job &j, const Opts &o, const HostImg *plo
             }
     sw.mark("enqueue");
     if (j.speckle > 0) speckle_map(ctx, d.out, j.speckle, j.speckle_diff);  // once, on level 0's final map
+    if (!j.fill.empty()) fill_holes_map(ctx, d.out, j.fill, j.fill_dirs, j.fill_dist);  // ... and after it
     if (!j.nolr_file.empty()) j.nolr = download(ctx, d.nolr, u.nx, u.ny, 1);
     j.outoff = download(ctx, d.out, u.nx, u.ny, 1);
     sw.mark("device+download");
@@ -829,6 +860,8 @@ static int device_job(Session &S, Job &j, const std::function<void()> &decoded, 
         }
         // MGM_SPECKLE: last, on the final left map (with several devices: `ctx` is the device that holds the gathered map)
         if (j.speckle > 0) speckle_map(ctx, L.dout, j.speckle, j.speckle_diff);
+        // MGM_FILL_HOLES: after every rejection step, before the back-projected image is made
+        if (!j.fill.empty()) fill_holes_map(ctx, L.dout, j.fill, j.fill_dirs, j.fill_dist);
         sw.mark("enqueue(rest)");
         j.outoff = download(ctx, L.dout, L.nx, L.ny, 1);
         sw.mark("device+download");
