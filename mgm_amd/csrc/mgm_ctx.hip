@@ -49,7 +49,8 @@ const DevSwitches &dev()
 long long lr_pad_floats() { return dev().lr_pad; }
 const WtaSwitches &wta_switches()
 {
-    static const WtaSwitches w{(int)tune_num("wta_prune_ppw", 2), (int)tune_num("wta_prune_wg", 0), (int)tune_num("wta_wg_per_cu", 0),
+    // (wta_prune_ppw: 1 since the search keeps two rounds of chunk loads in flight, which only the PPW = 1 instances have registers for)
+    static const WtaSwitches w{(int)tune_num("wta_prune_ppw", 1),(int)tune_num("wta_prune_wg", 0), (int)tune_num("wta_wg_per_cu", 0),
                                tune_num("wta_packed", 1) != 0, tune_num("wta_wide4", 1) != 0, tune_num("wta_quad", 1) != 0,
                                (int)tune_num("wta_right_seg", 0)};
     return w;

@@ -286,7 +286,7 @@ const DevSwitches &dev();
 long long lr_pad_floats();
 // ... and the winner search's (MGM_HIP_TUNE=wta_*; A/B timing), copied into every request of its planner (plan_wta, plan_wta_right)
 struct WtaSwitches {
-    int prune_ppw;  // wta_prune_ppw=1|2: groups of eight pixels per wave and turn of the pruned search (k_wta_pruned's PPW)
+    int prune_ppw;  // wta_prune_ppw=1|2: groups of eight pixels per wave and turn of the pruned search (k_wta_pruned's PPW; default 1)
     int prune_wg;   // wta_prune_wg=<workgroups per CU> of the pruned search (0: 64)
     int wg_per_cu;  // wta_wg_per_cu=<workgroups per CU> of the plain search (0: by the instance)
     int packed;     // wta_packed=0: one pixel per slab also at 128 / 64 labels

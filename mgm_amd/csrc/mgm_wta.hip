@@ -407,9 +407,13 @@ __global__ void __launch_bounds__(256) k_wta_any(const WtaParams P)
 //   (b) the chunk with the smallest LB (the lowest one on ties) loads its Lr pieces: best0 = its smallest finite S (+INF: none);
 //   (c) every other chunk with LB <= best0 loads too -- the set is fixed here, `<=` keeps a tie at a lower label in play; a chunk
 //       that stays out has S >= LB > best0 on all its labels;
-//   (d) first strict minimum among the finite S of what was loaded = the smallest (S, label); vfit recomputes S at the winner
-//       and its two neighbours from memory (lines just read, but for a neighbour in a chunk that stayed out);
+//   (d) first strict minimum among the finite S of what was loaded = the smallest (S, label); vfit takes S at the winner's two
+//       neighbours from the lane that brought the winner (it held them when it took the label) and reads memory only for a
+//       neighbour in another chunk (winner at label 32k or 32k + 31), by sum_fix's operations: the same float;
 //   (e) nothing finite: NaN label, +INF cost, as in k_wta.
+// The steps of a turn are round trips to memory, each starting after the last, and the waves wait on them (profiles/r09_*): (a) of the
+// NEXT turn is asked for as soon as this turn's is consumed, (d) has no round trip of its own but for the edge labels, and with one
+// group of pixels per wave (c) keeps two rounds in flight.
 // On census volumes 1.8-2 of the 8 chunks of a pixel are loaded: 2.4 KB per pixel instead of 8.4.
 //
 // The layout: a pixel is a GROUP of eight lanes, a wave works on eight consecutive pixels at once (two per DPP row of 16 lanes).
@@ -476,22 +480,31 @@ __device__ __forceinline__ void wta_pruned(const WtaParams &P)
     const int ndir = ND, fix = P.FIX;
     const long long mstride = P.nvol / 32;  // chunk minima per pass
     unsigned nloaded = 0, npx = 0;          // (mgm_debug_wta_stats) of this wave
-    for (long long g0 = ((long long)blockIdx.x * 4 + wv) * (8 * PPW); g0 < P.npix; g0 += (long long)gridDim.x * 4 * 8 * PPW) {
+    const long long turn = (long long)gridDim.x * 4 * 8 * PPW;
+    long long g0 = ((long long)blockIdx.x * 4 + wv) * (8 * PPW);
+    // (a) the chunk's costs and minima, of the turn that starts at pixel g: asked for one turn ahead
+    uint4 cq[PPW][2];
+    float mn[PPW][MAXD];
+    auto load_a = [&](const long long g) {
+#pragma unroll
+        for (int u = 0; u < PPW; u++) {
+            const long long q = g + 8 * u + (lane >> 3), px = q < P.npix ? q : P.npix - 1;
+            const uint4 *cp = reinterpret_cast<const uint4 *>(P.C8 + px * L + j * 32);
+            cq[u][0] = cp[0], cq[u][1] = cp[1];
+#pragma unroll
+            for (int p = 0; p < MAXD; p++)
+                if (p < ndir) mn[u][p] = P.Lmin[(long long)p * mstride + px * (L / 32) + j];
+        }
+    };
+    if (g0 < P.npix) load_a(g0);
+    for (; g0 < P.npix; g0 += turn) {
         long long pix[PPW];
         bool own[PPW];  // the group's pixel exists (the groups past the last pixel repeat it and write nothing)
-        // (a) the chunk's costs and minima
-        uint4 cq[PPW][2];
-        float mn[PPW][MAXD];
 #pragma unroll
         for (int u = 0; u < PPW; u++) {
             const long long q = g0 + 8 * u + (lane >> 3);
             own[u] = q < P.npix;
             pix[u] = own[u] ? q : P.npix - 1;
-            const uint4 *cp = reinterpret_cast<const uint4 *>(P.C8 + pix[u] * L + j * 32);
-            cq[u][0] = cp[0], cq[u][1] = cp[1];
-#pragma unroll
-            for (int p = 0; p < MAXD; p++)
-                if (p < ndir) mn[u][p] = P.Lmin[(long long)p * mstride + pix[u] * (L / 32) + j];
         }
         float clb[PPW];
         int seed[PPW];  // the seed chunk, -1: no label can hold a finite S
@@ -514,12 +527,12 @@ __device__ __forceinline__ void wta_pruned(const WtaParams &P)
             const unsigned at = (unsigned)(__builtin_amdgcn_ballot_w64(lb == gmin) >> gsh) & 255u;  // (never 0: gmin is one of them)
             seed[u] = gmin < f_inf() ? __builtin_ctz(at | 256u) : -1;
         }
+        // cq and mn are consumed: the next turn's go out now and arrive behind (b), (c) and the stores of this one
+        if (g0 + turn < P.npix) load_a(g0 + turn);
         // The group's eight lanes read chunk ck[u] of their pixel, lane j its labels 4j..: a 128-byte line per pass, the requests of all
-        // passes (and pixels) back to back; S of those four labels.  (Loaded and consumed in one block: what a lane would carry
-        // across a branch it sat out stays live for the whole loop.)
-        auto chunk_S = [&](const int (&ck)[PPW], float (&S)[PPW][4]) {
-            float l[PPW][MAXD][4];
-            unsigned cw[PPW];
+        // passes (and pixels) back to back; then S of those four labels.  (chunk_S, loaded and consumed in one block, wherever one
+        // round is in flight: what a lane would carry across a branch it sat out stays live for the whole loop.)
+        auto chunk_load =[&](const int (&ck)[PPW], float (&l)[PPW][MAXD][4], unsigned (&cw)[PPW]) {
 #pragma unroll
             for (int u = 0; u < PPW; u++) {
                 const long long at = pix[u] * L + ck[u] * 32 + j * 4;
@@ -531,6 +544,8 @@ __device__ __forceinline__ void wta_pruned(const WtaParams &P)
                         l[u][p][0] = q.x, l[u][p][1] = q.y, l[u][p][2] = q.z, l[u][p][3] = q.w;
                     }
             }
+        };
+        auto chunk_sum = [&](const float (&l)[PPW][MAXD][4], const unsigned (&cw)[PPW], float (&S)[PPW][4]) {
 #pragma unroll
             for (int u = 0; u < PPW; u++) {
                 float c[4];
@@ -539,10 +554,33 @@ __device__ __forceinline__ void wta_pruned(const WtaParams &P)
                 sum_fix<MAXD>(l[u], c, ndir, fix, S[u]);
             }
         };
+        auto chunk_S = [&](const int (&ck)[PPW], float (&S)[PPW][4]) {
+            float l[PPW][MAXD][4];
+            unsigned cw[PPW];
+            chunk_load(ck, l, cw);
+            chunk_sum(l, cw, S);
+        };
         // (b) the seed chunks
         float best[PPW];
         int bi[PPW], sck[PPW];
         unsigned cand[PPW];  // the chunks (c) still has to load, a bit each
+        // S at the two labels beside the lane's best one, for vfit: kept whenever the lane takes a label -- its own values, or the
+        // edge value of the lane beside it (row_shr:1, row_shl:1).  Lanes 0 and 7 of a group get another group's value for a label
+        // that lies in another chunk, b % 32 == 0 or 31: (d) knows that from b and fetches S there from memory.
+        float nlo[PPW], nhi[PPW];
+        auto take = [&](const int u, const float (&S)[4], const int ck, const bool ties) {
+            const float lo = dpp_f<0x111>(S[3]), hi = dpp_f<0x101>(S[0]);
+#pragma unroll
+            for (int k = 0; k < 4; k++) {  // ((c)'s chunks do not arrive by rising label: there the lower label wins a tie)
+                const int o = ck * 32 + j * 4 + k;
+                if (finite_bits(S[k]) && (S[k] < best[u] || (ties && S[k] == best[u] && o < bi[u]))) {
+                    best[u] = S[k];
+                    bi[u] = o;
+                    nlo[u] = k > 0 ? S[k > 0 ? k - 1 : 0] : lo;
+                    nhi[u] = k < 3 ? S[k < 3 ? k + 1 : 3] : hi;
+                }
+            }
+        };
         {
             float S[PPW][4];
 #pragma unroll
@@ -552,14 +590,8 @@ __device__ __forceinline__ void wta_pruned(const WtaParams &P)
             for (int u = 0; u < PPW; u++) {
                 best[u] = f_inf();
                 bi[u] = NONE;
-                if (seed[u] >= 0) {
-#pragma unroll
-                    for (int k = 0; k < 4; k++)
-                        if (finite_bits(S[u][k]) && best[u] > S[u][k]) {
-                            best[u] = S[u][k];
-                            bi[u] = seed[u] * 32 + j * 4 + k;
-                        }
-                }
+                nlo[u] = nhi[u] = 0.0f;
+                if (seed[u] >= 0) take(u, S[u], seed[u], false);
                 const float best0 = group_fmin(best[u]);
                 // (c)'s set, fixed here: lane (g, j) speaks for chunk j of its pixel
                 const bool cd = seed[u] >= 0 && j != seed[u] && clb[u] <= best0;
@@ -571,63 +603,102 @@ __device__ __forceinline__ void wta_pruned(const WtaParams &P)
             }
         }
         // (c) while any group has a candidate left: every group loads its lowest one; a group without any sits the round out under
-        // the exec mask (with several pixels per group of lanes: one whose other pixel still has some reads its seed's line again)
-        for (;;) {
-            bool more = false;
+        // the exec mask (with several pixels per group of lanes: one whose other pixel still has some reads its seed's line again).
+        // One group of pixels per wave: the set is fixed, so the next round's loads go out BEFORE this round's are consumed -- two
+        // rounds' registers, A and B, in turn (160 VGPRs at 8 passes; with two groups per wave that would be all 256).
+        if constexpr (PPW == 1) {
+            float lA[PPW][MAXD][4], lB[PPW][MAXD][4];
+            unsigned cwA[PPW], cwB[PPW];
+            int ckA[PPW], ckB[PPW];
+            bool actA[PPW], actB[PPW];
+            auto issue = [&](int (&ck)[PPW], bool (&act)[PPW], float (&l)[PPW][MAXD][4], unsigned (&cw)[PPW]) {
+                bool more = false;
 #pragma unroll
-            for (int u = 0; u < PPW; u++) more = more || cand[u] != 0u;
-            if (!__builtin_amdgcn_ballot_w64(more)) break;
-            if (more) {
-                int ck[PPW];
+                for (int u = 0; u < PPW; u++) {
+                    act[u] = cand[u] != 0u;
+                    ck[u] = act[u] ? __builtin_ctz(cand[u]) : sck[u];
+                    cand[u] &= cand[u] - 1u;
+                    more = more || act[u];
+                }
+                if (!__builtin_amdgcn_ballot_w64(more)) return false;
+                if (more) chunk_load(ck, l, cw);
+                return true;
+            };
+            auto consume = [&](const int (&ck)[PPW], const bool (&act)[PPW], const float (&l)[PPW][MAXD][4], const unsigned (&cw)[PPW]) {
                 float S[PPW][4];
-#pragma unroll
-                for (int u = 0; u < PPW; u++) ck[u] = cand[u] != 0u ? __builtin_ctz(cand[u]) : sck[u];
-                chunk_S(ck, S);
+                chunk_sum(l, cw, S);
 #pragma unroll
                 for (int u = 0; u < PPW; u++)
-                    if (cand[u] != 0u) {
+                    if (act[u]) take(u, S[u], ck[u], true);
+            };
+            if (issue(ckA, actA, lA, cwA))
+                for (;;) {
+                    const bool nb = issue(ckB, actB, lB, cwB);
+                    consume(ckA, actA, lA, cwA);
+                    if (!nb) break;
+                    const bool na = issue(ckA, actA, lA, cwA);
+                    consume(ckB, actB, lB, cwB);
+                    if (!na) break;
+                }
+        } else {
+            for (;;) {
+                bool more = false;
 #pragma unroll
-                        for (int k = 0; k < 4; k++) {  // (the chunks do not arrive by rising label: the lower label wins a tie)
-                            const int o = ck[u] * 32 + j * 4 + k;
-                            if (finite_bits(S[u][k]) && (S[u][k] < best[u] || (S[u][k] == best[u] && o < bi[u]))) {
-                                best[u] = S[u][k];
-                                bi[u] = o;
-                            }
+                for (int u = 0; u < PPW; u++) more = more || cand[u] != 0u;
+                if (!__builtin_amdgcn_ballot_w64(more)) break;
+                if (more) {
+                    int ck[PPW];
+                    float S[PPW][4];
+#pragma unroll
+                    for (int u = 0; u < PPW; u++) ck[u] = cand[u] != 0u ? __builtin_ctz(cand[u]) : sck[u];
+                    chunk_S(ck, S);
+#pragma unroll
+                    for (int u = 0; u < PPW; u++)
+                        if (cand[u] != 0u) {
+                            take(u, S[u], ck[u], true);
+                            cand[u] &= cand[u] - 1u;
                         }
-                        cand[u] &= cand[u] - 1u;
-                    }
+                }
             }
         }
 #pragma unroll
         for (int u = 0; u < PPW; u++) {
             // (d) first strict minimum among the finite entries by rising label: the group's smallest (S, label)
+            const int mine = bi[u];
             dpp_take<0xB1>(best[u], bi[u]);
             dpp_take<0x4E>(best[u], bi[u]);
             dpp_take<0x141>(best[u], bi[u]);
             const int b = bi[u];
+            // the lane that brought the winner writes the pixel: it holds S beside it (lane 0 where there is no winner)
+            const bool writer = b == NONE ? j == 0 : mine == b;
             float outv, outc = best[u];
             if (b == NONE) outv = __builtin_nanf("");  // the reference leaves minP uninitialised here
             else outv = (float)(b + P.dmin);
             if (P.refine == 1) {  // (wave-uniform)
                 const bool gate = b != NONE && b - 1 >= 0 && b + 2 <= L - 1;  // mgm_refine.h:58
-                // lanes 0..2 of the group: S at b-1, b, b+1 from memory, by sum_fix's operations in its order (the same float)
-                float a = 0.0f;
-                if (gate && j < 3) {
-                    const long long at = pix[u] * L + (b - 1 + j);
+                // a winner at the first or last label of its chunk: S beside it, in the next chunk, from memory, by sum_fix's operations
+                // in its order (the same float) -- whether that chunk was loaded or not.  One ballot: most waves have none.
+                const bool below = (b & 31) == 0, fetch = writer && gate && (below || (b & 31) == 31);
+                if (__builtin_amdgcn_ballot_w64(fetch)) {
+                    if (fetch) {
+                        const long long at = pix[u] * L + (below ? b - 1 : b + 1);
+                        float a = 0.0f;
 #pragma unroll
-                    for (int p = 0; p < MAXD; p++)
-                        if (p < ndir) a = a + P.Lr[(long long)p * P.nvol + at];
-                    if (fix == 1) a = a - (float)(ndir - 1) * c8_decode(P.C8[at]);
+                        for (int p = 0; p < MAXD; p++)
+                            if (p < ndir) a = a + P.Lr[(long long)p * P.nvol + at];
+                        if (fix == 1) a = a - (float)(ndir - 1) * c8_decode(P.C8[at]);
+                        if (below) nlo[u] = a;
+                        else nhi[u] = a;
+                    }
                 }
-                const float v1 = dpp_f<0xB1>(a), v2 = dpp_f<0x4E>(a);  // (lane 0 of the group: those of lanes 1 and 2)
                 if (gate) {
                     float vmin, dx;
-                    vfit(a, v1, v2, vmin, dx);
+                    vfit(nlo[u], best[u], nhi[u], vmin, dx);
                     outv = (float)(b + P.dmin) + dx;
                     outc = vmin;
                 }
             }
-            if (j == 0 && own[u]) {
+            if (writer && own[u]) {
                 P.out[pix[u]] = outv;
                 P.outcost[pix[u]] = outc;
             }
