@@ -261,6 +261,24 @@ int mgm_multi_aggregate(mgm_multi *m, const mgm_cv *const *C, const mgm_img *con
  * call on this ctx into `dense` ([ny][nx][L]). */
 int mgm_debug_download_lr(mgm_ctx *ctx, int pass, float *dense);
 
+/* Test aid (tests/test_gpu_wta_rel_crafted.py): the device pointer of pass `pass`'s Lr volume of volume 0 of the LAST aggregation on
+ * this ctx, when that aggregation ran on the volume's range-proportional copy: [ny * nx][*slots] floats, slot k of a pixel = the
+ * disparity record[0] + k, where the pixel's record is the four ints (disparity of slot 0 = its lowest disparity - 1, lowest,
+ * highest, 0) at *records + 4 * pixel (device memory too).  *slots is 64 or 128, *cb the bytes per cost code of the copy (1, 2, 4),
+ * *pass_stride the floats from one pass's volume to the next; each of the four may be NULL.  NULL where mgm_debug_download_lr
+ * refuses its range-proportional form: no such aggregation was the last one, the volume has been refilled since, `pass` out of
+ * range.  What is written there is what mgm_wta_windowed_dev and mgm_debug_wta_rel_again_dev search next. */
+void *mgm_debug_rel_lr_device_ptr(mgm_ctx *ctx, int pass, int *slots, int *cb, long long *pass_stride, void **records);
+
+/* Test aid: the winner search that ended the LAST aggregation of C on this ctx, again -- for an aggregation that ran on C's
+ * range-proportional copy: every pixel's window is its own range, the Lr volumes are read as they lie in the workspace, no pass
+ * kernel runs.  fix_overcount and refine are this call's (any refinement name); S: NULL, or receives the corrected aggregated
+ * volume on the dense hull as mgm_aggregate_dev hands it out there (the caller frees it).  MGM_ERR_INVALID when C was not part
+ * of the context's last aggregation, when that one did not run on the range-proportional copy, or with another NDIR than its
+ * (mgm_wta_windowed_dev's guard).  No synchronisation. */
+int mgm_debug_wta_rel_again_dev(mgm_ctx *ctx, const mgm_cv *C, int NDIR, int fix_overcount, const char *refine, mgm_img *out,
+                                mgm_img *outcost, mgm_cv **S);
+
 /* Test/diagnostic aid: the chunk minima (one float per pixel and chunk of 32 labels: [ny][nx][L/32]) that the pass kernel
  * left beside pass `pass`'s Lr volume of volume `slot` of the LAST aggregation call on this ctx, read where the pruned winner
  * search reads them.  MGM_ERR_INVALID when that launch wrote no minima (any launch the pruned search does not follow), when

@@ -34,6 +34,7 @@ ABI_SYMBOLS = [
     "mgm_debug_wta_stats", "mgm_debug_download_lmin", "mgm_debug_last_pass_kernel",
     "mgm_multiscale_levels", "mgm_zoom_out_dev", "mgm_ranges_zoom_out_dev", "mgm_ranges_from_coarse_dev", "mgm_multiscale_pair_dev",
     "mgm_wta_runnerup_dev", "mgm_uniqueness_dev", "mgm_speckle_dev", "mgm_fill_holes_dev",
+    "mgm_debug_rel_lr_device_ptr", "mgm_debug_wta_rel_again_dev",
 ]
 
 MGM_OK, MGM_ERR_INVALID, MGM_ERR_UNSUPPORTED, MGM_ERR_HIP, MGM_ERR_NOMEM, MGM_ERR_INTERNAL = range(6)
@@ -125,6 +126,9 @@ def load_library():
     L.mgm_aggregate_batch_dev.argtypes = [vp, i, pp, pp, f, f, i, i, i, i, cp, pp, pp, pp]
     L.mgm_debug_download_lr.argtypes = [vp, i, fp]
     L.mgm_debug_download_lmin.argtypes = [vp, i, i, fp]
+    L.mgm_debug_rel_lr_device_ptr.argtypes = [vp, i, C.POINTER(i), C.POINTER(i), C.POINTER(C.c_longlong), pp]
+    L.mgm_debug_rel_lr_device_ptr.restype = vp
+    L.mgm_debug_wta_rel_again_dev.argtypes = [vp, vp, i, i, cp, vp, vp, pp]
     L.mgm_refine_dev.argtypes = [vp, vp, cp, vp, vp]
     L.mgm_refine.argtypes = [vp, vp, cp, fp, fp]
     L.mgm_selftest_div3.argtypes = [vp, C.POINTER(C.c_ulonglong)]
@@ -597,6 +601,33 @@ class Context:
         out = np.empty((ny, nx, (dmax - dmin + 1) // 32), np.float32)
         self._chk(self.lib.mgm_debug_download_lmin(self.h, slot, p, _ptr(out)))
         return out
+
+    def debug_rel_lr(self, p):
+        """Test aid (mgm_debug_rel_lr_device_ptr): (device pointer of pass p's Lr volume [npix][slots] of the last range-proportional
+        run, slots, bytes per cost code, floats between passes, device pointer of the records [npix][4] int32), or None where
+        mgm_debug_download_lr would refuse."""
+        slots, cb, stride, rec = C.c_int(0), C.c_int(0), C.c_longlong(0), C.c_void_p()
+        ptr = self.lib.mgm_debug_rel_lr_device_ptr(self.h, p, C.byref(slots), C.byref(cb), C.byref(stride), C.byref(rec))
+        return (ptr, slots.value, cb.value, stride.value, rec.value) if ptr else None
+
+    def debug_wta_rel_again_dev(self, Cv, NDIR, fix_overcount, refine, out=None, outcost=None, want_S=False):
+        """Test aid (mgm_debug_wta_rel_again_dev): the un-windowed search of the last range-proportional aggregation of Cv again,
+        on the Lr volumes as they lie in the workspace: (S or None, out, outcost) as device handles."""
+        nx, ny, _, _ = Cv.dims
+        mine = []  # the images made here: freed if the call fails
+        for given in (out, outcost):
+            if not given:
+                mine.append(self.new_image(nx, ny))
+        out, outcost = out or mine[0], outcost or mine[-1]
+        S = C.c_void_p()
+        try:
+            self._chk(self.lib.mgm_debug_wta_rel_again_dev(self.h, Cv.h, NDIR, fix_overcount, refine.encode() if refine else None,
+                                                           out.h, outcost.h, C.byref(S) if want_S else None))
+        except Exception:
+            for im in mine:
+                im.free()
+            raise
+        return (CostVolume(self, S) if want_S else None), out, outcost
 
     def refine(self, S, method, out, outcost):
         out = np.array(out, np.float32, copy=True)

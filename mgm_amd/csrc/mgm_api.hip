@@ -429,6 +429,50 @@ int mgm_debug_download_lr(mgm_ctx *c, int pass, float *dense)
     return mgm_ctx_synchronize(c);
 }
 
+// Test aid: where volume 0's Lr volume of pass `pass` of the last range-proportional run lies, [npix][slots] floats, with the format
+// it was written in -- refused exactly where the range-proportional branch of mgm_debug_download_lr refuses.
+void *mgm_debug_rel_lr_device_ptr(mgm_ctx *c, int pass, int *slots, int *cb, long long *pass_stride, void **records)
+{
+    if (pipe_join(c)) return nullptr;
+    if (!c || !(c->rel_last.batch > 0 && c->last.ndir == 0 && c->rel_last.cvs[0] && c->lr_rel.p)) return nullptr;  // no such run
+    if (pass < 0 || pass >= c->rel_last.ndir) return nullptr;
+    const mgm_cv *C = c->rel_last.cvs[0];
+    if (c->rel_last.slot_of(C) != 0 || C->rel_slots != c->rel_last.slots || !C->relbuf) return nullptr;  // refilled since
+    if (slots) *slots = C->rel_slots;
+    if (cb) *cb = C->rel_cb;
+    if (pass_stride) *pass_stride = c->rel_last.stride;
+    if (records) *records = C->rel_records();
+    return const_cast<float *>(c->rel_last.lr(c->lr_rel, 0, pass));
+}
+
+// Test aid: the un-windowed search (and k_rel_S) of run_rel's step 7 again, on the Lr volumes as they lie in the workspace.
+int mgm_debug_wta_rel_again_dev(mgm_ctx *c, const mgm_cv *C, int NDIR, int fix_overcount, const char *refine, mgm_img *out, mgm_img *outcost,
+                                mgm_cv **S)
+{
+    if (int jr = pipe_join(c)) return jr;  // (pipelined context: run what has been deferred first)
+    if (S) *S = nullptr;
+    if (!c || !C || !out || !outcost) return fail(c, MGM_ERR_INVALID, "mgm_debug_wta_rel_again: null argument");
+    for (const mgm_img *im : {(const mgm_img *)out, (const mgm_img *)outcost})
+        if (im->nx != C->nx || im->ny != C->ny || im->nch != 1) return fail(c, MGM_ERR_INVALID, "mgm_debug_wta_rel_again: image size mismatch");
+    const int v = c->rel_last.slot_of(C);
+    if (v < 0 || c->rel_last.ndir != NDIR || c->last.ndir != 0 || !c->lr_rel.p || !C->relbuf)
+        return fail(c, MGM_ERR_INVALID, "mgm_debug_wta_rel_again: this volume was not part of the context's last range-proportional aggregation with NDIR passes");
+    HIPCHK(c, hipSetDevice(c->device));
+    float *Sout = nullptr;
+    if (S) {
+        if (int r = mgm_cv_create(c, C->nx, C->ny, C->dmin, C->dmax, S)) return r;
+        Sout = (*S)->d;
+    }
+    const int r = run_wta_rel(c, C, v, NDIR, fix_overcount, refinement_index(refine), nullptr, nullptr, out->d, outcost->d, Sout);
+    if (r && S) {  // no S volume of a failed call is handed out
+        const std::string msg = c->err;
+        mgm_cv_free(c, *S);
+        *S = nullptr;
+        c->err = msg;
+    }
+    return r;
+}
+
 int mgm_debug_download_lmin(mgm_ctx *c, int slot, int pass, float *out)
 {
     if (int jr = pipe_join(c)) return jr;  // (pipelined context: run what has been deferred first)
