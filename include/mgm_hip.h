@@ -270,6 +270,14 @@ int mgm_debug_download_lr(mgm_ctx *ctx, int pass, float *dense);
  * range.  What is written there is what mgm_wta_windowed_dev and mgm_debug_wta_rel_again_dev search next. */
 void *mgm_debug_rel_lr_device_ptr(mgm_ctx *ctx, int pass, int *slots, int *cb, long long *pass_stride, void **records);
 
+/* Test aid (tests/test_gpu_wta_runnerup_crafted.py): the device pointer of pass `pass`'s Lr volume of volume `volume` of the LAST
+ * aggregation on this ctx, when that one was a dense run: [ny * nx][*Lk] floats, of which the first L of a pixel are its labels and
+ * the slots L..*Lk-1 padding of the launch (*Lk == L: none).  *pass_stride: the floats from one pass's volume to the next; either
+ * may be NULL.  Unlike mgm_lr_device_ptr it serves a padded label stride and every volume of a batch.  NULL when the last
+ * aggregation was no dense run (none yet, trimmed, range-proportional) or `volume` / `pass` lie outside it.  Launches nothing and
+ * changes no record; what is written there is what mgm_wta_windowed_dev, mgm_wta_right_dev and mgm_wta_runnerup_dev search next. */
+void *mgm_debug_lr_device_ptr(mgm_ctx *ctx, int volume, int pass, int *Lk, long long *pass_stride);
+
 /* Test aid: the winner search that ended the LAST aggregation of C on this ctx, again -- for an aggregation that ran on C's
  * range-proportional copy: every pixel's window is its own range, the Lr volumes are read as they lie in the workspace, no pass
  * kernel runs.  fix_overcount and refine are this call's (any refinement name); S: NULL, or receives the corrected aggregated

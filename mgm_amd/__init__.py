@@ -34,7 +34,7 @@ ABI_SYMBOLS = [
     "mgm_debug_wta_stats", "mgm_debug_download_lmin", "mgm_debug_last_pass_kernel",
     "mgm_multiscale_levels", "mgm_zoom_out_dev", "mgm_ranges_zoom_out_dev", "mgm_ranges_from_coarse_dev", "mgm_multiscale_pair_dev",
     "mgm_wta_runnerup_dev", "mgm_uniqueness_dev", "mgm_speckle_dev", "mgm_fill_holes_dev",
-    "mgm_debug_rel_lr_device_ptr", "mgm_debug_wta_rel_again_dev",
+    "mgm_debug_rel_lr_device_ptr", "mgm_debug_wta_rel_again_dev", "mgm_debug_lr_device_ptr",
 ]
 
 MGM_OK, MGM_ERR_INVALID, MGM_ERR_UNSUPPORTED, MGM_ERR_HIP, MGM_ERR_NOMEM, MGM_ERR_INTERNAL = range(6)
@@ -128,6 +128,8 @@ def load_library():
     L.mgm_debug_download_lmin.argtypes = [vp, i, i, fp]
     L.mgm_debug_rel_lr_device_ptr.argtypes = [vp, i, C.POINTER(i), C.POINTER(i), C.POINTER(C.c_longlong), pp]
     L.mgm_debug_rel_lr_device_ptr.restype = vp
+    L.mgm_debug_lr_device_ptr.argtypes = [vp, i, i, C.POINTER(i), C.POINTER(C.c_longlong)]
+    L.mgm_debug_lr_device_ptr.restype = vp
     L.mgm_debug_wta_rel_again_dev.argtypes = [vp, vp, i, i, cp, vp, vp, pp]
     L.mgm_refine_dev.argtypes = [vp, vp, cp, vp, vp]
     L.mgm_refine.argtypes = [vp, vp, cp, fp, fp]
@@ -609,6 +611,14 @@ class Context:
         slots, cb, stride, rec = C.c_int(0), C.c_int(0), C.c_longlong(0), C.c_void_p()
         ptr = self.lib.mgm_debug_rel_lr_device_ptr(self.h, p, C.byref(slots), C.byref(cb), C.byref(stride), C.byref(rec))
         return (ptr, slots.value, cb.value, stride.value, rec.value) if ptr else None
+
+    def debug_lr_ptr(self, volume, p):
+        """Test aid (mgm_debug_lr_device_ptr): (device pointer of pass p's Lr volume [npix][Lk] of volume `volume` of the last dense
+        run, the label stride Lk, floats between passes), or None where the last aggregation was no dense run or has no such
+        volume or pass."""
+        Lk, stride = C.c_int(0), C.c_longlong(0)
+        ptr = self.lib.mgm_debug_lr_device_ptr(self.h, volume, p, C.byref(Lk), C.byref(stride))
+        return (ptr, Lk.value, stride.value) if ptr else None
 
     def debug_wta_rel_again_dev(self, Cv, NDIR, fix_overcount, refine, out=None, outcost=None, want_S=False):
         """Test aid (mgm_debug_wta_rel_again_dev): the un-windowed search of the last range-proportional aggregation of Cv again,

@@ -445,6 +445,18 @@ void *mgm_debug_rel_lr_device_ptr(mgm_ctx *c, int pass, int *slots, int *cb, lon
     return const_cast<float *>(c->rel_last.lr(c->lr_rel, 0, pass));
 }
 
+// Test aid: where pass `pass` of volume `volume` of the last DENSE run lies, [npix][*Lk] floats of which the first L of a pixel are
+// labels -- whatever the label stride (mgm_lr_device_ptr refuses a padded one and serves volume 0 only).  Launches nothing.
+void *mgm_debug_lr_device_ptr(mgm_ctx *c, int volume, int pass, int *Lk, long long *pass_stride)
+{
+    if (pipe_join(c)) return nullptr;
+    if (!c || !c->lr.p || c->last.ndir < 1 || c->last.batch < 1) return nullptr;  // no such run
+    if (volume < 0 || volume >= c->last.batch || pass < 0 || pass >= c->last.ndir) return nullptr;
+    if (Lk) *Lk = c->last.Lk;
+    if (pass_stride) *pass_stride = c->last.stride;
+    return const_cast<float *>(c->last.lr(c->lr, volume, pass));
+}
+
 // Test aid: the un-windowed search (and k_rel_S) of run_rel's step 7 again, on the Lr volumes as they lie in the workspace.
 int mgm_debug_wta_rel_again_dev(mgm_ctx *c, const mgm_cv *C, int NDIR, int fix_overcount, const char *refine, mgm_img *out, mgm_img *outcost,
                                 mgm_cv **S)

@@ -28,6 +28,18 @@ def test_library_exports_every_declared_symbol():
     assert b"gfx950" in mgm_amd.load_library().mgm_version()
 
 
+def test_the_lr_pointer_aids_refuse_without_a_context():
+    """mgm_lr_device_ptr and the test aid mgm_debug_lr_device_ptr: NULL, and nothing written (the refusals that need a
+    context -- no dense run, a volume or a pass outside it -- are tests/test_gpu_wta_runnerup_crafted.py's)"""
+    lib = mgm_amd.load_library()
+    Lk, stride = ctypes.c_int(-7), ctypes.c_longlong(-9)
+    for volume, p in ((0, 0), (-1, 0), (0, -1), (1, 8)):
+        assert not lib.mgm_debug_lr_device_ptr(None, volume, p, ctypes.byref(Lk), ctypes.byref(stride))
+        assert not lib.mgm_debug_lr_device_ptr(None, volume, p, None, None)
+    assert (Lk.value, stride.value) == (-7, -9)
+    assert not lib.mgm_lr_device_ptr(None, 0)
+
+
 def test_no_cpu_fallback():
     try:
         ctx = mgm_amd.Context(0)

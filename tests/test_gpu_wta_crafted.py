@@ -374,6 +374,48 @@ def test_windowed_and_right_search_on_overwritten_volumes(own, oracle, L, NDIR):
             h.free()
 
 
+@pytest.mark.parametrize("NDIR", [8, 4])
+@pytest.mark.parametrize("L,nx,ny", [(128, 23, 7), (384, 23, 7), (768, 23, 7), (1024, 23, 7), (64, 150, 2), (128, 140, 2)])
+def test_right_search_on_the_other_instances_and_on_split_rows(own, planlib, L, nx, ny, NDIR):
+    """B: k_wta_right at 2, 6, 12 and 16 labels per lane (the test above runs 1, 3, 4 and 8), and rows wider than the
+    max(64, L) right pixels of a segment (plan_wta_right): crafted values cross a segment boundary and wrap the LDS ring"""
+    dmin, split = -(L // 2), nx > 23
+    Cv = synth.raw_volume(nx, ny, L, seed=9, inf_frac=0.02)
+    cv = own.upload_volume(Cv, dmin)
+    vnxs = (nx, nx - 9, nx + 9)
+    for vnx in vnxs:
+        ch = dict(zip(PM.RIGHT_OUT, TP.ask(planlib, "right", [TP.right_request(L=L, nx=nx, ny=ny, vnx=vnx, dmin=dmin)])[0]))
+        assert (ch["family"], ch["LPL"]) == (PM.RIGHT_STREAM, L // 64), ch
+        segments = -(-vnx // ch["seg"])
+        assert (segments > 1) == split, (vnx, ch)
+    own.timing_reset()
+    try:
+        for k, name in enumerate(("ties", "edges", "nonfinite", "nolabel")):
+            own.timing(k == 0)
+            _, o, c = own.aggregate_dev(cv, 8.0, 32.0, NDIR, 3, 0, 1, None, None)
+            own.synchronize()
+            o.free(), c.free()
+            lr = W.LR_CLASSES[name](600 + k, NDIR, ny, nx, L)
+            overwrite(own, lr)
+            for fix in (0, 1):
+                S = W.sum_fix(lr, Cv, NDIR, fix)
+                for vnx in vnxs:
+                    for refine in (None, "vfit"):
+                        want_o, want_c = wta_right(S, dmin, vnx, refine)
+                        for walk in ("0", "1"):
+                            os.environ["MGM_HIP_WTA_RIGHT_ANY"] = walk
+                            o, c = own.wta_right_dev(cv, NDIR, fix, refine, vnx)
+                            got_o, got_c = o.download()[0], c.download()[0]
+                            o.free(), c.free()
+                            assert ndiff(got_c, want_c) == 0 and ndiff(got_o, want_o) == 0, ("right", name, L, nx, NDIR, fix, refine, vnx, walk)
+        assert "k_wta_right" in {n for n, _ in own.timings()}
+    finally:
+        own.timing(False)
+        os.environ.pop("MGM_HIP_WTA_RIGHT_ANY", None)
+        own.trim()  # nothing later reads the overwritten volumes
+        cv.free()
+
+
 # ---- C: the stand-alone refinement ---------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name", CLASSES)
 def test_refine_alone_on_labels_the_test_chooses(own, oracle, name):
