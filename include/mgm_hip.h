@@ -394,13 +394,42 @@ int mgm_speckle_dev(mgm_ctx *ctx, const mgm_img *d, int maxsize, float maxdiff, 
  *                min = v[0], max = v[n-1], median = v[n/2] (the upper median).  No float arithmetic: always one of d's values
  *   out(p)       = d(p) bit for bit on valid pixels and on holes without a candidate (NaN payloads and +-INF stay), else the fill value
  *   filled(p)    = 1.0f where a hole received a value, 0.0f elsewhere
- * One channel; classifying holes into occlusions and mismatches (which needs the other view) is out of scope.  out and filled may
+ * One channel; one rule for every hole (occlusions and mismatches apart: mgm_classify_holes_dev and the classified fill below).  out and filled may
  * each be NULL, not both; out may be d, filled must be an image of its own; all images are one-channel and of one size; a mode
  * that is NULL or none of the three names, dirs outside {2, 4, 8}, maxdist < 0: MGM_ERR_INVALID.  More than 2^31 - 1 pixels:
  * MGM_ERR_UNSUPPORTED.  The result depends on no traversal order; the step is NOT idempotent (a second application may fill what the
  * first could not reach).  Scratch: dirs float planes of the map's size and the bands' carries, kept by the context (mgm_ctx_trim
  * releases them).  No synchronisation; the timing table lists the call as k_holes. */
 int mgm_fill_holes_dev(mgm_ctx *ctx, const mgm_img *d, const char *mode, int dirs, int maxdist, mgm_img *out, mgm_img *filled);
+/* Hole classification (DESIGN.md "hole classification"; this library's own step, the reference has none; after Hirschmueller 2008,
+ * section 2.6): every hole of d is an occlusion or a mismatch, decided from the other view.  d is the nx x ny x 1 map with holes,
+ * other the OTHER view's vnx x ny x 1 map as it went INTO the left-right test (not the checked one: a checked map can never
+ * point back at a pixel that test rejected), dmin <= dmax the disparity range, tau finite and >= 0, cls an nx x ny x 1 image.
+ *   cls(x,y) = 0.0f  where d(x,y) is finite
+ *   cls(x,y) = 2.0f  (mismatch) at a hole iff an integer xr exists with max(0, x+dmin) <= xr <= min(vnx-1, x+dmax), other(xr,y)
+ *                    finite and fabsf(((float)xr + other(xr,y)) - (float)x) <= tau: some pixel of the other view lands on it.  In
+ *                    float, in that order, no contraction, one comparison; a landing coordinate that overflows to +-INF never matches
+ *   cls(x,y) = 1.0f  (occlusion) at every other hole, those whose whole range falls outside `other` included
+ * The convention is mgm_leftright_dev's: left x with disparity d names right x + d.  A NULL argument, an image that is not
+ * one-channel, other->ny != d->ny, cls not of d's size or cls == d or cls == other, dmin > dmax, tau negative or not finite:
+ * MGM_ERR_INVALID.  More than 2^31 - 1 pixels: MGM_ERR_UNSUPPORTED.  Any range length: the work per hole grows with it, the memory
+ * does not.  No scratch.  No synchronisation; the timing table lists the call as k_holes_classify. */
+int mgm_classify_holes_dev(mgm_ctx *ctx, const mgm_img *d, const mgm_img *other, int dmin, int dmax, float tau, mgm_img *cls);
+/* The classified fill: mgm_fill_holes_dev with one rule for the occlusions and one for the mismatches.  Candidates, directions, dirs,
+ * maxdist, the ordering by (value, direction index), out on valid pixels and on holes without a candidate, and filled are exactly
+ * mgm_fill_holes_dev's.  Mode names: "median", "min", "max" and
+ *   seclow  = v[min(1, n-1)]    the second lowest candidate (the lowest when there is one)
+ *   sechigh = v[max(n-2, 0)]    the second highest
+ * A hole with cls(p) == 1.0f takes mode_occ, every other hole mode_mis, whatever else cls holds there (NaN included); cls is read at
+ * holes only.  An occlusion wants the BACKGROUND's second candidate: which of the two that is depends on the sign of the caller's
+ * disparities -- with a range like -r -64 -R 0 the background is the higher value, sechigh.  No float arithmetic: always one of d's
+ * values.  out and filled may each be NULL, not both; out may be d; filled must be an image of its own (not d, cls or out); all
+ * images one-channel and of d's size; a NULL argument, a mode name outside the five, dirs outside {2, 4, 8}, maxdist < 0:
+ * MGM_ERR_INVALID.  More than 2^31 - 1 pixels: MGM_ERR_UNSUPPORTED.  mode_occ == mode_mis (one of the three old names) is
+ * mgm_fill_holes_dev bit for bit.  Scratch: mgm_fill_holes_dev's, shared with it.  No synchronisation; the timing table lists the
+ * call as k_holes.  The class map is the caller's image: the command line has no file option for it. */
+int mgm_fill_holes_classified_dev(mgm_ctx *ctx, const mgm_img *d, const mgm_img *cls, const char *mode_occ, const char *mode_mis,
+                                  int dirs, int maxdist, mgm_img *out, mgm_img *filled);
 /* update_dmin_dmax (mgm.cc:120-158; main() uses slack 3, radius 2) followed by the two
  * remove_nonfinite_values_Img calls (mgm.cc:387-388): dminI/dmaxI are updated in place from the disparity map. */
 int mgm_update_ranges_dev(mgm_ctx *ctx, const mgm_img *outoff, mgm_img *dminI, mgm_img *dmaxI, int slack, int radius);
@@ -474,6 +503,8 @@ typedef struct mgm_ms_params {
     float tau;            /* TESTLRRL_TAU */
     int *levels_run;      /* optional out: the effective level count */
     mgm_ms_level *levels; /* optional out: `nscales` entries, [s] filled for every level that ran */
+    mgm_img *outR_nolr;   /* optional out (NULL or absent: nothing happens): vnx*vny, the finest level's right map after MEDIAN and
+                             before its left-right test -- what mgm_classify_holes_dev wants as `other`; untouched with testlrrl = 0 */
 } mgm_ms_params;
 
 /* One stereo pair, coarse to fine.  Per level exactly what the `mgm` command line does for a pair (weights, ranged cost

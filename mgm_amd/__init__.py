@@ -34,6 +34,7 @@ ABI_SYMBOLS = [
     "mgm_debug_wta_stats", "mgm_debug_download_lmin", "mgm_debug_last_pass_kernel",
     "mgm_multiscale_levels", "mgm_zoom_out_dev", "mgm_ranges_zoom_out_dev", "mgm_ranges_from_coarse_dev", "mgm_multiscale_pair_dev",
     "mgm_wta_runnerup_dev", "mgm_uniqueness_dev", "mgm_speckle_dev", "mgm_fill_holes_dev",
+    "mgm_classify_holes_dev", "mgm_fill_holes_classified_dev",
     "mgm_debug_rel_lr_device_ptr", "mgm_debug_wta_rel_again_dev", "mgm_debug_lr_device_ptr",
 ]
 
@@ -62,7 +63,8 @@ class MsParams(C.Structure):
                 ("NDIR", C.c_int), ("TSGM", C.c_int), ("use_fh", C.c_int), ("fix_overcount", C.c_int), ("aP2", C.c_float),
                 ("aThresh", C.c_float), ("prefilter", C.c_char_p), ("distance", C.c_char_p), ("truncDist", C.c_float),
                 ("census_win", C.c_int), ("refine", C.c_char_p), ("iterations", C.c_int), ("median", C.c_int),
-                ("testlrrl", C.c_int), ("tau", C.c_float), ("levels_run", C.POINTER(C.c_int)), ("levels", C.POINTER(MsLevel))]
+                ("testlrrl", C.c_int), ("tau", C.c_float), ("levels_run", C.POINTER(C.c_int)), ("levels", C.POINTER(MsLevel)),
+                ("outR_nolr", C.c_void_p)]
 
 
 def load_library():
@@ -120,6 +122,8 @@ def load_library():
     L.mgm_uniqueness_dev.argtypes = [vp, vp, vp, vp, f, vp, vp]
     L.mgm_speckle_dev.argtypes = [vp, vp, i, f, vp, vp]
     L.mgm_fill_holes_dev.argtypes = [vp, vp, cp, i, i, vp, vp]
+    L.mgm_classify_holes_dev.argtypes = [vp, vp, vp, i, i, f, vp]
+    L.mgm_fill_holes_classified_dev.argtypes = [vp, vp, vp, cp, cp, i, i, vp, vp]
     L.mgm_update_ranges_dev.argtypes = [vp, vp, vp, vp, i, i]
     L.mgm_leftright_dev.argtypes = [vp, vp, vp, f, vp]
     L.mgm_backproject_dev.argtypes = [vp, vp, vp, vp, vp]
@@ -456,6 +460,48 @@ class Context:
             raise
         return (out if out else None), filled
 
+    def classify_holes_dev(self, d, other, dmin, dmax, tau, cls=None):
+        """Hole classification (mgm_classify_holes_dev): the device image cls -- 0 where d is finite, 2 (a mismatch) at a hole (x, y)
+        that some column xr of [x + dmin, x + dmax] inside `other` lands on, |xr + other(xr, y) - x| <= tau in float, 1 (an occlusion)
+        at every other hole.  other: the other view's map as it went INTO the left-right test, of d's height.  cls: an image of d's
+        size to write, None for a new one."""
+        _, ny, nx = d.shape
+        mine = []  # the images made here: freed if the call fails
+        try:
+            if cls is None:
+                cls = self.new_image(nx, ny)
+                mine.append(cls)
+            self._chk(self.lib.mgm_classify_holes_dev(self.h, d.h, other.h, dmin, dmax, tau, cls.h))
+        except Exception:
+            for im in mine:
+                im.free()
+            raise
+        return cls
+
+    def fill_holes_classified_dev(self, d, cls, mode_occ="sechigh", mode_mis="median", dirs=8, maxdist=0, out=None, want_filled=False):
+        """The classified fill (mgm_fill_holes_classified_dev): fill_holes_dev with two rules -- a hole with cls == 1 (an occlusion)
+        takes mode_occ, every other hole mode_mis; the modes are median, min, max, seclow (the second lowest candidate) and sechigh
+        (the second highest).  The background is sechigh where disparities are negative (a range like -64 .. 0) and seclow where
+        they are positive.  Device images (out, filled), as fill_holes_dev returns them."""
+        _, ny, nx = d.shape
+        mine = []  # the images made here: freed if the call fails
+        try:
+            if out is None:
+                out = self.new_image(nx, ny)
+                mine.append(out)
+            filled = None
+            if want_filled:
+                filled = self.new_image(nx, ny)
+                mine.append(filled)
+            enc = lambda m: None if m is None else str(m).encode()
+            self._chk(self.lib.mgm_fill_holes_classified_dev(self.h, d.h, cls.h if cls is not None else None, enc(mode_occ), enc(mode_mis), dirs,
+                                                             maxdist, out.h if out else None, filled.h if want_filled else None))
+        except Exception:
+            for im in mine:
+                im.free()
+            raise
+        return (out if out else None), filled
+
     def pair_right_from_left(self, u, v, dmin, dmax, P1=8.0, P2=32.0, NDIR=4, TSGM=4, use_fh=0, fix_overcount=1, aP2=1.0, aThresh=5.0,
                              prefilter="none", distance="ad", truncDist=float("inf"), census_win=3, refine="none", tau=1.0, median=0):
         """A stereo pair with ONE run: the left->right cost volume and aggregation, the right map read out of that run
@@ -517,15 +563,19 @@ class Context:
 
     def multiscale_pair(self, u, v, dmin, dmax, nscales, P1=8.0, P2=32.0, NDIR=4, TSGM=4, use_fh=0, fix_overcount=1, aP2=1.0,
                         aThresh=5.0, prefilter="none", distance="ad", truncDist=float("inf"), census_win=3, refine="none",
-                        iterations=1, median=0, testlrrl=1, tau=1.0, slack=3, radius=2, lo=None, hi=None, want_nolr=True):
+                        iterations=1, median=0, testlrrl=1, tau=1.0, slack=3, radius=2, lo=None, hi=None, want_nolr=True,
+                        want_right_nolr=False):
         """mgm_multiscale_pair_dev on device images u, v (P1 / P2 as given: multiply by the channel count yourself).
-        Returns a dict of device images outL, costL, outR, costR (None with testlrrl=0), nolr (None unless wanted) and
+        Returns a dict of device images outL, costL, outR, costR (None with testlrrl=0), nolr (None unless wanted), outR_nolr
+        (with want_right_nolr and testlrrl: the full-size right map before its left-right test, else None) and
         `levels`: one dict per level that ran, [0] = full size."""
         _, ny, nx = u.shape
         _, vny, vnx = v.shape
-        res = dict(outL=self.new_image(nx, ny), costL=self.new_image(nx, ny), outR=None, costR=None, nolr=None)
+        res = dict(outL=self.new_image(nx, ny), costL=self.new_image(nx, ny), outR=None, costR=None, nolr=None, outR_nolr=None)
         if testlrrl:
             res["outR"], res["costR"] = self.new_image(vnx, vny), self.new_image(vnx, vny)
+            if want_right_nolr:
+                res["outR_nolr"] = self.new_image(vnx, vny)
         if want_nolr:
             res["nolr"] = self.new_image(nx, ny)
         n = C.c_int(0)
@@ -533,7 +583,7 @@ class Context:
         p = MsParams(C.sizeof(MsParams), nscales, slack, radius, dmin, dmax, lo.h if lo is not None else None,
                      hi.h if hi is not None else None, P1, P2, NDIR, TSGM, use_fh, fix_overcount, aP2, aThresh, prefilter.encode(),
                      distance.encode(), truncDist, census_win, (refine or "none").encode(), iterations, median, testlrrl, tau,
-                     C.pointer(n), lv)
+                     C.pointer(n), lv, res["outR_nolr"].h if res["outR_nolr"] is not None else None)
         hnd = lambda im: im.h if im is not None else None
         r = self.lib.mgm_multiscale_pair_dev(self.h, u.h, v.h, C.byref(p), hnd(res["outL"]), hnd(res["costL"]), hnd(res["outR"]),
                                              hnd(res["costR"]), hnd(res["nolr"]))

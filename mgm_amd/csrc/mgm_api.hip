@@ -766,6 +766,72 @@ int mgm_fill_holes_dev(mgm_ctx *c, const mgm_img *d, const char *mode, int dirs,
     return MGM_OK;
 }
 
+// Hole classification (k_holes_classify in mgm_holes.hip): plan_holes_classify decides the grid, the span and the LDS
+// bytes; one launch, no scratch.
+int mgm_classify_holes_dev(mgm_ctx *c, const mgm_img *d, const mgm_img *other, int dmin, int dmax, float tau, mgm_img *cls)
+{
+    if (int jr = pipe_join(c)) return jr;  // (pipelined context: run what has been deferred first)
+    if (!c || !d || !other || !cls) return fail(c, MGM_ERR_INVALID, "mgm_classify_holes: null argument");
+    if (d->nch != 1 || other->nch != 1 || cls->nch != 1) return fail(c, MGM_ERR_INVALID, "mgm_classify_holes: every image has one channel");
+    if (other->ny != d->ny) return fail(c, MGM_ERR_INVALID, "mgm_classify_holes: the other view's map must have d's height");
+    if (cls->nx != d->nx || cls->ny != d->ny) return fail(c, MGM_ERR_INVALID, "mgm_classify_holes: cls must have d's size");
+    if (cls == d || cls == other) return fail(c, MGM_ERR_INVALID, "mgm_classify_holes: cls must be an image of its own");
+    if (dmin > dmax) return fail(c, MGM_ERR_INVALID, "mgm_classify_holes: dmin must be <= dmax");
+    if (!(tau >= 0.0f && tau < __builtin_inff())) return fail(c, MGM_ERR_INVALID, "mgm_classify_holes: tau must be finite and >= 0");
+    const HolesClassifyChoice choice = plan_holes_classify(HolesClassifyRequest{d->nx, d->ny, other->nx, c->num_cu, (long long)dmax - dmin + 1});
+    if (choice.family == kHolesRefuse) return fail(c, MGM_ERR_UNSUPPORTED, "mgm_classify_holes: more than 2^31 - 1 pixels (pixel coordinates are int32)");
+    HIPCHK(c, hipSetDevice(c->device));
+    HolesClassifyParams p{};
+    p.d = d->d, p.other = other->d, p.cls = cls->d;
+    p.nx = d->nx, p.ny = d->ny, p.vnx = other->nx, p.dmin = dmin, p.dmax = dmax, p.tau = tau;
+    TimeScope t(c, "k_holes_classify");
+    if (hipError_t e = launch_holes_classify(p, choice, c->stream)) return hipfail(c, e, "k_holes_classify");
+    return MGM_OK;
+}
+
+// The classified fill: mgm_fill_holes_dev's phases on the same scratch with the classified instance of the apply phase.
+static int holes_mode5(const char *m)
+{
+    static const char *const names[5] = {"median", "min", "max", "seclow", "sechigh"};
+    for (int k = 0; m && k < 5; k++)
+        if (!strcmp(m, names[k])) return k;
+    return -1;
+}
+int mgm_fill_holes_classified_dev(mgm_ctx *c, const mgm_img *d, const mgm_img *cls, const char *mode_occ, const char *mode_mis, int dirs, int maxdist,
+                                  mgm_img *out, mgm_img *filled)
+{
+    if (int jr = pipe_join(c)) return jr;  // (pipelined context: run what has been deferred first)
+    if (!c || !d || !cls || (!out && !filled)) return fail(c, MGM_ERR_INVALID, "mgm_fill_holes_classified: null argument (at least one of out, filled)");
+    const int mo = holes_mode5(mode_occ), mm = holes_mode5(mode_mis);
+    if (mo < 0 || mm < 0) return fail(c, MGM_ERR_INVALID, "mgm_fill_holes_classified: a mode must be median, min, max, seclow or sechigh");
+    if (dirs != 2 && dirs != 4 && dirs != 8) return fail(c, MGM_ERR_INVALID, "mgm_fill_holes_classified: dirs must be 2, 4 or 8");
+    if (maxdist < 0) return fail(c, MGM_ERR_INVALID, "mgm_fill_holes_classified: maxdist must be >= 0 (0: no limit)");
+    for (const mgm_img *im : {d, cls, (const mgm_img *)out, (const mgm_img *)filled})
+        if (im && (im->nx != d->nx || im->ny != d->ny || im->nch != 1))
+            return fail(c, MGM_ERR_INVALID, "mgm_fill_holes_classified: image size mismatch (one channel, one size)");
+    if (filled && (filled == d || filled == cls || filled == out)) return fail(c, MGM_ERR_INVALID, "mgm_fill_holes_classified: filled must be an image of its own");
+    const HolesChoice choice = plan_holes(HolesRequest{d->nx, d->ny, dirs, c->num_cu});
+    if (choice.family == kHolesRefuse) return fail(c, MGM_ERR_UNSUPPORTED, "mgm_fill_holes_classified: more than 2^31 - 1 pixels (pixel coordinates are int32)");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (int r = reserve(c, c->holes, (size_t)choice.scratch_bytes)) return r;
+    HolesParams p{};
+    p.d = d->d;
+    p.cls = cls->d;
+    p.out = out ? out->d : nullptr;
+    p.filled = filled ? filled->d : nullptr;
+    p.planes = (float *)c->holes.p;
+    p.cpos = (int *)(p.planes + (size_t)choice.planes * d->nx * d->ny);
+    p.cval = (float *)(p.cpos + choice.carry_words);
+    p.nx = d->nx, p.ny = d->ny, p.dirs = dirs, p.maxdist = maxdist, p.mode = mm, p.mode_occ = mo;
+    TimeScope t(c, "k_holes");
+    for (int phase = 0; phase < kHolesPhases; phase++) {
+        if (!holes_phase_runs(phase, dirs)) continue;
+        TimeScope tp(c, holes_phase_name(phase));
+        if (hipError_t e = launch_holes_phase(phase, p, choice, c->stream)) return hipfail(c, e, holes_phase_name(phase));
+    }
+    return MGM_OK;
+}
+
 int mgm_leftright_dev(mgm_ctx *c, const mgm_img *d, const mgm_img *other, float tau, mgm_img *out)
 {
     if (int jr = pipe_join(c)) return jr;  // (pipelined context: run what has been deferred first)

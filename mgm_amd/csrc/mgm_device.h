@@ -149,7 +149,10 @@ struct HolesParams {
     int *cpos;            // scratch: the bands' carry-outs of directions 2.., [direction - 2][band][line]: the row of the band's last
     float *cval;          //          finite pixel in walking order on that line (-1: none) and its value
     int nx, ny, dirs, maxdist;
-    int mode;             // 0 median (upper), 1 min, 2 max
+    int mode;             // 0 median (upper), 1 min, 2 max; with cls also 3 seclow, 4 sechigh
+    // the classified fill: nullptr, or [nx*ny] classes -- a hole with cls == 1 takes mode_occ, every other hole `mode`
+    const float *cls;
+    int mode_occ;
 };
 struct HolesChoice;  // (mgm_planner.h: what plan_holes decided)
 enum HolesPhase { kHolesRows = 0, kHolesCarry, kHolesWalk, kHolesApply, kHolesPhases };
@@ -157,6 +160,17 @@ const char *holes_phase_name(int phase);  // "k_holes_rows", ...
 // dirs = 2 has no columns and no diagonals: its carry and walk phases launch nothing (the caller skips them: holes_phase_runs)
 inline bool holes_phase_runs(int phase, int dirs) { return dirs > 2 || (phase != kHolesCarry && phase != kHolesWalk); }
 hipError_t launch_holes_phase(int phase, const HolesParams &p, const HolesChoice &c, hipStream_t s);
+// hole classification (k_holes_classify, mgm_holes.hip): cls = 0 on finite pixels, 2 on the holes that a pixel of the
+// other view's row points back at within tau (a mismatch), 1 on the other holes (an occlusion)
+struct HolesClassifyParams {
+    const float *d;      // [nx*ny] the map with holes
+    const float *other;  // [vnx*ny] the other view's map as it went into the left-right test
+    float *cls;          // [nx*ny]
+    int nx, ny, vnx, dmin, dmax;
+    float tau;
+};
+struct HolesClassifyChoice;  // (mgm_planner.h: what plan_holes_classify decided)
+hipError_t launch_holes_classify(const HolesClassifyParams &p, const HolesClassifyChoice &c, hipStream_t s);
 
 // ---- ragged volumes in the range-proportional layout (mgm_pass_rel.hip, k_wta_rel): 64 label slots per pixel placed at the
 // pixel's own window, slot k <-> disparity base + k

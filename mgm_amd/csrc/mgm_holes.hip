@@ -28,6 +28,9 @@
 //
 // Candidate planes are written at holes only (every hole, every direction: NaN where there is none) and read at holes only.
 // No loop here waits for a value that another wave must produce: no flag, no atomic, no barrier across workgroups.
+//
+// Hole classification lives here too: k_holes_classify tells occlusions from mismatches with the other view's map,
+// and the classified instances of k_holes_apply fill each class by its own rule; both are described where they stand.
 #include "mgm_device.h"
 #include "mgm_planner.h"
 
@@ -170,9 +173,12 @@ __device__ __forceinline__ void holes_cx(float &a, int &ia, float &b, int &ib)
 }
 
 // d[p] is read before out[p] is written and the candidates are finished: out may be d (no __restrict__ on either).
-template <int DIRS>
+// CLS, the classified instance: a hole with cls(p) == 1.0f (an occlusion) takes mode_occ, every other hole `mode`,
+// whatever else cls holds there; the modes 3 seclow v[min(1, n-1)] and 4 sechigh v[max(n-2, 0)] exist for it.  cls is read at holes
+// only, and like d before out[p] is written.  Without CLS neither cls nor mode_occ is looked at.
+template <int DIRS, bool CLS>
 __global__ void __launch_bounds__(kHolesThreads) k_holes_apply(const float *d, long long npix, const float *__restrict__ planes, int mode,
-                                                              float *out, float *__restrict__ filled)
+                                                              float *out, float *__restrict__ filled, const float *cls, int mode_occ)
 {
     static_assert(DIRS == 2 || DIRS == 4 || DIRS == 8, "the compare-exchange networks below");
     const long long p = (long long)blockIdx.x * kHolesThreads + threadIdx.x;
@@ -201,13 +207,95 @@ __global__ void __launch_bounds__(kHolesThreads) k_holes_apply(const float *d, l
             CX(1, 2), CX(3, 4), CX(5, 6);
         }
 #undef CX
-        const int pick = mode == 1 ? 0 : (mode == 2 ? n - 1 : n / 2);
+        int pick = mode == 1 ? 0 : (mode == 2 ? n - 1 : n / 2);
+        if (CLS) {
+            const int m = cls[p] == 1.0f ? mode_occ : mode;
+            pick = m == 1 ? 0 : (m == 2 ? n - 1 : (m == 3 ? min(1, n - 1) : (m == 4 ? max(n - 2, 0) : n / 2)));
+        }
 #pragma unroll
         for (int k = 0; k < DIRS; k++)
             if (k == pick && n > 0) r = c[k];
     }
     if (out) out[p] = r;
     if (filled) filled[p] = n > 0 ? 1.0f : 0.0f;
+}
+
+// Hole classification: cls = 0 on finite pixels; a hole at (x, y) is a mismatch (2) iff a column xr of the other view
+// with max(0, x + dmin) <= xr <= min(vnx - 1, x + dmax) has other(xr, y) finite and fabsf(((float)xr + other(xr, y)) - (float)x) <= tau
+// -- some pixel of the other view points back at it -- else an occlusion (1).  In float, in that order (this file is built without
+// contraction); a landing coordinate (float)xr + other that overflows to +-INF, like a NaN, matches nothing.
+//
+// One workgroup per row segment of `seg` = kHolesThreads pixels, one pixel per thread; blockIdx.y strides over the rows.
+//   1. every thread reads its pixel; the segment's holes are compacted into an LDS list with one ballot per wave and the waves'
+//      counts (a segment without holes writes its zeros and is done)
+//   2. the columns the segment's holes can name, [x0 + dmin, x1 + dmax] cut to the other view, are staged in LDS as landing
+//      coordinates, `span` at a time (NaN where other is not finite): both maps are read once per segment, whatever L is
+//   3. wave w takes the holes w, w + waves, ... one at a time: 64 columns per step, one LDS read and one ballot per step, and it leaves
+//      the hole at the first step with a match; a matched hole is marked in the list (its entry turns negative) and skipped in later spans
+//   4. every thread looks its hole up in the list by the rank it got in 1. and writes its class
+// No atomics, nothing waits on another workgroup; the barriers are the workgroup's own, reached by all its threads (every loop bound
+// below is uniform across the workgroup).
+__global__ void __launch_bounds__(kHolesThreads) k_holes_classify(const float *__restrict__ d, int nx, int ny, const float *__restrict__ other, int vnx,
+                                                                 int dmin, int dmax, float tau, int span, float *__restrict__ cls)
+{
+    extern __shared__ float holes_cls_lds[];
+    constexpr int W = kHolesThreads / kWave;
+    static_assert(W <= kHolesClsWords, "one count per wave");
+    float *land = holes_cls_lds;                   // [span]
+    int *list = (int *)(holes_cls_lds + span);     // [kHolesThreads] the holes' x - x0; -1 - (x - x0) once matched
+    int *count = list + kHolesThreads;             // [W] holes per wave
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long long x0 = (long long)blockIdx.x * kHolesThreads, x = x0 + threadIdx.x;
+    const long long x1 = min(x0 + kHolesThreads, (long long)nx) - 1;  // the segment's last pixel
+    // the columns of the other view that the segment's holes can name (empty when lo_all > hi_all: every hole is an occlusion)
+    const long long lo_all = max(0ll, x0 + dmin), hi_all = min((long long)vnx - 1, x1 + dmax);
+    for (long long y = blockIdx.y; y < ny; y += gridDim.y) {
+        const bool in = x < nx;
+        const float v = d[in ? y * nx + x : 0];
+        const bool hole = in && !finite_bits(v);
+        const unsigned long long mask = __ballot(hole);
+        if (lane == 0) count[wave] = __popcll(mask);
+        __syncthreads();
+        int before = 0, nholes = 0;
+#pragma unroll
+        for (int w = 0; w < W; w++) {
+            const int cw = count[w];
+            before += w < wave ? cw : 0;
+            nholes += cw;
+        }
+        const int rank = before + __popcll(mask & ((1ull << lane) - 1));
+        if (hole) list[rank] = threadIdx.x;
+        __syncthreads();  // (the list is complete, and everyone has read count[])
+        if (nholes > 0) {
+            for (long long s0 = lo_all; s0 <= hi_all; s0 += span) {
+                const long long s1 = min(s0 + span - 1, hi_all);  // the span's columns [s0, s1], all inside the other view
+                for (long long xr = s0 + threadIdx.x; xr <= s1; xr += kHolesThreads) {
+                    const float o = other[y * vnx + xr];
+                    land[xr - s0] = finite_bits(o) ? (float)xr + o : holes_none();
+                }
+                __syncthreads();
+                for (int h = wave; h < nholes; h += W) {
+                    const int e = list[h];  // wave-uniform
+                    if (e < 0) continue;
+                    const long long hx = x0 + e;
+                    const float fx = (float)hx;
+                    const long long lo = max(hx + dmin, s0), hi = min(hx + dmax, s1);
+                    bool matched = false;
+                    for (long long j0 = lo; j0 <= hi && !matched; j0 += kWave) {
+                        const long long j = j0 + lane;
+                        const float a = land[j <= hi ? j - s0 : 0];
+                        matched = __ballot(j <= hi && fabsf(a - fx) <= tau) != 0;
+                    }
+                    if (matched && lane == 0) list[h] = -1 - e;
+                }
+                __syncthreads();  // (the span is done with: land may be overwritten; the marks are visible)
+            }
+        }
+        if (in) cls[y * nx + x] = hole ? (list[rank] < 0 ? 2.0f : 1.0f) : 0.0f;
+        // No barrier before the next row: a thread that runs ahead writes only count[], which nobody reads any more after the row's
+        // second barrier, and reaches no write of list or land before the next row's first barrier -- which every thread passes only
+        // after it has read its list entry above.
+    }
 }
 
 const char *holes_phase_name(int phase)
@@ -233,13 +321,30 @@ hipError_t launch_holes_phase(int phase, const HolesParams &p, const HolesChoice
             break;
         case kHolesApply: {
             const dim3 grid((unsigned)c.grid_apply);
-            if (p.dirs == 2) hipLaunchKernelGGL(k_holes_apply<2>, grid, block, 0, s, p.d, npix, p.planes, p.mode, p.out, p.filled);
-            else if (p.dirs == 4) hipLaunchKernelGGL(k_holes_apply<4>, grid, block, 0, s, p.d, npix, p.planes, p.mode, p.out, p.filled);
-            else hipLaunchKernelGGL(k_holes_apply<8>, grid, block, 0, s, p.d, npix, p.planes, p.mode, p.out, p.filled);
+#define APPLY(DIRS, CLS) hipLaunchKernelGGL((k_holes_apply<DIRS, CLS>), grid, block, 0, s, p.d, npix, p.planes, p.mode, p.out, p.filled, p.cls, p.mode_occ)
+            if (p.cls) {  // the classified instances: p.mode is the mismatches' rule
+                if (p.dirs == 2) APPLY(2, true);
+                else if (p.dirs == 4) APPLY(4, true);
+                else APPLY(8, true);
+            } else if (p.dirs == 2) APPLY(2, false);
+            else if (p.dirs == 4) APPLY(4, false);
+            else APPLY(8, false);
+#undef APPLY
             break;
         }
         default: return hipErrorInvalidValue;
     }
+    return hipGetLastError();
+}
+
+// The grid, the span and the LDS bytes are the choice's (plan_holes_classify); the segment is the workgroup.
+hipError_t launch_holes_classify(const HolesClassifyParams &p, const HolesClassifyChoice &c, hipStream_t s)
+{
+    if (c.family != kHolesLines || c.seg != kHolesThreads || c.span < 1 || c.span % kHolesChunk || c.span > kHolesClsMaxSpan ||
+        c.lds_bytes != 4 * (c.span + c.seg + kHolesClsWords) || c.grid_x < 1 || c.grid_y < 1 || c.grid_y > kHolesClsMaxRows)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_holes_classify, dim3((unsigned)c.grid_x, (unsigned)c.grid_y), dim3(kHolesThreads), (size_t)c.lds_bytes, s, p.d, p.nx, p.ny,
+                       p.other, p.vnx, p.dmin, p.dmax, p.tau, c.span, p.cls);
     return hipGetLastError();
 }
 

@@ -7,6 +7,7 @@
 // instance, which grid, pruned or not); tests/test_wta_plan.py, tests/test_runnerup_plan.py.
 // ... and the speckle filter's tile, grids and scratch (plan_speckle); tests/test_speckle_plan.py.
 // ... and hole filling's chunk, band, grids and scratch (plan_holes); tests/test_holes_plan.py.
+// ... and hole classification's segment, span, grid and LDS bytes (plan_holes_classify); tests/test_occlusion_model.py.
 // ... and which kernels take an aggregation call at all (plan_agg_route, plan_subbatch, plan_dense_kernels behind them: pure functions
 // that ASK for the facts of the device they need, one at a time); tests/test_route_plan.py.
 #pragma once
@@ -1088,6 +1089,44 @@ inline HolesChoice plan_holes(const HolesRequest &q)
     c.grid_rows = (2ll * q.ny * kHolesChunk + kHolesThreads - 1) / kHolesThreads;
     c.grid_walk = (c.nlines + kHolesThreads - 1) / kHolesThreads;
     c.grid_apply = (npix + kHolesThreads - 1) / kHolesThreads;
+    return c;
+}
+
+// ---- hole classification (k_holes_classify, mgm_holes.hip) -----------------------------------------------------------
+// A workgroup takes `seg` pixels of a row at a time (one per thread) and stages the other view's landing coordinates of the columns
+// the segment's holes can name -- [x0 + dmin, x1 + dmax] cut to the other view -- in LDS, `span` of them at a time: a label range
+// of any length L is a loop over spans, never a larger allocation.  The launch is grid_x segments x grid_y workgroup rows; a
+// workgroup row strides over the image rows.  tests/test_occlusion_model.py.
+struct HolesClassifyRequest {
+    int nx, ny;   // the map with holes
+    int vnx;      // the other view's width (its height is ny)
+    int num_cu;   // compute units of the device (0: unknown); one choice per shape today, as in HolesRequest
+    long long L;  // labels of the range: dmax - dmin + 1 >= 1 (64 bits: the difference of two ints)
+};
+static_assert(std::has_unique_object_representations_v<HolesClassifyRequest>, "HolesClassifyRequest: integers only, no padding");
+struct HolesClassifyChoice {
+    long long grid_x;     // segments of a row
+    long long grid_y;     // workgroup rows: min(ny, kHolesClsMaxRows); workgroup row r takes the image rows r, r + grid_y, ...
+    int lds_bytes;        // 4 * (span + seg + kHolesClsWords): landing coordinates, the segment's hole list, the waves' counts
+    int family;           // kHolesRefuse or kHolesLines (the one kernel there is)
+    int seg;              // pixels of a row per workgroup and turn: kHolesThreads
+    int span;             // landing coordinates staged at a time: a multiple of the wave's width, at most kHolesClsMaxSpan
+};
+static_assert(std::has_unique_object_representations_v<HolesClassifyChoice>, "HolesClassifyChoice: integers only, no padding");
+constexpr int kHolesClsMaxSpan = 1024, kHolesClsMaxRows = 65535, kHolesClsWords = 8;
+inline HolesClassifyChoice plan_holes_classify(const HolesClassifyRequest &q)
+{
+    HolesClassifyChoice c{};
+    if (q.nx < 1 || q.ny < 1 || (long long)q.nx * q.ny > kHolesMaxPixels) return c;  // (what plan_holes refuses)
+    if (q.vnx < 1 || q.L < 1) return c;
+    c.family = kHolesLines;
+    c.seg = kHolesThreads;
+    // the columns one full segment can name: seg + L - 1 (L is at most 2^32: no overflow in 64 bits), never more than the other view has
+    const long long want = std::min<long long>(std::min<long long>(q.L, kHolesClsMaxSpan) + c.seg - 1, q.vnx);
+    c.span = (int)std::min<long long>(kHolesClsMaxSpan, (want + kHolesChunk - 1) / kHolesChunk * kHolesChunk);
+    c.grid_x = ((long long)q.nx + c.seg - 1) / c.seg;
+    c.grid_y = std::min<long long>(q.ny, kHolesClsMaxRows);
+    c.lds_bytes = 4 * (c.span + c.seg + kHolesClsWords);
     return c;
 }
 

@@ -510,6 +510,7 @@ int ms_run(mgm_ctx *c, const mgm_img *u0, const mgm_img *v0, const mgm_ms_params
             }
         }
         if (finest && nolr && (r = copy_image(c, O[0], nolr))) return r;
+        if (finest && nrun == 2 && p.outR_nolr && (r = copy_image(c, O[1], p.outR_nolr))) return r;
         if (nrun == 2) {
             if ((r = mgm_leftright_dev(c, O[1], O[0], p.tau, st.spare[1])) || (r = mgm_leftright_dev(c, O[0], O[1], p.tau, st.spare[0]))) return r;
             for (int k = 0; k < 2; k++)
@@ -552,10 +553,12 @@ extern "C" int mgm_multiscale_pair_dev(mgm_ctx *c, const mgm_img *u, const mgm_i
     for (const mgm_img *im : {(const mgm_img *)outR, (const mgm_img *)costR})
         if (im && (im->nx != v->nx || im->ny != v->ny || im->nch != 1))
             return fail(c, MGM_ERR_INVALID, "mgm_multiscale_pair: outR / costR must have the right image's size");
+    if (p.outR_nolr && (p.outR_nolr->nx != v->nx || p.outR_nolr->ny != v->ny || p.outR_nolr->nch != 1))
+        return fail(c, MGM_ERR_INVALID, "mgm_multiscale_pair: outR_nolr must have the right image's size");
     {
-        const mgm_img *outs[5] = {outL, costL, outR, costR, outL_nolr};
-        for (int a = 0; a < 5; a++)
-            for (int b = a + 1; b < 5; b++)
+        const mgm_img *outs[6] = {outL, costL, outR, costR, outL_nolr, p.outR_nolr};
+        for (int a = 0; a < 6; a++)
+            for (int b = a + 1; b < 6; b++)
                 if (outs[a] && outs[a] == outs[b]) return fail(c, MGM_ERR_INVALID, "mgm_multiscale_pair: the output images must be different images");
     }
     HIPCHK(c, hipSetDevice(c->device));

@@ -346,6 +346,18 @@ static void fill_holes_map(mgm_ctx *ctx, mgm_img *d, const std::string &mode, in
     if (int rc = mgm_fill_holes_dev(ctx, d, mode.c_str(), dirs, maxdist, d, nullptr)) die(ctx, rc, "mgm_fill_holes");
 }
 
+// MGM_FILL_HOLES_OCC=seclow|sechigh|min|max|median: the holes of the final left map are classified from the right map
+// as it entered the left-right test (`other`), over -r/-R at TESTLRRL_TAU; occlusions take `occ`, mismatches MGM_FILL_HOLES's rule
+static void fill_holes_classified_map(mgm_ctx *ctx, mgm_img *d, const mgm_img *other, int dmin, int dmax, float tau, const std::string &occ,
+                                      const std::string &mis, int dirs, int maxdist)
+{
+    ImgHold cls{ctx};
+    int nx, ny, nch, rc;
+    if ((rc = mgm_img_dims(d, &nx, &ny, &nch)) || (rc = mgm_img_create(ctx, nx, ny, 1, &cls.im))) die(ctx, rc, "mgm_img_create");
+    if ((rc = mgm_classify_holes_dev(ctx, d, other, dmin, dmax, tau, cls.im))) die(ctx, rc, "mgm_classify_holes");
+    if ((rc = mgm_fill_holes_classified_dev(ctx, d, cls.im, occ.c_str(), mis.c_str(), dirs, maxdist, d, nullptr))) die(ctx, rc, "mgm_fill_holes_classified");
+}
+
 // iterations 2..TSGM_ITER of main()'s loop (mgm.cc:377-388): the ranges narrow around the previous solution
 // (update_dmin_dmax), the volume -- and with it every scan-line pass -- stays the same, so only the winner search and
 // the refinement are redone, on the Lr volumes the context still holds
@@ -407,6 +419,7 @@ struct Job {
     std::string fill;         // MGM_FILL_HOLES: median, min or max -- the final left map's holes are filled (empty: off)
     int fill_dirs = 8;        // MGM_FILL_HOLES_DIRS: 2, 4 or 8 rays
     int fill_dist = 0;        // MGM_FILL_HOLES_DIST: a candidate is at most this many steps away (0: no limit)
+    std::string fill_occ;     // MGM_FILL_HOLES_OCC: the occlusions' rule -- the holes are classified, `fill` is the mismatches' (empty: off)
     int early = -1;           // >= 0: the command line ends before any work with this code ...
     std::string early_out;    // ... after these lines on stdout
     std::string early_err;    // ... and stderr
@@ -460,6 +473,12 @@ static void parse_job(Job &j)
                         "              MGM_FILL_HOLES_DIST=0 steps away (0: no limit); rays read the unfilled map; a hole that no ray serves stays;\n"
                         "              runs last, after MGM_SPECKLE, and before the back-projected image, with -S on the full-size map only; leaves\n"
                         "              the -l map, the cost map, -c's map and stdout as they are; combines with every other mode)\n"
+                        "             MGM_FILL_HOLES_OCC=none (seclow, sechigh, min, max or median, with MGM_FILL_HOLES: the holes are classified first --\n"
+                        "              a hole (x,y) is a mismatch when a pixel xr of the right map as it entered the left-right test, x+dmin <= xr <=\n"
+                        "              x+dmax of -r/-R, lands within TESTLRRL_TAU of it, |xr + right(xr,y) - x| <= tau, else an occlusion; occlusions take\n"
+                        "              this rule, mismatches MGM_FILL_HOLES's; seclow / sechigh: the second lowest / second highest candidate -- the\n"
+                        "              background's is sechigh for a range like -r -64 -R 0, seclow for positive disparities; needs the right view:\n"
+                        "              TESTLRRL=0 leaves none, whatever MGM_RIGHT_FROM_LEFT is: exit code 2; the class map has no file option)\n"
                         "             (with several MGM_DEVICES, -S / -m -M / TSGM_ITER > 1 run on the first device; in --batch mode a FIRST line\n"
                         "              of that kind brings up one device for the whole batch, a later one leaves the other lines their devices)\n"
                         "resident mode: mgm --batch FILE|-   (one such command line per line of FILE, one device context for all)");
@@ -512,6 +531,13 @@ static void parse_job(Job &j)
         if (fl && (end == fl || *end || !(dist >= 0 && dist <= 2147483647.0) || dist != std::floor(dist)))
             return early(1, nullptr, "mgm: MGM_FILL_HOLES_DIST must be an integer >= 0 (steps; 0: no limit)\n");
         j.fill = m == "none" ? "" : m;
+        const char *fo = getenv("MGM_FILL_HOLES_OCC");
+        const std::string oc = fo ? fo : "";
+        if (!(oc.empty() || oc == "none" || oc == "seclow" || oc == "sechigh" || oc == "min" || oc == "max" || oc == "median"))
+            return early(1, nullptr, "mgm: MGM_FILL_HOLES_OCC must be seclow, sechigh, min, max, median or none\n");
+        j.fill_occ = oc == "none" ? "" : oc;
+        if (!j.fill_occ.empty() && j.fill.empty())
+            return early(1, nullptr, "mgm: MGM_FILL_HOLES_OCC needs MGM_FILL_HOLES=median, min or max (the mismatches' rule)\n");
         j.fill_dirs = (int)nd;
         j.fill_dist = (int)dist;
     }
@@ -628,9 +654,10 @@ static void multiscale_job(Session &S, Job &j, const Opts &o, const HostImg *plo
     struct Objs {
         mgm_ctx *ctx;
         mgm_img *du = nullptr, *dv = nullptr, *dlo = nullptr, *dhi = nullptr, *out = nullptr, *cost = nullptr, *nolr = nullptr, *syn = nullptr;
+        mgm_img *rnolr = nullptr;  // MGM_FILL_HOLES_OCC: the full-size right map before its left-right test
         ~Objs()
         {
-            for (mgm_img *im : {du, dv, dlo, dhi, out, cost, nolr, syn}) mgm_img_free(ctx, im);
+            for (mgm_img *im : {du, dv, dlo, dhi, out, cost, nolr, syn, rnolr}) mgm_img_free(ctx, im);
         }
     } d{ctx};
     int rc;
@@ -640,6 +667,7 @@ static void multiscale_job(Session &S, Job &j, const Opts &o, const HostImg *plo
         die(ctx, rc, "upload");
     for (mgm_img **im : {&d.out, &d.cost}) image_like(ctx, u.nx, u.ny, 1, im);
     if (!j.nolr_file.empty()) image_like(ctx, u.nx, u.ny, 1, &d.nolr);
+    if (!j.fill_occ.empty()) image_like(ctx, v.nx, v.ny, 1, &d.rnolr);
     mgm_ms_level levels[8] = {};
     int nlev = 0;
     mgm_ms_params p{};
@@ -655,6 +683,7 @@ static void multiscale_job(Session &S, Job &j, const Opts &o, const HostImg *plo
     p.refine = o.refine.c_str();
     p.iterations = ITER, p.median = median, p.testlrrl = both, p.tau = tau;
     p.levels_run = &nlev, p.levels = levels;
+    p.outR_nolr = d.rnolr;
     sw.mark("upload");
     if ((rc = mgm_multiscale_pair_dev(ctx, d.du, d.dv, &p, d.out, d.cost, nullptr, nullptr, d.nolr))) die(ctx, rc, "mgm_multiscale_pair");
     for (int s = nlev - 1; s >= 0; s--)
@@ -666,7 +695,8 @@ static void multiscale_job(Session &S, Job &j, const Opts &o, const HostImg *plo
             }
     sw.mark("enqueue");
     if (j.speckle > 0) speckle_map(ctx, d.out, j.speckle, j.speckle_diff);  // once, on level 0's final map
-    if (!j.fill.empty()) fill_holes_map(ctx, d.out, j.fill, j.fill_dirs, j.fill_dist);  // ... and after it
+    if (!j.fill_occ.empty()) fill_holes_classified_map(ctx, d.out, d.rnolr, o.dmin, o.dmax, tau, j.fill_occ, j.fill, j.fill_dirs, j.fill_dist);
+    else if (!j.fill.empty()) fill_holes_map(ctx, d.out, j.fill, j.fill_dirs, j.fill_dist);  // ... and after it
     if (!j.nolr_file.empty()) j.nolr = download(ctx, d.nolr, u.nx, u.ny, 1);
     j.outoff = download(ctx, d.out, u.nx, u.ny, 1);
     sw.mark("device+download");
@@ -721,6 +751,11 @@ static int device_job(Session &S, Job &j, const std::function<void()> &decoded, 
             fprintf(stderr, "mgm: -c / MGM_UNIQUENESS does not combine with %s\n", why);
             return 2;
         }
+    }
+    // MGM_FILL_HOLES_OCC: the classification reads the right map that entered the left-right test
+    if (!j.fill_occ.empty() && TESTLRRL == 0) {
+        fprintf(stderr, "mgm: MGM_FILL_HOLES_OCC needs the right view: TESTLRRL=0 leaves none (MGM_RIGHT_FROM_LEFT takes effect only with TESTLRRL != 0)\n");
+        return 2;
     }
     try {
         bring_up(S, ITER, ranged, j.nscales > 1);
@@ -861,7 +896,9 @@ static int device_job(Session &S, Job &j, const std::function<void()> &decoded, 
         // MGM_SPECKLE: last, on the final left map (with several devices: `ctx` is the device that holds the gathered map)
         if (j.speckle > 0) speckle_map(ctx, L.dout, j.speckle, j.speckle_diff);
         // MGM_FILL_HOLES: after every rejection step, before the back-projected image is made
-        if (!j.fill.empty()) fill_holes_map(ctx, L.dout, j.fill, j.fill_dirs, j.fill_dist);
+        // (MGM_FILL_HOLES_OCC: after the swap above R.dspare is the right map as it entered the left-right test)
+        if (!j.fill_occ.empty()) fill_holes_classified_map(ctx, L.dout, R.dspare, o.dmin, o.dmax, (float)TAU, j.fill_occ, j.fill, j.fill_dirs, j.fill_dist);
+        else if (!j.fill.empty()) fill_holes_map(ctx, L.dout, j.fill, j.fill_dirs, j.fill_dist);
         sw.mark("enqueue(rest)");
         j.outoff = download(ctx, L.dout, L.nx, L.ny, 1);
         sw.mark("device+download");
