@@ -160,6 +160,36 @@ int mgm_costvolume_build_ranged_dev(mgm_ctx *ctx, const mgm_img *u, const mgm_im
                                     const mgm_img *dmaxI, int hull_min, int hull_max, const char *prefilter,
                                     const char *distance, float truncDist, int census_win, mgm_cv **C);
 
+/* ---- sub-pixel label spacing: half- and quarter-pixel cost volumes (DESIGN.md "sub-pixel labels"; this library's own mode) ----
+ * The other image is matched at the fractional shifts k/s, k = 0..s-1, s = 1, 2 or 4: s phase images v_k, s ordinary builds C_k over
+ * [dmin, dmax], interleaved into ONE fine volume F with the labels s*dmin .. s*dmax, s*(dmax-dmin)+1 of them; fine label d' stands
+ * for the disparity d'/s.
+ *   phase image  v_0 is v, the same bits.  k > 0, t = k/s, per channel and row in fp32, column indices clamped to [0, vnx-1], every
+ *                product rounded and the sums in the order written (no contraction), non-finite pixels as IEEE gives:
+ *                  "linear"  v_k(x) = (1-t)*v(x) + t*v(x+1)
+ *                  "cubic"   v_k(x) = ((w0*v(x-1) + w1*v(x)) + w2*v(x+1)) + w3*v(x+2), Keys' weights (a = -1/2), exact in fp32:
+ *                            t = 1/4: -9/128, 111/128, 29/128, -3/128;  1/2: -1/16, 9/16, 9/16, -1/16;  3/4: t = 1/4 reversed
+ *   fine volume  with o' = d' - s*dmin:  F(y,x,o') = C_{o' mod s}(y,x,o' div s), the same bits, where C_k is exactly what
+ *                mgm_costvolume_build_dev(u, v_k, dmin, dmax, ...) produces, its "no finite cost => zeros" rule included; label
+ *                dmax of the phases k > 0 is dropped.  s = 1: F is C_0.  With non-finite pixels in v a fractional phase can lose
+ *                every label of a pixel where phase 0 keeps some: that phase's entries then read 0 by that rule -- use finite images.
+ * mgm_aggregate*, every winner search, the refinements and the runner-up search take F as any dense volume and work per FINE label:
+ * their maps are in fine units (mgm_subpix_scale_dev: out = in / (float)s, exact, NaN stays NaN; cost maps are not rescaled), and a
+ * slope of one pixel now takes s steps of P1.  The right view is the same call with the images exchanged and [-dmax, -dmin].
+ * F leaves the call in the state a direct build of its label count would leave it: one-byte codes (the compact or the padded compact
+ * copy, the fp32 copy stale) when every phase holds them by construction -- single-word census -- and an fp32 volume without copies,
+ * like an uploaded one, in every other case.  *F / *out: NULL for a new object, or one of the same geometry, refilled in place.
+ * Scratch: one phase image and s phase volumes of the [dmin, dmax] geometry, kept by the context for the next call of that geometry
+ * (mgm_ctx_trim releases them; like the other steps' scratch they are not part of what mgm_ctx_set_workspace_limit caps).
+ * MGM_ERR_INVALID: s outside {1, 2, 4}, k outside 0..s-1, an interp that is neither name, dmax < dmin, images of different channel
+ * counts, an object to refill of another geometry (for the phase image also: v itself).  mgm_subpix_scale_dev: out may be in.
+ * No synchronisation; the timing table lists k_subpix_phase, k_cv_interleave and k_scale_map. */
+int mgm_subpix_phase_dev(mgm_ctx *ctx, const mgm_img *v, int s, int k, const char *interp, mgm_img **out);
+int mgm_costvolume_build_subpix_dev(mgm_ctx *ctx, const mgm_img *u, const mgm_img *v, int dmin, int dmax, int s,
+                                    const char *interp, const char *prefilter, const char *distance, float truncDist,
+                                    int census_win, mgm_cv **F);
+int mgm_subpix_scale_dev(mgm_ctx *ctx, const mgm_img *in, int s, mgm_img *out);
+
 /* ---- edge weights: compute_mgm_weights --------------------------------- */
 /* compute_mgm_weights (mgm_weights.h:63-85; called at mgm.cc:372 when -aP2 != 1): 8 planes of nx*ny weights.  *w8 == NULL
  * on entry: a new image is created; non-NULL: that nx*ny*8 image is refilled (like *C of mgm_costvolume_build_dev). */

@@ -35,6 +35,7 @@ ABI_SYMBOLS = [
     "mgm_multiscale_levels", "mgm_zoom_out_dev", "mgm_ranges_zoom_out_dev", "mgm_ranges_from_coarse_dev", "mgm_multiscale_pair_dev",
     "mgm_wta_runnerup_dev", "mgm_uniqueness_dev", "mgm_speckle_dev", "mgm_fill_holes_dev",
     "mgm_classify_holes_dev", "mgm_fill_holes_classified_dev",
+    "mgm_subpix_phase_dev", "mgm_costvolume_build_subpix_dev", "mgm_subpix_scale_dev",
     "mgm_debug_rel_lr_device_ptr", "mgm_debug_wta_rel_again_dev", "mgm_debug_lr_device_ptr",
 ]
 
@@ -124,6 +125,9 @@ def load_library():
     L.mgm_fill_holes_dev.argtypes = [vp, vp, cp, i, i, vp, vp]
     L.mgm_classify_holes_dev.argtypes = [vp, vp, vp, i, i, f, vp]
     L.mgm_fill_holes_classified_dev.argtypes = [vp, vp, vp, cp, cp, i, i, vp, vp]
+    L.mgm_subpix_phase_dev.argtypes = [vp, vp, i, i, cp, pp]
+    L.mgm_costvolume_build_subpix_dev.argtypes = [vp, vp, vp, i, i, i, cp, cp, cp, f, i, pp]
+    L.mgm_subpix_scale_dev.argtypes = [vp, vp, i, vp]
     L.mgm_update_ranges_dev.argtypes = [vp, vp, vp, vp, i, i]
     L.mgm_leftright_dev.argtypes = [vp, vp, vp, f, vp]
     L.mgm_backproject_dev.argtypes = [vp, vp, vp, vp, vp]
@@ -536,6 +540,76 @@ class Context:
             if o is not None and o is not chkR and o is not costL:
                 o.free()
         return chkL, chkR, costL
+
+    # ---- sub-pixel label spacing (mgm_subpix.hip) ----
+    def subpix_phase_dev(self, v, s, k, interp="cubic", into=None):
+        """The phase image v_k of v at the shift k/s along x (mgm_subpix_phase_dev): s 1, 2 or 4, k 0..s-1, interp "linear" or "cubic"
+        (Keys, a = -1/2); k = 0 is a copy of v.  into: an image of v's shape to refill, None for a new one."""
+        h = C.c_void_p(into.h.value) if into is not None else C.c_void_p()
+        self._chk(self.lib.mgm_subpix_phase_dev(self.h, v.h, s, k, None if interp is None else str(interp).encode(), C.byref(h)))
+        return into if into is not None else Image(self, h)
+
+    def costvolume_subpix_dev(self, u, v, dmin, dmax, s, interp="cubic", prefilter="none", distance="ad", truncDist=float("inf"),
+                              census_win=3, into=None):
+        """The fine volume of mgm_costvolume_build_subpix_dev: labels s*dmin .. s*dmax, fine label d' = the disparity d'/s, made of
+        s ordinary builds of u against the phase images of v.  Aggregations and searches of it give maps in fine units
+        (subpix_scale_dev); P1, P2, the runner-up radius and the refinements act per fine label."""
+        h = C.c_void_p(into.h.value) if into is not None else C.c_void_p()
+        self._chk(self.lib.mgm_costvolume_build_subpix_dev(self.h, u.h, v.h, dmin, dmax, s, None if interp is None else str(interp).encode(),
+                                                           prefilter.encode(), distance.encode(), truncDist, census_win, C.byref(h)))
+        return into if into is not None else CostVolume(self, h)
+
+    def subpix_scale_dev(self, img, s, out=None):
+        """out = img / s (mgm_subpix_scale_dev): a map in fine labels becomes one in pixels.  out may be img itself; None: a new image."""
+        nch, ny, nx = img.shape
+        mine = out is None
+        out = self.new_image(nx, ny, nch) if mine else out
+        try:
+            self._chk(self.lib.mgm_subpix_scale_dev(self.h, img.h, s, out.h))
+        except Exception:
+            if mine:
+                out.free()
+            raise
+        return out
+
+    def pair_subpix(self, u, v, dmin, dmax, s, interp="cubic", P1=8.0, P2=32.0, NDIR=4, TSGM=4, use_fh=0, fix_overcount=1, aP2=1.0,
+                    aThresh=5.0, prefilter="none", distance="ad", truncDist=float("inf"), census_win=3, refine="none", tau=1.0, median=0):
+        """A stereo pair at the label spacing 1/s: both runs on fine volumes (the right->left one with the images exchanged and the
+        range [-dmax, -dmin]), the rescale to pixels, the optional medians and the left-right test of the left map.  u, v: device
+        images of one height; P1 / P2 as given, PER FINE LABEL (a slope of one pixel takes s steps of P1).  Returns device images
+        (checked left map, unchecked left map, unchecked right map, left cost map); the cost map is not rescaled."""
+        _, ny, nx = u.shape
+        _, vny, vnx = v.shape
+        if vny != ny:
+            raise ValueError("pair_subpix: the two images must have one height")
+        refine = refine if refine and refine != "none" else None
+        mine = []
+        try:
+            maps = []
+            for a, b, lo, hi in ((u, v, dmin, dmax), (v, u, -dmax, -dmin)):
+                cv = self.costvolume_subpix_dev(a, b, lo, hi, s, interp, prefilter, distance, truncDist, census_win)
+                mine.append(cv)
+                w8 = self.weights_dev(a, aP2, aThresh) if aP2 != 1 else None
+                mine.append(w8)
+                _, out, cost = self.aggregate_dev(cv, P1, P2, NDIR, TSGM, use_fh, fix_overcount, w8=w8, refine=refine)
+                mine += [out, cost]
+                self.subpix_scale_dev(out, s, out=out)
+                if median:
+                    m = self.median_dev(out, median)
+                    mine.append(m)
+                    out = m
+                maps.append((out, cost))
+            (outL, costL), (outR, _) = maps
+            chkL = self.leftright_dev(outL, outR, tau)
+        except Exception:
+            for o in mine:
+                if o is not None:
+                    o.free()
+            raise
+        for o in mine:
+            if o is not None and o is not outL and o is not outR and o is not costL:
+                o.free()
+        return chkL, outL, outR, costL
 
     def update_ranges_dev(self, outoff, dminI, dmaxI, slack=3, radius=2):
         self._chk(self.lib.mgm_update_ranges_dev(self.h, outoff.h, dminI.h, dmaxI.h, slack, radius))

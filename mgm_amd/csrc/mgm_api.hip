@@ -832,6 +832,54 @@ int mgm_fill_holes_classified_dev(mgm_ctx *c, const mgm_img *d, const mgm_img *c
     return MGM_OK;
 }
 
+// Sub-pixel label spacing (mgm_subpix.hip): the phase image on its own (the build makes its own in the context's
+// scratch) and the rescale of a map from fine labels to pixels.
+int mgm_subpix_phase_dev(mgm_ctx *c, const mgm_img *v, int s, int k, const char *interp, mgm_img **out)
+{
+    if (int jr = pipe_join(c)) return jr;  // (pipelined context: run what has been deferred first)
+    if (!c || !v || !out) return fail(c, MGM_ERR_INVALID, "mgm_subpix_phase: null argument");
+    if (s != 1 && s != 2 && s != 4) return fail(c, MGM_ERR_INVALID, "mgm_subpix_phase: s must be 1, 2 or 4");
+    if (k < 0 || k >= s) return fail(c, MGM_ERR_INVALID, "mgm_subpix_phase: k must be 0 .. s-1");
+    const int ip = subpix_interp_index(interp);
+    if (ip < 0) return fail(c, MGM_ERR_INVALID, "mgm_subpix_phase: interp must be linear or cubic");
+    if (*out && ((*out)->nx != v->nx || (*out)->ny != v->ny || (*out)->nch != v->nch || *out == v))
+        return fail(c, MGM_ERR_INVALID, "mgm_subpix_phase: *out is non-NULL but is v or has a different geometry");
+    HIPCHK(c, hipSetDevice(c->device));
+    const bool provided = *out != nullptr;
+    if (!provided)
+        if (int r = mgm_img_create(c, v->nx, v->ny, v->nch, out)) return r;
+    hipError_t e;
+    if (k == 0) {  // v_0 is v, the same bits
+        e = hipMemcpyAsync((*out)->d, v->d, sizeof(float) * (size_t)v->nx * v->ny * v->nch, hipMemcpyDeviceToDevice, c->stream);
+    } else {
+        TimeScope t(c, "k_subpix_phase");
+        e = launch_subpix_phase(v->d, v->nx, (long long)v->ny * v->nch, s, k, ip, (*out)->d, c->stream);
+    }
+    if (e != hipSuccess) {
+        const int r = hipfail(c, e, "k_subpix_phase");
+        if (!provided) {
+            const std::string msg = c->err;
+            mgm_img_free(c, *out);
+            *out = nullptr;
+            c->err = msg;
+        }
+        return r;
+    }
+    return MGM_OK;
+}
+
+int mgm_subpix_scale_dev(mgm_ctx *c, const mgm_img *in, int s, mgm_img *out)
+{
+    if (int jr = pipe_join(c)) return jr;  // (pipelined context: run what has been deferred first)
+    if (!c || !in || !out) return fail(c, MGM_ERR_INVALID, "mgm_subpix_scale: null argument");
+    if (s != 1 && s != 2 && s != 4) return fail(c, MGM_ERR_INVALID, "mgm_subpix_scale: s must be 1, 2 or 4");
+    if (out->nx != in->nx || out->ny != in->ny || out->nch != in->nch) return fail(c, MGM_ERR_INVALID, "mgm_subpix_scale: image size mismatch");
+    HIPCHK(c, hipSetDevice(c->device));
+    TimeScope t(c, "k_scale_map");
+    HIPCHK(c, launch_scale_map(in->d, (long long)in->nx * in->ny * in->nch, s, out->d, c->stream));
+    return MGM_OK;
+}
+
 int mgm_leftright_dev(mgm_ctx *c, const mgm_img *d, const mgm_img *other, float tau, mgm_img *out)
 {
     if (int jr = pipe_join(c)) return jr;  // (pipelined context: run what has been deferred first)

@@ -239,6 +239,7 @@ int mgm_ctx_destroy(mgm_ctx *c)
     c->dense_plans.free_all();
     c->rel_plans.free_all();
     for (Buf *b : workspace_bufs(c)) release(*b);
+    subpix_release(c);
     release(c->words);
     for (auto &t : c->tim) {
         if (t.alias) continue;
@@ -274,6 +275,7 @@ int mgm_ctx_trim(mgm_ctx *c)
     c->rel_last.clear();
     c->wta_stats_n = 0;
     for (Buf *b : workspace_bufs(c)) release(*b);
+    subpix_release(c);
     forget_hand_regions(c);
     c->dense_plans.free_all();
     c->rel_plans.free_all();

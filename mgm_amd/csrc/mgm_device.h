@@ -172,6 +172,20 @@ struct HolesClassifyParams {
 struct HolesClassifyChoice;  // (mgm_planner.h: what plan_holes_classify decided)
 hipError_t launch_holes_classify(const HolesClassifyParams &p, const HolesClassifyChoice &c, hipStream_t s);
 
+// sub-pixel label spacing (mgm_subpix.hip): the phase image v_k of v at the shift k/s (k_subpix_phase), the fine
+// volume gathered from the s phase volumes (k_cv_interleave), and the maps' rescale out = in / s (k_scale_map; out may be in)
+enum SubpixInterp { kSubpixLinear = 0, kSubpixCubic };
+hipError_t launch_subpix_phase(const float *v, int vnx, long long nrows, int s, int k, int interp, float *out, hipStream_t st);
+struct SubpixParams {
+    const void *phase[4];  // the s phase volumes [npix][in_slots], all in one form: one-byte codes (cb = 1) or fp32 (cb = 4)
+    void *F;               // [npix][slots] in that form; F(p, o') = phase[o' % s](p, o' / s) for o' < labels, the code of +INF beyond
+    long long npix;
+    int labels, slots, in_slots, s, cb;
+};
+struct SubpixChoice;  // (mgm_planner.h: what plan_subpix decided)
+hipError_t launch_cv_interleave(const SubpixParams &p, const SubpixChoice &c, hipStream_t st);
+hipError_t launch_scale_map(const float *in, long long n, int s, float *out, hipStream_t st);
+
 // ---- ragged volumes in the range-proportional layout (mgm_pass_rel.hip, k_wta_rel): 64 label slots per pixel placed at the
 // pixel's own window, slot k <-> disparity base + k
 struct RelVolume {

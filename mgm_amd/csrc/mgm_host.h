@@ -209,6 +209,10 @@ struct mgm_ctx {
     Buf lmin, wta_stats;  // (wta_stats: kWtaStatBytes)
     Buf speckle;          // mgm_speckle_dev: the parent and count planes of its labelling (plan_speckle's scratch_bytes)
     Buf holes;            // mgm_fill_holes_dev: the candidate planes and the bands' carries (plan_holes's scratch_bytes)
+    // mgm_costvolume_build_subpix_dev: the phase image, refilled in place for every k > 0, and the s phase volumes the
+    // fine volume is gathered from; kept for the next call of the same geometry, released by mgm_ctx_trim (subpix_release)
+    mgm_img *subpix_img = nullptr;
+    mgm_cv *subpix_cv[4] = {};
     int wta_stats_n = 0;
     DenseRun last;    // the last aggregation, if it was a dense one ...
     RelRun rel_last;  // ... or a range-proportional one (each remember stage clears the other)
@@ -364,6 +368,8 @@ int c8_resolve(mgm_ctx *c, const mgm_cv *ccv, bool *use);
 int p8_alloc(mgm_ctx *c, mgm_cv *cv, int LP, int cb);
 int rel_resolve(mgm_ctx *c, const mgm_cv *cv, bool *usable);
 int rel_alloc(mgm_ctx *c, mgm_cv *cv, int slots, int cb);  // (re)allocates relbuf for the format and sets rel_slots / rel_cb; MGM_OK also when the device has no room (relbuf stays null)
+void subpix_release(mgm_ctx *c);  // frees the sub-pixel build's scratch image and volumes (the caller has synchronised)
+int subpix_interp_index(const char *name);  // "linear" 0, "cubic" 1, anything else (NULL included) -1
 
 // the launch plan (mgm_plan.hip)
 int run_passes(mgm_ctx *c, const mgm_cv *const *Cs, const mgm_img *const *w8s, int nb, float P1, float P2, int MGM, int use_fh, int first,

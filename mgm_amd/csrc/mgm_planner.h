@@ -1130,6 +1130,61 @@ inline HolesClassifyChoice plan_holes_classify(const HolesClassifyRequest &q)
     return c;
 }
 
+// ---- sub-pixel label spacing (k_cv_interleave, mgm_subpix.hip) -----------------------------------------------------
+// The fine volume F(p, o') = C_{o' mod s}(p, o' div s) is GATHERED from the s phase volumes at once: a workgroup takes `pix`
+// consecutive pixels and writes their rows of F -- one contiguous span of memory -- in chunks of `vec` costs per thread, every chunk
+// one aligned 16-byte store, reading each phase's rows of the same pixels (contiguous as well).  One-byte codes: a row has `slots`
+// label slots (a multiple of 64: the compact or the padded compact form), the slots beyond `labels` get the code of +INF; fp32: a row
+// has exactly `labels` floats, so rows are only 4-byte aligned and the chunks are cut from the workgroup's span instead (pix is a
+// multiple of four: the span starts 16-byte aligned).  The pixels per workgroup, the grid and the family are decided here and
+// nowhere else; tests/test_subpix_plan.py.
+struct SubpixRequest {
+    long long npix;  // pixels of the volume
+    int labels;      // L' = s * (L - 1) + 1 labels of the fine volume
+    int slots;       // label slots of a pixel's row of F: cb = 1: labels or the padded count (a multiple of 64); cb = 4: labels
+    int in_slots;    // label slots of a pixel's row of a phase volume (>= L = (labels - 1) / s + 1; cb = 4: exactly L)
+    int s;           // phases: 2 or 4
+    int cb;          // bytes per cost of the form the phases are in and F gets: 1 (codes) or 4 (fp32)
+    int num_cu;      // compute units of the device (0: unknown); one choice per shape today, as in HolesRequest
+};
+static_assert(std::has_unique_object_representations_v<SubpixRequest>, "SubpixRequest: integers only, no padding");
+enum SubpixFamily { kSubpixRefuse = 0, kSubpixCodes, kSubpixFloats };
+struct SubpixChoice {
+    long long grid;  // workgroups of kSubpixThreads threads; workgroup b takes the pixels [b * pix, min(npix, (b + 1) * pix))
+    int family;
+    int pix;         // pixels per workgroup
+    int vec;         // costs per thread and chunk: 16 codes or 4 floats (16 bytes either way)
+    int chunks;      // chunks of a full workgroup: pix * slots / vec (codes: whole rows; floats: the last one may be cut)
+};
+static_assert(std::has_unique_object_representations_v<SubpixChoice>, "SubpixChoice: integers only, no padding");
+constexpr int kSubpixThreads = 256, kSubpixSpanBytes = 16384;  // bytes of F per workgroup, at least: four chunks per thread
+constexpr int kSubpixMaxLabels = 1 << 22;                      // (kMaxLabels, mgm_device.h: what mgm_cv_create admits)
+inline SubpixChoice plan_subpix(const SubpixRequest &q)
+{
+    SubpixChoice c{};
+    if (q.npix < 1 || q.labels < 1 || q.labels > kSubpixMaxLabels || (q.s != 2 && q.s != 4) || (q.labels - 1) % q.s) return c;
+    const int L = (q.labels - 1) / q.s + 1;  // labels of a phase volume
+    long long pix;
+    if (q.cb == 1) {
+        if (q.slots < q.labels || q.slots % 64 || q.in_slots < L || q.in_slots % 64) return c;
+        c.family = kSubpixCodes, c.vec = 16;
+        pix = std::max<long long>(1, (kSubpixSpanBytes + q.slots - 1) / q.slots);
+    } else if (q.cb == 4) {
+        if (q.slots != q.labels || q.in_slots != L) return c;
+        c.family = kSubpixFloats, c.vec = 4;
+        pix = std::max<long long>(1, (kSubpixSpanBytes / 4 + q.labels - 1) / q.labels);
+        pix = (pix + 3) / 4 * 4;
+    } else {
+        return c;
+    }
+    // (the costs of a workgroup index in 32 bits: at most 4 * 2^22 floats, or 16384 + slots codes)
+    const long long grid = (q.npix + pix - 1) / pix;
+    if (grid > 2147483647ll) return SubpixChoice{};
+    c.grid = grid, c.pix = (int)pix;
+    c.chunks = (int)((pix * q.slots + c.vec - 1) / c.vec);
+    return c;
+}
+
 // ---- which kernels take an aggregation call ----------------------------------------------------------------------------------
 // Three decisions that need facts only the device knows (the weights' values, whether a volume's compact or range-proportional copy
 // is usable, whether a padded copy fits a compact form), and must not ask for one they can do without: a call that is no candidate

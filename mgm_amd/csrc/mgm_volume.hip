@@ -492,7 +492,176 @@ static int costvolume_build(mgm_ctx *c, const mgm_img *u, const mgm_img *v, int 
     return r;
 }
 
+// ---- sub-pixel label spacing: the fine volume gathered from s ordinary builds -----------------------------------------
+void subpix_release(mgm_ctx *c)
+{
+    if (c->subpix_img) {
+        (void)hipFree(c->subpix_img->d);
+        delete c->subpix_img;
+        c->subpix_img = nullptr;
+    }
+    for (mgm_cv *&cv : c->subpix_cv)
+        if (cv) {
+            mgm_cv_free(c, cv);
+            cv = nullptr;
+        }
+}
+int subpix_interp_index(const char *name)
+{
+    if (name && !strcmp(name, "linear")) return kSubpixLinear;
+    if (name && !strcmp(name, "cubic")) return kSubpixCubic;
+    return -1;
+}
+
+// The s phase volumes C_k = build(u, v_k) over [dmin, dmax], in the context's scratch (v_0 = v; v_k, k > 0: the scratch image).
+static int subpix_build_phases(mgm_ctx *c, const mgm_img *u, const mgm_img *v, int dmin, int dmax, int s, int interp, const char *prefilter,
+                               const char *distance, float truncDist, int census_win)
+{
+    int r;
+    bool synced = false;
+    const auto sync_once = [&]() -> int {  // (kernels of an earlier call may still read what is about to be freed)
+        if (!synced) HIPCHK(c, hipStreamSynchronize(c->stream));
+        synced = true;
+        return MGM_OK;
+    };
+    if (c->subpix_img && (c->subpix_img->nx != v->nx || c->subpix_img->ny != v->ny || c->subpix_img->nch != v->nch)) {
+        if ((r = sync_once())) return r;
+        (void)hipFree(c->subpix_img->d);
+        delete c->subpix_img;
+        c->subpix_img = nullptr;
+    }
+    if (!c->subpix_img && (r = mgm_img_create(c, v->nx, v->ny, v->nch, &c->subpix_img))) return r;
+    for (int k = 0; k < 4; k++) {
+        mgm_cv *&cv = c->subpix_cv[k];
+        if (cv && (k >= s || cv->nx != u->nx || cv->ny != u->ny || cv->dmin != dmin || cv->dmax != dmax)) {
+            mgm_cv_free(c, cv);  // (synchronises)
+            cv = nullptr;
+        }
+    }
+    for (int k = 0; k < s; k++) {
+        const mgm_img *vk = v;
+        if (k > 0) {
+            TimeScope t(c, "k_subpix_phase");
+            HIPCHK(c, launch_subpix_phase(v->d, v->nx, (long long)v->ny * v->nch, s, k, interp, c->subpix_img->d, c->stream));
+            vk = c->subpix_img;
+        }
+        if ((r = costvolume_build(c, u, vk, dmin, dmax, nullptr, nullptr, prefilter, distance, truncDist, census_win, &c->subpix_cv[k]))) return r;
+    }
+    return MGM_OK;
+}
+
+// The gather.  When the plan of a direct build of F's label count starts in a one-byte form that fits by construction (single-word
+// census under a truncation that is a byte code) and every phase holds valid one-byte codes, F gets that form -- the compact copy,
+// or the padded compact copy where the builder would have written one -- and its fp32 copy is stale.  In every other case the phases
+// are brought to fp32 (ensure_f32) and F is an fp32 volume that knows nothing of its copies, like an uploaded one.
+static int subpix_gather(mgm_ctx *c, const mgm_img *u, const mgm_img *v, int s, const char *prefilter, const char *distance, float truncDist,
+                         int census_win, mgm_cv *F)
+{
+    int r;
+    const int Lf = F->dmax - F->dmin + 1;
+    const long long npix = (long long)F->nx * F->ny;
+    const FillRequest q{u->nx, u->ny, v->nx, v->ny, u->nch, Lf, distance_index(distance), prefilter_index(prefilter), census_win, truncDist,
+                        false, FillMemory{}, dev().c8, dev().pad, dev().lazy_f32, rel_enabled(), tune_num("rel_direct", 1) != 0};
+    const FillPlan plan = plan_fill(q);
+    const FillAttempt a = plan.first;
+    bool codes = !plan.err && (a.form == FillForm::CompactOnly || a.form == FillForm::Padded) && !a.readback && a.cbytes == 1;
+    SubpixParams p{};
+    p.npix = npix, p.labels = Lf, p.s = s;
+    for (int k = 0; k < s && codes; k++) {  // every phase in ONE one-byte form
+        const mgm_cv *P = c->subpix_cv[k];
+        const bool c8 = P->c8_state == CopyState::Valid && P->d8 && P->cbytes == 1, p8 = P->p8_state == CopyState::Valid && P->p8 && P->p8_cb == 1;
+        const int slots = c8 ? P->dmax - P->dmin + 1 : p8 ? P->p8_L : 0;
+        codes = slots != 0 && (k == 0 || slots == p.in_slots);
+        p.in_slots = slots;
+        p.phase[k] = c8 ? P->d8 : P->p8;
+    }
+    bool nan_words = false;
+    if (codes) {
+        p.cb = 1, p.slots = a.slots;
+        if (a.form == FillForm::Padded) {
+            if ((r = p8_alloc(c, F, a.slots, 1))) return r;
+            p.F = F->p8;
+        } else {
+            if ((r = c8_alloc(c, F, 1))) return r;
+            p.F = F->d8;
+        }
+    } else {
+        for (int k = 0; k < s; k++) {
+            if ((r = ensure_f32(c, c->subpix_cv[k]))) return r;
+            p.phase[k] = c->subpix_cv[k]->d;
+            nan_words |= c->subpix_cv[k]->nan_words;
+        }
+        if ((r = cv_alloc_f32(c, F))) return r;
+        p.cb = 4, p.slots = Lf, p.in_slots = (Lf - 1) / s + 1, p.F = F->d;
+    }
+    const SubpixChoice choice = plan_subpix(SubpixRequest{p.npix, p.labels, p.slots, p.in_slots, p.s, p.cb, c->num_cu});
+    if (choice.family == kSubpixRefuse) return fail(c, MGM_ERR_INTERNAL, "mgm_costvolume_build_subpix: no launch plan for this volume");
+    {
+        TimeScope t(c, "k_cv_interleave");
+        if (hipError_t e = launch_cv_interleave(p, choice, c->stream)) return hipfail(c, e, "k_cv_interleave");
+    }
+    if (codes) {
+        commit_fill(F, q, plan, a, FillMemory{});
+    } else {
+        cv_freshly_uploaded(F);
+        F->mem = FillMemory{};
+        F->f32_state = 1;
+        F->rel_only = false;
+        F->rel_state = CopyState::None;
+        F->nan_words = nan_words;
+    }
+    return MGM_OK;
+}
+
+static int costvolume_build_subpix(mgm_ctx *c, const mgm_img *u, const mgm_img *v, int dmin, int dmax, int s, const char *interp, const char *prefilter,
+                                   const char *distance, float truncDist, int census_win, mgm_cv **out)
+{
+    if (!c || !u || !v || !out) return fail(c, MGM_ERR_INVALID, "mgm_costvolume_build_subpix: null argument");
+    if (s != 1 && s != 2 && s != 4) return fail(c, MGM_ERR_INVALID, "mgm_costvolume_build_subpix: s must be 1, 2 or 4");
+    const int ip = subpix_interp_index(interp);
+    if (ip < 0) return fail(c, MGM_ERR_INVALID, "mgm_costvolume_build_subpix: interp must be linear or cubic");
+    if (dmax < dmin) return fail(c, MGM_ERR_INVALID, "mgm_costvolume_build_subpix: dmax < dmin");
+    if (u->nch != v->nch) return fail(c, MGM_ERR_INVALID, "mgm_costvolume_build_subpix: channel counts differ");
+    const long long flo = (long long)s * dmin, fhi = (long long)s * dmax;
+    if (flo < -2147483647ll - 1 || fhi > 2147483647ll) return fail(c, MGM_ERR_INVALID, "mgm_costvolume_build_subpix: s * dmin .. s * dmax does not fit an int");
+    if (fhi - flo + 1 > kMaxLabels) return fail(c, MGM_ERR_UNSUPPORTED, "more than 4 194 304 disparity labels per pixel are not supported");
+    if (s == 1) return costvolume_build(c, u, v, dmin, dmax, nullptr, nullptr, prefilter, distance, truncDist, census_win, out);  // F is C_0
+    HIPCHK(c, hipSetDevice(c->device));
+    int r;
+    if (*out) {
+        if ((*out)->nx != u->nx || (*out)->ny != u->ny || (*out)->dmin != (int)flo || (*out)->dmax != (int)fhi)
+            return fail(c, MGM_ERR_INVALID, "mgm_costvolume_build_subpix: *F is non-NULL but has a different geometry");
+        if (pipe_uses(c, *out) && (r = pipe_flush(c))) return r;
+        for (const mgm_cv *P : c->subpix_cv)
+            if (P == *out) return fail(c, MGM_ERR_INVALID, "mgm_costvolume_build_subpix: *F is one of the context's own volumes");
+    }
+    // a refusal of the ordinary build (a census window that is no multiple of 8 bits, ...) comes before anything is touched
+    if ((r = subpix_build_phases(c, u, v, dmin, dmax, s, ip, prefilter, distance, truncDist, census_win))) return r;
+    const bool provided = *out != nullptr;
+    if (!provided && (r = cv_create(c, u->nx, u->ny, (int)flo, (int)fhi, false, out))) return r;
+    mgm_cv *F = *out;
+    r = prepare_volume(c, F, nullptr, nullptr);
+    if (!r) r = subpix_gather(c, u, v, s, prefilter, distance, truncDist, census_win, F);
+    F->unfilled = r != MGM_OK;
+    if (r != MGM_OK) {
+        cv_refill_failed(F);
+        if (!provided) {
+            const std::string msg = c->err;
+            mgm_cv_free(c, F);
+            *out = nullptr;
+            c->err = msg;
+        }
+    }
+    return r;
+}
+
 extern "C" {
+
+int mgm_costvolume_build_subpix_dev(mgm_ctx *c, const mgm_img *u, const mgm_img *v, int dmin, int dmax, int s, const char *interp,
+                                    const char *prefilter, const char *distance, float truncDist, int census_win, mgm_cv **F)
+{
+    return costvolume_build_subpix(c, u, v, dmin, dmax, s, interp, prefilter, distance, truncDist, census_win, F);
+}
 
 int mgm_costvolume_build_dev(mgm_ctx *c, const mgm_img *u, const mgm_img *v, int dmin, int dmax, const char *prefilter,
                              const char *distance, float truncDist, int census_win, mgm_cv **out)

@@ -126,6 +126,8 @@ struct Opts {
     float P1, P2, aP2, aThresh, truncDist;
     std::string distance, prefilter, refine;
     int TSGM, FH, FIX, census_win;
+    int subpix = 1;                      // MGM_SUBPIX: labels per pixel of disparity, 1 (off), 2 or 4
+    std::string subpix_interp = "cubic"; // MGM_SUBPIX_INTERP: linear or cubic
 };
 
 // A device-side failure: thrown, never exit() -- in resident mode the job fails and the next one runs.
@@ -149,6 +151,7 @@ struct Run {
     mgm_cv *C = nullptr;
     bool weighted_msg = false, borrowed_uv = false, ragged = false;
     int nx = 0, ny = 0, nch = 0, vnx = 0, vny = 0, dmin = 0, dmax = 0;  // (what the kept objects were made for)
+    int subpix = 1;  // ... and the label spacing of C: its labels are subpix * dmin .. subpix * dmax
 };
 
 static void free_run(mgm_ctx *ctx, Run &r)
@@ -201,10 +204,11 @@ static void prepare_run(mgm_ctx *ctx, const HostImg &u, const HostImg &v, int dm
             dmax = std::max(dmax, (int)hi->data[i]);
         }
     const bool keep = r.C && !r.ragged && !ragged && r.nx == u.nx && r.ny == u.ny && r.nch == u.nch && r.vnx == v.nx && r.vny == v.ny &&
-                      r.dmin == dmin && r.dmax == dmax && r.borrowed_uv == (uv_from != nullptr);
+                      r.dmin == dmin && r.dmax == dmax && r.subpix == o.subpix && r.borrowed_uv == (uv_from != nullptr);
     if (!keep) free_run(ctx, r);
     r.nx = u.nx, r.ny = u.ny, r.nch = u.nch, r.vnx = v.nx, r.vny = v.ny, r.dmin = dmin, r.dmax = dmax, r.ragged = ragged;
     r.weighted_msg = false;
+    r.subpix = o.subpix;
     if (uv_from) {
         r.du = uv_from->dv;
         r.dv = uv_from->du;
@@ -237,6 +241,10 @@ static void prepare_run(mgm_ctx *ctx, const HostImg &u, const HostImg &v, int dm
         mgm_img_free(ctx, dlo);
         mgm_img_free(ctx, dhi);
         if (rc) die(ctx, rc, "mgm_costvolume_build_ranged");
+    } else if (o.subpix > 1) {  // MGM_SUBPIX: the fine volume, labels subpix * dmin .. subpix * dmax (never with range images)
+        if ((rc = mgm_costvolume_build_subpix_dev(ctx, r.du, r.dv, dmin, dmax, o.subpix, o.subpix_interp.c_str(), o.prefilter.c_str(), o.distance.c_str(),
+                                                  o.truncDist, o.census_win, &r.C)))
+            die(ctx, rc, "mgm_costvolume_build_subpix");
     } else if ((rc = mgm_costvolume_build_dev(ctx, r.du, r.dv, dmin, dmax, o.prefilter.c_str(), o.distance.c_str(), o.truncDist, o.census_win, &r.C))) {
         die(ctx, rc, "mgm_costvolume_build");
     }
@@ -302,6 +310,13 @@ static HostImg download(mgm_ctx *ctx, const mgm_img *im, int nx, int ny, int nch
     const int rc = mgm_img_download(ctx, im, h.data.data());
     if (rc) die(ctx, rc, "download");
     return h;
+}
+
+// MGM_SUBPIX: a run's refined map from fine labels to pixels, in place, right after its search
+static void rescale_run(mgm_ctx *ctx, const Opts &o, Run &r)
+{
+    if (o.subpix <= 1) return;
+    if (int rc = mgm_subpix_scale_dev(ctx, r.dout, o.subpix, r.dout)) die(ctx, rc, "mgm_subpix_scale");
 }
 
 // outoff = median_filter(outoff, MEDIAN) on the device (mgm.cc:396, 419), any radius
@@ -479,6 +494,12 @@ static void parse_job(Job &j)
                         "              this rule, mismatches MGM_FILL_HOLES's; seclow / sechigh: the second lowest / second highest candidate -- the\n"
                         "              background's is sechigh for a range like -r -64 -R 0, seclow for positive disparities; needs the right view:\n"
                         "              TESTLRRL=0 leaves none, whatever MGM_RIGHT_FROM_LEFT is: exit code 2; the class map has no file option)\n"
+                        "             MGM_SUBPIX=1 (2 or 4: labels every half / quarter pixel -- both runs match against the other image shifted by\n"
+                        "              k/s pixels, MGM_SUBPIX_INTERP=cubic (Keys; or linear), and aggregate s*(dmax-dmin)+1 labels; each run's map is\n"
+                        "              divided by s right after its refinement, before MGM_UNIQUENESS, MEDIAN, the left-right test and the -l map, so\n"
+                        "              TESTLRRL_TAU, MGM_SPECKLE_DIFF, -r/-R and every output stay in pixels; -P1/-P2, -s and MGM_UNIQUENESS_RADIUS act\n"
+                        "              per FINE label: a slope of one pixel takes s steps of P1; not with -m/-M, -S > 1, TSGM_ITER != 1,\n"
+                        "              MGM_RIGHT_FROM_LEFT=1, several MGM_DEVICES, nor any other value: exit code 2)\n"
                         "             (with several MGM_DEVICES, -S / -m -M / TSGM_ITER > 1 run on the first device; in --batch mode a FIRST line\n"
                         "              of that kind brings up one device for the whole batch, a later one leaves the other lines their devices)\n"
                         "resident mode: mgm --batch FILE|-   (one such command line per line of FILE, one device context for all)");
@@ -540,6 +561,14 @@ static void parse_job(Job &j)
             return early(1, nullptr, "mgm: MGM_FILL_HOLES_OCC needs MGM_FILL_HOLES=median, min or max (the mismatches' rule)\n");
         j.fill_dirs = (int)nd;
         j.fill_dist = (int)dist;
+    }
+    {  // MGM_SUBPIX / MGM_SUBPIX_INTERP (as strict; exit code 2)
+        const char *sp = getenv("MGM_SUBPIX"), *si = getenv("MGM_SUBPIX_INTERP");
+        const std::string v = sp ? sp : "1", ip = si ? si : "cubic";
+        if (!(v == "1" || v == "2" || v == "4")) return early(2, nullptr, "mgm: MGM_SUBPIX must be 1 (off), 2 or 4\n");
+        if (!(ip == "linear" || ip == "cubic")) return early(2, nullptr, "mgm: MGM_SUBPIX_INTERP must be linear or cubic\n");
+        o.subpix = v[0] - '0';
+        o.subpix_interp = ip;
     }
     if (j.nscales < 1 || j.nscales > 8) return early(1, nullptr, "mgm: -S nscales must be 1..8\n");
     if (argc > 1) j.f_u = argv[1];
@@ -752,6 +781,19 @@ static int device_job(Session &S, Job &j, const std::function<void()> &decoded, 
             return 2;
         }
     }
+    // MGM_SUBPIX=2|4 (this program's own mode): both runs on fine volumes, their maps rescaled to pixels
+    if (o.subpix > 1) {
+        const char *why = nullptr;
+        if (ranged) why = "range images (-m/-M)";
+        else if (j.nscales > 1) why = "-S > 1";
+        else if (ITER != 1) why = "TSGM_ITER != 1";
+        else if (rfl) why = "MGM_RIGHT_FROM_LEFT=1";
+        else if (getenv("MGM_DEVICES") && strchr(getenv("MGM_DEVICES"), ',')) why = "several MGM_DEVICES";
+        if (why) {
+            fprintf(stderr, "mgm: MGM_SUBPIX does not combine with %s\n", why);
+            return 2;
+        }
+    }
     // MGM_FILL_HOLES_OCC: the classification reads the right map that entered the left-right test
     if (!j.fill_occ.empty() && TESTLRRL == 0) {
         fprintf(stderr, "mgm: MGM_FILL_HOLES_OCC needs the right view: TESTLRRL=0 leaves none (MGM_RIGHT_FROM_LEFT takes effect only with TESTLRRL != 0)\n");
@@ -788,6 +830,10 @@ static int device_job(Session &S, Job &j, const std::function<void()> &decoded, 
         }
         if (uq && multi) {  // (resident mode: an earlier line brought several devices up)
             fprintf(stderr, "mgm: -c / MGM_UNIQUENESS does not combine with several MGM_DEVICES\n");
+            return 2;
+        }
+        if (o.subpix > 1 && multi) {  // (resident mode: an earlier line brought several devices up)
+            fprintf(stderr, "mgm: MGM_SUBPIX does not combine with several MGM_DEVICES\n");
             return 2;
         }
         if (rfl && u.ny != v.ny) {
@@ -856,6 +902,7 @@ static int device_job(Session &S, Job &j, const std::function<void()> &decoded, 
             else if (!together) aggregate_run(ctx, o, L);
             report_run(o, L);
             iterate_run(ctx, o, L, ITER, o.dmin, o.dmax, plo, phi);
+            rescale_run(ctx, o, L);
             if (uq) uniqueness_run(ctx, o, L, (float)j.uniq, j.uniq_radius, j.conf_file.empty() ? nullptr : &dconf.im);
         }
         if (MEDIAN != 0) median_run(ctx, L, (int)MEDIAN);
@@ -879,6 +926,7 @@ static int device_job(Session &S, Job &j, const std::function<void()> &decoded, 
                 else if (!together) aggregate_run(ctx, o, R);
                 report_run(o, R);
                 iterate_run(ctx, o, R, ITER, -o.dmax, -o.dmin);
+                rescale_run(ctx, o, R);
                 if (j.uniq != 0) uniqueness_run(ctx, o, R, (float)j.uniq, j.uniq_radius, nullptr);
             }
             if (MEDIAN != 0) median_run(ctx, R, (int)MEDIAN);
