@@ -95,7 +95,7 @@ def build_cli(force=False):
     """The host program: src/mgm_main.cc (plain g++) linked against libmgm_hip.so -> mgm_amd/bin/mgm."""
     src = os.path.join(HERE, "..", "src", "mgm_main.cc")
     hdrs = [os.path.join(HERE, "..", "src", "npyio.h"), os.path.join(HERE, "..", "src", "imgio.h"),
-            os.path.join(HERE, "..", "include", "mgm_hip.h")]
+            os.path.join(HERE, "..", "include", "mgm_hip.h"), os.path.join(HERE, "..", "src", "mgm_jobplan.h")]
     exe = os.path.join(HERE, "bin", "mgm")
     os.makedirs(os.path.dirname(exe), exist_ok=True)
     if force or _stale(exe, [src, LIB] + hdrs):

@@ -46,10 +46,15 @@
 
 #include "../include/mgm_hip.h"
 #include "imgio.h"
+#include "mgm_jobplan.h"
+
+using mgm_cli::JobPlan;
+using mgm_cli::Opts;
 
 // ---- MGM_HIP_STATS=1: where the wall time of the run goes (stderr, one line) ------------------
 struct Stopwatch {
-    bool on = getenv("MGM_HIP_STATS") && atoi(getenv("MGM_HIP_STATS")) != 0;
+    bool on;
+    explicit Stopwatch(const JobPlan &p) : on(p.stats) {}
     std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now(), last = t0;
     std::string line;
     void mark(const char *what)
@@ -93,42 +98,11 @@ struct Stopwatch {
     }
 };
 
-// ---- environment "smart parameters" (smartparameter.h:26-50): double, read once --------------
-static double env_param(const char *name, double dflt)
-{
-    const char *s = getenv(name);
-    double y;
-    if (s && sscanf(s, "%lf", &y) == 1) return y;
-    return dflt;
-}
-
-// ---- pick_option (mgm.cc:165-179): single-dash name, value = next argv, both removed ----------
-static const char *pick_option(int *argc, char **argv, const char *opt, const char *dflt)
-{
-    for (int i = 0; i < *argc - 1; i++)
-        if (argv[i][0] == '-' && 0 == strcmp(argv[i] + 1, opt)) {
-            const char *r = argv[i + 1];
-            *argc -= 2;
-            for (int j = i; j < *argc; j++) argv[j] = argv[j + 2];
-            return r;
-        }
-    return dflt;
-}
-
 static void remove_nonfinite(HostImg &u, float v)  // img_tools.h:37-41
 {
     for (float &x : u.data)
         if (!std::isfinite(x)) x = v;
 }
-
-struct Opts {
-    int dmin, dmax, NDIR;
-    float P1, P2, aP2, aThresh, truncDist;
-    std::string distance, prefilter, refine;
-    int TSGM, FH, FIX, census_win;
-    int subpix = 1;                      // MGM_SUBPIX: labels per pixel of disparity, 1 (off), 2 or 4
-    std::string subpix_interp = "cubic"; // MGM_SUBPIX_INTERP: linear or cubic
-};
 
 // A device-side failure: thrown, never exit() -- in resident mode the job fails and the next one runs.
 // code(): the process exit code of a one-shot run (2: valid in the reference, refused here).
@@ -164,6 +138,12 @@ static void free_run(mgm_ctx *ctx, Run &r)
     for (mgm_img *im : {r.dw, r.dout, r.dcost, r.dspare}) mgm_img_free(ctx, im);
     r = Run();
 }
+
+struct ImgHold {  // a device image freed with its scope (several in one declaration: the last one first)
+    mgm_ctx *ctx;
+    mgm_img *im = nullptr;
+    ~ImgHold() { mgm_img_free(ctx, im); }
+};
 
 // the device image of `h`: a kept one of the same size refilled, else a new one
 static void upload_into(mgm_ctx *ctx, const HostImg &h, mgm_img **im)
@@ -231,16 +211,12 @@ static void prepare_run(mgm_ctx *ctx, const HostImg &u, const HostImg &v, int dm
         r.dw = nullptr;
     }
     if (ragged) {
-        mgm_img *dlo = nullptr, *dhi = nullptr;
-        if ((rc = mgm_img_upload(ctx, lo->data.data(), u.nx, u.ny, 1, &dlo)) || (rc = mgm_img_upload(ctx, hi->data.data(), u.nx, u.ny, 1, &dhi))) {
-            mgm_img_free(ctx, dlo);
+        ImgHold dhi{ctx}, dlo{ctx};
+        if ((rc = mgm_img_upload(ctx, lo->data.data(), u.nx, u.ny, 1, &dlo.im)) || (rc = mgm_img_upload(ctx, hi->data.data(), u.nx, u.ny, 1, &dhi.im)))
             die(ctx, rc, "upload");
-        }
-        rc = mgm_costvolume_build_ranged_dev(ctx, r.du, r.dv, dlo, dhi, dmin, dmax, o.prefilter.c_str(), o.distance.c_str(), o.truncDist,
-                                             o.census_win, &r.C);
-        mgm_img_free(ctx, dlo);
-        mgm_img_free(ctx, dhi);
-        if (rc) die(ctx, rc, "mgm_costvolume_build_ranged");
+        if ((rc = mgm_costvolume_build_ranged_dev(ctx, r.du, r.dv, dlo.im, dhi.im, dmin, dmax, o.prefilter.c_str(), o.distance.c_str(), o.truncDist,
+                                                  o.census_win, &r.C)))
+            die(ctx, rc, "mgm_costvolume_build_ranged");
     } else if (o.subpix > 1) {  // MGM_SUBPIX: the fine volume, labels subpix * dmin .. subpix * dmax (never with range images)
         if ((rc = mgm_costvolume_build_subpix_dev(ctx, r.du, r.dv, dmin, dmax, o.subpix, o.subpix_interp.c_str(), o.prefilter.c_str(), o.distance.c_str(),
                                                   o.truncDist, o.census_win, &r.C)))
@@ -328,12 +304,6 @@ static void median_run(mgm_ctx *ctx, Run &r, int radius)
     std::swap(r.dout, r.dspare);
 }
 
-struct ImgHold {  // a device image freed with its scope
-    mgm_ctx *ctx;
-    mgm_img *im = nullptr;
-    ~ImgHold() { mgm_img_free(ctx, im); }
-};
-
 // -c / MGM_UNIQUENESS, right behind the aggregation of `r`: the runner-up search over the Lr volumes the context
 // still holds of that run, then conf = 1 - cost1 / cost2 into *conf (if wanted) and, with ratio != 0, NaN into the run's
 // (refined) map wherever conf < ratio
@@ -385,27 +355,14 @@ static void iterate_run(mgm_ctx *ctx, const Opts &o, Run &r, int iterations, int
         lo = lo0->data;
         hi = hi0->data;
     }
-    mgm_img *dlo = nullptr, *dhi = nullptr;
+    ImgHold dhi{ctx}, dlo{ctx};
     int rc;
-    if ((rc = mgm_img_upload(ctx, lo.data(), r.nx, r.ny, 1, &dlo)) || (rc = mgm_img_upload(ctx, hi.data(), r.nx, r.ny, 1, &dhi))) {
-        mgm_img_free(ctx, dlo);
-        die(ctx, rc, "upload");
-    }
+    if ((rc = mgm_img_upload(ctx, lo.data(), r.nx, r.ny, 1, &dlo.im)) || (rc = mgm_img_upload(ctx, hi.data(), r.nx, r.ny, 1, &dhi.im))) die(ctx, rc, "upload");
     for (int it = 1; it < iterations; it++) {
-        const char *what = "mgm_update_ranges";
-        if (!(rc = mgm_update_ranges_dev(ctx, r.dout, dlo, dhi, 3, 2))) {
-            what = "mgm_wta_windowed";
-            rc = mgm_wta_windowed_dev(ctx, r.C, o.NDIR, o.FIX, o.refine.c_str(), dlo, dhi, r.dout, r.dcost);
-        }
-        if (rc) {
-            mgm_img_free(ctx, dlo);
-            mgm_img_free(ctx, dhi);
-            die(ctx, rc, what);
-        }
+        if ((rc = mgm_update_ranges_dev(ctx, r.dout, dlo.im, dhi.im, 3, 2))) die(ctx, rc, "mgm_update_ranges");
+        if ((rc = mgm_wta_windowed_dev(ctx, r.C, o.NDIR, o.FIX, o.refine.c_str(), dlo.im, dhi.im, r.dout, r.dcost))) die(ctx, rc, "mgm_wta_windowed");
         report_run(o, r);
     }
-    mgm_img_free(ctx, dlo);
-    mgm_img_free(ctx, dhi);
 }
 
 // The device side of the process: created for the first job, kept for the following ones (resident mode) together with
@@ -422,22 +379,7 @@ struct Session {
 // ---- a job ------------------------------------------------------------------------------------------------------------
 struct Job {
     std::vector<std::string> tok;  // the command line (argv[0] included)
-    // parsed
-    Opts o{};
-    std::string min_file, max_file, nolr_file, f_u, f_v, f_out, f_cost, f_back;
-    int nscales = 1;          // -S: levels of the coarse-to-fine driver (1: the single-scale path)
-    std::string conf_file;    // -c: the left->right run's confidence map
-    double uniq = 0;          // MGM_UNIQUENESS: the uniqueness filter's ratio (0: off)
-    int uniq_radius = 1;      // MGM_UNIQUENESS_RADIUS: labels around the winner the runner-up stays away from
-    int speckle = 0;          // MGM_SPECKLE: components of the final left map of at most this many pixels go (0: off)
-    float speckle_diff = 1;   // MGM_SPECKLE_DIFF: neighbours are joined up to this difference
-    std::string fill;         // MGM_FILL_HOLES: median, min or max -- the final left map's holes are filled (empty: off)
-    int fill_dirs = 8;        // MGM_FILL_HOLES_DIRS: 2, 4 or 8 rays
-    int fill_dist = 0;        // MGM_FILL_HOLES_DIST: a candidate is at most this many steps away (0: no limit)
-    std::string fill_occ;     // MGM_FILL_HOLES_OCC: the occlusions' rule -- the holes are classified, `fill` is the mismatches' (empty: off)
-    int early = -1;           // >= 0: the command line ends before any work with this code ...
-    std::string early_out;    // ... after these lines on stdout
-    std::string early_err;    // ... and stderr
+    JobPlan p;                     // what it is going to do (mgm_jobplan.h)
     // decoded
     HostImg u, v, rlo, rhi;
     std::exception_ptr decode_err;
@@ -446,161 +388,34 @@ struct Job {
     int rc = 0;  // the job's exit code
 };
 
-static void parse_job(Job &j)
+// a job whose plan is to end before any work: its texts, its code
+static bool ends_early(Job &j)
 {
-    std::vector<char *> av;
-    for (auto &t : j.tok) av.push_back(&t[0]);
-    av.push_back(nullptr);
-    int argc = (int)j.tok.size();
-    char **argv = av.data();
-    auto early = [&](int code, const char *out, const std::string &err = "") {
-        j.early = code;
-        if (out) j.early_out = std::string(out) + "\n";
-        j.early_err = err;
-    };
-    if (argc < 2 || !strcmp(argv[1], "-h")) return early(0, "usage:\n\tmgm [-options] u v out [cost [backflow]]");
-    if (!strcmp(argv[1], "-?")) return early(0, "Compute stereo disparities by the MGM algorithm.");
-    if (!strcmp(argv[1], "--version")) return early(0, "mgm 2.0 (mgm-hip, MI355X)");
-    if (!strcmp(argv[1], "--help"))
-        return early(0, "mgm [options] in_u in_v out_disp [out_cost [out_backflow]]   (in: png tif pgm ppm pfm npy; out: tif pfm npy)\n"
-                        "options: -r dmin(-30) -R dmax(30) -O NDIR(4) -P1 (8) -P2 (32) -p prefilter(none) -t distance(ad)\n"
-                        "         -truncDist (inf) -s subpix(none) -aP1 (1) -aP2 (1) -aThresh (5) -m FILE -M FILE -l FILE\n"
-                        "         -S nscales(1): coarse to fine over up to 8 half-size levels (this program's own mode, not the reference's)\n"
-                        "         -c FILE: the left->right run's confidence map, 1 - cost1/cost2 of the winner and the runner-up (own mode)\n"
-                        "environment: CENSUS_NCC_WIN=3 TESTLRRL=1 TESTLRRL_TAU=1.0 MEDIAN=0 TSGM=4 TSGM_ITER=1\n"
-                        "             TSGM_FIX_OVERCOUNT=1 USE_TRUNCATED_LINEAR_POTENTIALS=0 MGM_DEVICE=0 MGM_DEVICES=0,1,...\n"
-                        "             MGM_MS_SLACK=3 MGM_MS_RADIUS=2 (-S: window around the coarser level's disparities)\n"
-                        "             MGM_RIGHT_FROM_LEFT=0 (1, with TESTLRRL != 0: no right->left run; the right map is read out of the left run's\n"
-                        "              aggregated volume along its diagonals, and stdout has the line `right from left` in place of that run's\n"
-                        "              lines; not with -m/-M, -S > 1, TSGM_ITER != 1, several MGM_DEVICES, -s parabola|cubic|parabolaOCV: exit code 2)\n"
-                        "             MGM_UNIQUENESS=0 (r in (0,1]: each run's map is NaN where 1 - cost1/cost2 < r, cost2 the aggregated cost of the\n"
-                        "              best label more than MGM_UNIQUENESS_RADIUS=1 away from the winner; applied right after the run's refinement,\n"
-                        "              before MEDIAN, the left-right test and the -l map; with MGM_RIGHT_FROM_LEFT=1 only the left map is filtered:\n"
-                        "              the right view has no runner-up; -c and MGM_UNIQUENESS not with -m/-M, -S > 1, TSGM_ITER != 1, several\n"
-                        "              MGM_DEVICES: exit code 2)\n"
-                        "             MGM_SPECKLE=0 (n > 0: the speckle filter -- every 4-connected component of finite pixels of the final left map,\n"
-                        "              neighbours joined where they differ by at most MGM_SPECKLE_DIFF=1, that has at most n pixels becomes NaN; runs\n"
-                        "              last but for MGM_FILL_HOLES, after MEDIAN and the left-right test and before the back-projected image, with -S\n"
-                        "              on the full-size map only; leaves the -l map, the cost map and stdout as they are; combines with every other mode)\n"
-                        "             MGM_FILL_HOLES=none (median, min or max: hole filling -- every non-finite pixel of the final left map takes the\n"
-                        "              median (the upper one) / minimum / maximum of the nearest finite pixels along the first MGM_FILL_HOLES_DIRS=8\n"
-                        "              (2, 4 or 8) of the rays (+1,0) (-1,0) (0,+1) (0,-1) (+1,+1) (-1,+1) (+1,-1) (-1,-1), each at most\n"
-                        "              MGM_FILL_HOLES_DIST=0 steps away (0: no limit); rays read the unfilled map; a hole that no ray serves stays;\n"
-                        "              runs last, after MGM_SPECKLE, and before the back-projected image, with -S on the full-size map only; leaves\n"
-                        "              the -l map, the cost map, -c's map and stdout as they are; combines with every other mode)\n"
-                        "             MGM_FILL_HOLES_OCC=none (seclow, sechigh, min, max or median, with MGM_FILL_HOLES: the holes are classified first --\n"
-                        "              a hole (x,y) is a mismatch when a pixel xr of the right map as it entered the left-right test, x+dmin <= xr <=\n"
-                        "              x+dmax of -r/-R, lands within TESTLRRL_TAU of it, |xr + right(xr,y) - x| <= tau, else an occlusion; occlusions take\n"
-                        "              this rule, mismatches MGM_FILL_HOLES's; seclow / sechigh: the second lowest / second highest candidate -- the\n"
-                        "              background's is sechigh for a range like -r -64 -R 0, seclow for positive disparities; needs the right view:\n"
-                        "              TESTLRRL=0 leaves none, whatever MGM_RIGHT_FROM_LEFT is: exit code 2; the class map has no file option)\n"
-                        "             MGM_SUBPIX=1 (2 or 4: labels every half / quarter pixel -- both runs match against the other image shifted by\n"
-                        "              k/s pixels, MGM_SUBPIX_INTERP=cubic (Keys; or linear), and aggregate s*(dmax-dmin)+1 labels; each run's map is\n"
-                        "              divided by s right after its refinement, before MGM_UNIQUENESS, MEDIAN, the left-right test and the -l map, so\n"
-                        "              TESTLRRL_TAU, MGM_SPECKLE_DIFF, -r/-R and every output stay in pixels; -P1/-P2, -s and MGM_UNIQUENESS_RADIUS act\n"
-                        "              per FINE label: a slope of one pixel takes s steps of P1; not with -m/-M, -S > 1, TSGM_ITER != 1,\n"
-                        "              MGM_RIGHT_FROM_LEFT=1, several MGM_DEVICES, nor any other value: exit code 2)\n"
-                        "             (with several MGM_DEVICES, -S / -m -M / TSGM_ITER > 1 run on the first device; in --batch mode a FIRST line\n"
-                        "              of that kind brings up one device for the whole batch, a later one leaves the other lines their devices)\n"
-                        "resident mode: mgm --batch FILE|-   (one such command line per line of FILE, one device context for all)");
-    if (argc < 4)
-        return early(1, nullptr, std::string("too few parameters\n   usage: ") + argv[0] +
-                                     "  [-r dmin -R dmax] [-m dminImg -M dmaxImg] [-O NDIR: 2, (4), 8] u v out [cost [backflow]]\n");
-    // mgm.cc:303-318, in the same order (the order matters for pick_option's argv surgery)
-    j.min_file = pick_option(&argc, argv, "m", "");
-    j.max_file = pick_option(&argc, argv, "M", "");
-    Opts &o = j.o;
-    o.dmin = atoi(pick_option(&argc, argv, "r", "-30"));
-    o.dmax = atoi(pick_option(&argc, argv, "R", "30"));
-    o.NDIR = atoi(pick_option(&argc, argv, "O", "4"));
-    o.P1 = (float)atof(pick_option(&argc, argv, "P1", "8"));
-    o.P2 = (float)atof(pick_option(&argc, argv, "P2", "32"));
-    pick_option(&argc, argv, "aP1", "1");  // accepted and unused, as in the reference
-    o.aP2 = (float)atof(pick_option(&argc, argv, "aP2", "1"));
-    o.aThresh = (float)atof(pick_option(&argc, argv, "aThresh", "5"));
-    o.distance = pick_option(&argc, argv, "t", "ad");
-    o.prefilter = pick_option(&argc, argv, "p", "none");
-    o.refine = pick_option(&argc, argv, "s", "none");
-    o.truncDist = (float)atof(pick_option(&argc, argv, "truncDist", "inf"));
-    j.nolr_file = pick_option(&argc, argv, "l", "");
-    j.nscales = atoi(pick_option(&argc, argv, "S", "1"));
-    j.conf_file = pick_option(&argc, argv, "c", "");
-    j.uniq = env_param("MGM_UNIQUENESS", 0);
-    j.uniq_radius = (int)env_param("MGM_UNIQUENESS_RADIUS", 1);
-    if (!(j.uniq >= 0 && j.uniq <= 1)) return early(1, nullptr, "mgm: MGM_UNIQUENESS must be a ratio in [0, 1]\n");
-    if (j.uniq_radius < 0) return early(1, nullptr, "mgm: MGM_UNIQUENESS_RADIUS must be >= 0\n");
-    {  // (strict: a value that is no number is refused, not replaced by the default)
-        const char *sn = getenv("MGM_SPECKLE"), *sd = getenv("MGM_SPECKLE_DIFF");
-        char *end = nullptr;
-        const double n = sn ? strtod(sn, &end) : 0;
-        if (sn && (end == sn || *end || !(n >= 0 && n <= 2147483647.0) || n != std::floor(n)))
-            return early(1, nullptr, "mgm: MGM_SPECKLE must be an integer >= 0 (pixels)\n");
-        const double df = sd ? strtod(sd, &end) : 1;
-        if (sd && (end == sd || *end || !(df >= 0))) return early(1, nullptr, "mgm: MGM_SPECKLE_DIFF must be a number >= 0\n");
-        j.speckle = (int)n;
-        j.speckle_diff = (float)df;
-    }
-    {  // (as strict)
-        const char *fm = getenv("MGM_FILL_HOLES"), *fd = getenv("MGM_FILL_HOLES_DIRS"), *fl = getenv("MGM_FILL_HOLES_DIST");
-        const std::string m = fm ? fm : "";
-        if (!(m.empty() || m == "none" || m == "median" || m == "min" || m == "max"))
-            return early(1, nullptr, "mgm: MGM_FILL_HOLES must be median, min, max or none\n");
-        char *end = nullptr;
-        const double nd = fd ? strtod(fd, &end) : 8;
-        if (fd && (end == fd || *end || !(nd == 2 || nd == 4 || nd == 8))) return early(1, nullptr, "mgm: MGM_FILL_HOLES_DIRS must be 2, 4 or 8\n");
-        const double dist = fl ? strtod(fl, &end) : 0;
-        if (fl && (end == fl || *end || !(dist >= 0 && dist <= 2147483647.0) || dist != std::floor(dist)))
-            return early(1, nullptr, "mgm: MGM_FILL_HOLES_DIST must be an integer >= 0 (steps; 0: no limit)\n");
-        j.fill = m == "none" ? "" : m;
-        const char *fo = getenv("MGM_FILL_HOLES_OCC");
-        const std::string oc = fo ? fo : "";
-        if (!(oc.empty() || oc == "none" || oc == "seclow" || oc == "sechigh" || oc == "min" || oc == "max" || oc == "median"))
-            return early(1, nullptr, "mgm: MGM_FILL_HOLES_OCC must be seclow, sechigh, min, max, median or none\n");
-        j.fill_occ = oc == "none" ? "" : oc;
-        if (!j.fill_occ.empty() && j.fill.empty())
-            return early(1, nullptr, "mgm: MGM_FILL_HOLES_OCC needs MGM_FILL_HOLES=median, min or max (the mismatches' rule)\n");
-        j.fill_dirs = (int)nd;
-        j.fill_dist = (int)dist;
-    }
-    {  // MGM_SUBPIX / MGM_SUBPIX_INTERP (as strict; exit code 2)
-        const char *sp = getenv("MGM_SUBPIX"), *si = getenv("MGM_SUBPIX_INTERP");
-        const std::string v = sp ? sp : "1", ip = si ? si : "cubic";
-        if (!(v == "1" || v == "2" || v == "4")) return early(2, nullptr, "mgm: MGM_SUBPIX must be 1 (off), 2 or 4\n");
-        if (!(ip == "linear" || ip == "cubic")) return early(2, nullptr, "mgm: MGM_SUBPIX_INTERP must be linear or cubic\n");
-        o.subpix = v[0] - '0';
-        o.subpix_interp = ip;
-    }
-    if (j.nscales < 1 || j.nscales > 8) return early(1, nullptr, "mgm: -S nscales must be 1..8\n");
-    if (argc > 1) j.f_u = argv[1];
-    if (argc > 2) j.f_v = argv[2];
-    if (argc > 3) j.f_out = argv[3];
-    if (argc > 4) j.f_cost = argv[4];
-    if (argc > 5) j.f_back = argv[5];
-    if (argc < 4) return early(1, nullptr, "too few parameters\n");
-    o.TSGM = (int)env_param("TSGM", 4);
-    o.FH = (int)env_param("USE_TRUNCATED_LINEAR_POTENTIALS", 0);
-    o.FIX = (int)env_param("TSGM_FIX_OVERCOUNT", 1);
-    o.census_win = (int)env_param("CENSUS_NCC_WIN", 3);
+    if (j.p.outcome != JobPlan::END) return false;
+    fputs(j.p.out_text.c_str(), stdout);
+    fputs(j.p.err_text.c_str(), stderr);
+    j.rc = j.p.code;
+    return true;
 }
 
 // DECODE: the input files of a job (any thread; touches neither the device nor stdout).  Both images on their own threads.
 static void decode_job(Job &j)
 {
-    if (j.early >= 0) return;
+    if (j.p.outcome != JobPlan::RUN) return;
     std::exception_ptr eu, ev;
-    std::thread tv([&] { try { j.v = imgio::read(j.f_v); remove_nonfinite(j.v, 0); } catch (...) { ev = std::current_exception(); } });
+    std::thread tv([&] { try { j.v = imgio::read(j.p.f_v); remove_nonfinite(j.v, 0); } catch (...) { ev = std::current_exception(); } });
     try {
-        j.u = imgio::read(j.f_u);
+        j.u = imgio::read(j.p.f_u);
         remove_nonfinite(j.u, 0);
     } catch (...) {
         eu = std::current_exception();
     }
     tv.join();
     j.decode_err = eu ? eu : ev;
-    if (!j.decode_err && !j.min_file.empty()) {
+    if (!j.decode_err && j.p.ranged) {
         try {
-            j.rlo = imgio::read(j.min_file);
-            j.rhi = imgio::read(j.max_file);
+            j.rlo = imgio::read(j.p.min_file);
+            j.rhi = imgio::read(j.p.max_file);
         } catch (...) {
             j.decode_err = std::current_exception();
         }
@@ -610,131 +425,135 @@ static void decode_job(Job &j)
 // ENCODE: the output files of a job (any thread)
 static void encode_job(Job &j)
 {
-    if (j.early >= 0 || j.rc != 0) return;
+    if (j.p.outcome == JobPlan::END || j.rc != 0) return;
+    const JobPlan &p = j.p;
     try {
-        if (!j.nolr_file.empty()) imgio::write(j.nolr_file, j.nolr);
-        if (!j.conf_file.empty()) imgio::write(j.conf_file, j.conf);
-        imgio::write(j.f_out, j.outoff);
-        if (!j.f_cost.empty()) imgio::write(j.f_cost, j.outcost);
-        if (!j.f_back.empty()) imgio::write(j.f_back, j.syn);
+        if (!p.nolr_file.empty()) imgio::write(p.nolr_file, j.nolr);
+        if (!p.conf_file.empty()) imgio::write(p.conf_file, j.conf);
+        imgio::write(p.f_out, j.outoff);
+        if (!p.f_cost.empty()) imgio::write(p.f_cost, j.outcost);
+        if (!p.f_back.empty()) imgio::write(p.f_back, j.syn);
     } catch (const std::exception &e) {
         fprintf(stderr, "mgm: %s\n", e.what());
         j.rc = 1;
     }
 }
 
-static void bring_up(Session &S, int ITER, bool ranged, bool multiscale)
+static void bring_up(Session &S, const JobPlan &p)
 {
     if (S.tried) return;  // (resident mode: the first job brings the device side up, the others find it there)
     S.tried = true;
-    if (const char *dl = getenv("MGM_DEVICES"))  // "0,1,2,3": several GPUs of this node
-        for (const char *q = dl; *q;) {
-            char *end;
-            const long d = strtol(q, &end, 10);
-            if (end == q) break;
-            S.devs.push_back((int)d);
-            q = *end == ',' ? end + 1 : end;
-        }
-    if (S.devs.size() > 1 && (ITER > 1 || ranged)) {
+    S.devs = p.devices;
+    if (S.devs.size() > 1 && (p.iterations > 1 || p.ranged)) {
         fprintf(stderr, "mgm: MGM_DEVICES: TSGM_ITER > 1 and range images run on the first device only\n");
         S.devs.resize(1);
     }
-    if (S.devs.size() > 1 && multiscale) {
+    if (S.devs.size() > 1 && p.nscales > 1) {
         fprintf(stderr, "mgm: MGM_DEVICES: -S (coarse to fine) runs on the first device only\n");
         S.devs.resize(1);
     }
     if (S.devs.size() > 1) {
         if ((S.rc_ctx = mgm_multi_create(S.devs.data(), (int)S.devs.size(), &S.multi)) == 0) S.ctx = mgm_multi_ctx(S.multi, 0);
     } else {
-        S.rc_ctx = mgm_ctx_create(S.devs.size() == 1 ? S.devs[0] : (int)env_param("MGM_DEVICE", 0), &S.ctx);
+        S.rc_ctx = mgm_ctx_create(S.devs.size() == 1 ? S.devs[0] : p.device, &S.ctx);
         // MGM_PLACE_TRIES=n: a context that stays may try n physical placements of its workspace and keep the fastest (off by default: three
         // more allocations of a 34 GB workspace cost ~2 s, what 100 further pairs gain back)
-        if (S.rc_ctx == 0 && S.resident) (void)mgm_ctx_set_placement_tries(S.ctx, (int)env_param("MGM_PLACE_TRIES", 0));
-        if (S.rc_ctx == 0 && getenv("MGM_HIP_KERNELS") && atoi(getenv("MGM_HIP_KERNELS")) != 0) (void)mgm_timing_enable(S.ctx, 1);
+        if (S.rc_ctx == 0 && S.resident) (void)mgm_ctx_set_placement_tries(S.ctx, p.place_tries);
+        if (S.rc_ctx == 0 && p.kernels) (void)mgm_timing_enable(S.ctx, 1);
     }
 }
 
 // MGM_HIP_KERNELS=1: which kernels the job ran, in launch order, on stderr (tests assert which pass kernel a command line took)
-static void report_kernels(mgm_ctx *ctx, mgm_multi *multi)
+static void report_kernels(mgm_ctx *ctx)
 {
-    if (getenv("MGM_HIP_KERNELS") && atoi(getenv("MGM_HIP_KERNELS")) != 0 && !multi) {
-        const int n = mgm_timing_count(ctx);
-        fprintf(stderr, "[mgm kernels]");
-        for (int k = 0; k < n; k++) {
-            const char *name = nullptr;
-            float ms = 0;
-            if (mgm_timing_get(ctx, k, &name, &ms) == 0 && name) fprintf(stderr, " %s", name);
-        }
-        fprintf(stderr, "\n");
-        (void)mgm_timing_reset(ctx);
+    const int n = mgm_timing_count(ctx);
+    fprintf(stderr, "[mgm kernels]");
+    for (int k = 0; k < n; k++) {
+        const char *name = nullptr;
+        float ms = 0;
+        if (mgm_timing_get(ctx, k, &name, &ms) == 0 && name) fprintf(stderr, " %s", name);
+    }
+    fprintf(stderr, "\n");
+    (void)mgm_timing_reset(ctx);
+}
+
+// The end of every job, on its final left map `out`: MGM_SPECKLE, then MGM_FILL_HOLES (7e; with MGM_FILL_HOLES_OCC
+// classified from `right_nolr`, the right map as it entered the left-right test, 7f) -- after every rejection step, before the
+// back-projected image is made --, then the downloads: the map, the cost map, -c's map, the back-projected image (mgm.cc:433-443)
+// of du and dv.  `between`: what the caller does after the last kernel is enqueued and before the first download.
+static void finish_job(mgm_ctx *ctx, Job &j, mgm_img *out, const mgm_img *right_nolr, const mgm_img *cost, const mgm_img *conf, const mgm_img *du,
+                       const mgm_img *dv, Stopwatch &sw, const std::function<void()> &between)
+{
+    const JobPlan &p = j.p;
+    const HostImg &u = j.u;
+    if (p.speckle > 0) speckle_map(ctx, out, p.speckle, p.speckle_diff);
+    if (!p.fill_occ.empty()) fill_holes_classified_map(ctx, out, right_nolr, p.o.dmin, p.o.dmax, p.tau, p.fill_occ, p.fill, p.fill_dirs, p.fill_dist);
+    else if (!p.fill.empty()) fill_holes_map(ctx, out, p.fill, p.fill_dirs, p.fill_dist);
+    between();
+    j.outoff = download(ctx, out, u.nx, u.ny, 1);
+    sw.mark("device+download");
+    if (!p.f_cost.empty()) j.outcost = download(ctx, cost, u.nx, u.ny, 1);
+    if (conf) j.conf = download(ctx, conf, u.nx, u.ny, 1);
+    if (!p.f_back.empty()) {
+        ImgHold syn{ctx};
+        int rc;
+        if ((rc = mgm_img_create(ctx, u.nx, u.ny, u.nch, &syn.im))) die(ctx, rc, "mgm_img_create");
+        if ((rc = mgm_backproject_dev(ctx, du, dv, out, syn.im))) die(ctx, rc, "mgm_backproject");
+        j.syn = download(ctx, syn.im, u.nx, u.ny, u.nch);
     }
 }
 
 // -S nscales > 1: the pair coarse to fine (mgm_multiscale_pair_dev; DESIGN.md "multiscale" -- this program's own mode, the
 // reference has none).  stdout: level by level from the coarsest, the lines a single-scale job prints for that level.  The
 // nolr map, the cost map and the back-projected image refer to the full-size level.  Device objects are this job's own.
-static void multiscale_job(Session &S, Job &j, const Opts &o, const HostImg *plo, const HostImg *phi, int ITER, bool both, float tau,
-                           int median, Stopwatch &sw)
+// `o`: the job's options with the penalties scaled by the number of channels.
+static void multiscale_job(Session &S, Job &j, const Opts &o, const HostImg *plo, const HostImg *phi, Stopwatch &sw)
 {
     mgm_ctx *ctx = S.ctx;
+    const JobPlan &pl = j.p;
     free_run(ctx, S.R);  // (kept from an earlier single-scale pair)
     free_run(ctx, S.L);
     const HostImg &u = j.u, &v = j.v;
-    struct Objs {
-        mgm_ctx *ctx;
-        mgm_img *du = nullptr, *dv = nullptr, *dlo = nullptr, *dhi = nullptr, *out = nullptr, *cost = nullptr, *nolr = nullptr, *syn = nullptr;
-        mgm_img *rnolr = nullptr;  // MGM_FILL_HOLES_OCC: the full-size right map before its left-right test
-        ~Objs()
-        {
-            for (mgm_img *im : {du, dv, dlo, dhi, out, cost, nolr, syn, rnolr}) mgm_img_free(ctx, im);
-        }
-    } d{ctx};
+    // (rnolr -- MGM_FILL_HOLES_OCC: the full-size right map before its left-right test)
+    ImgHold rnolr{ctx}, nolr{ctx}, cost{ctx}, out{ctx}, dhi{ctx}, dlo{ctx}, dv{ctx}, du{ctx};
     int rc;
-    if ((rc = mgm_img_upload(ctx, u.data.data(), u.nx, u.ny, u.nch, &d.du)) || (rc = mgm_img_upload(ctx, v.data.data(), v.nx, v.ny, v.nch, &d.dv)))
+    if ((rc = mgm_img_upload(ctx, u.data.data(), u.nx, u.ny, u.nch, &du.im)) || (rc = mgm_img_upload(ctx, v.data.data(), v.nx, v.ny, v.nch, &dv.im)))
         die(ctx, rc, "upload");
-    if (plo && ((rc = mgm_img_upload(ctx, plo->data.data(), u.nx, u.ny, 1, &d.dlo)) || (rc = mgm_img_upload(ctx, phi->data.data(), u.nx, u.ny, 1, &d.dhi))))
+    if (plo && ((rc = mgm_img_upload(ctx, plo->data.data(), u.nx, u.ny, 1, &dlo.im)) || (rc = mgm_img_upload(ctx, phi->data.data(), u.nx, u.ny, 1, &dhi.im))))
         die(ctx, rc, "upload");
-    for (mgm_img **im : {&d.out, &d.cost}) image_like(ctx, u.nx, u.ny, 1, im);
-    if (!j.nolr_file.empty()) image_like(ctx, u.nx, u.ny, 1, &d.nolr);
-    if (!j.fill_occ.empty()) image_like(ctx, v.nx, v.ny, 1, &d.rnolr);
+    for (mgm_img **im : {&out.im, &cost.im}) image_like(ctx, u.nx, u.ny, 1, im);
+    if (!pl.nolr_file.empty()) image_like(ctx, u.nx, u.ny, 1, &nolr.im);
+    if (!pl.fill_occ.empty()) image_like(ctx, v.nx, v.ny, 1, &rnolr.im);
     mgm_ms_level levels[8] = {};
     int nlev = 0;
     mgm_ms_params p{};
     p.struct_size = sizeof p;
-    p.nscales = j.nscales;
-    p.slack = (int)env_param("MGM_MS_SLACK", 3);
-    p.radius = (int)env_param("MGM_MS_RADIUS", 2);
+    p.nscales = pl.nscales;
+    p.slack = pl.ms_slack;
+    p.radius = pl.ms_radius;
     p.dmin = o.dmin, p.dmax = o.dmax;
-    p.lo = d.dlo, p.hi = d.dhi;
+    p.lo = dlo.im, p.hi = dhi.im;
     p.P1 = o.P1, p.P2 = o.P2, p.NDIR = o.NDIR, p.TSGM = o.TSGM, p.use_fh = o.FH, p.fix_overcount = o.FIX;
     p.aP2 = o.aP2, p.aThresh = o.aThresh;
     p.prefilter = o.prefilter.c_str(), p.distance = o.distance.c_str(), p.truncDist = o.truncDist, p.census_win = o.census_win;
     p.refine = o.refine.c_str();
-    p.iterations = ITER, p.median = median, p.testlrrl = both, p.tau = tau;
+    p.iterations = pl.iterations, p.median = (int)pl.median, p.testlrrl = pl.both, p.tau = pl.tau;
     p.levels_run = &nlev, p.levels = levels;
-    p.outR_nolr = d.rnolr;
+    p.outR_nolr = rnolr.im;
     sw.mark("upload");
-    if ((rc = mgm_multiscale_pair_dev(ctx, d.du, d.dv, &p, d.out, d.cost, nullptr, nullptr, d.nolr))) die(ctx, rc, "mgm_multiscale_pair");
+    if ((rc = mgm_multiscale_pair_dev(ctx, du.im, dv.im, &p, out.im, cost.im, nullptr, nullptr, nolr.im))) die(ctx, rc, "mgm_multiscale_pair");
     for (int s = nlev - 1; s >= 0; s--)
-        for (int k = 0; k < (both ? 2 : 1); k++)
-            for (int it = 0; it < ITER; it++) {
+        for (int k = 0; k < (pl.both ? 2 : 1); k++)
+            for (int it = 0; it < pl.iterations; it++) {
                 Run r;
                 r.weighted_msg = levels[s].weighted[k] != 0;
                 report_run(o, r);
             }
     sw.mark("enqueue");
-    if (j.speckle > 0) speckle_map(ctx, d.out, j.speckle, j.speckle_diff);  // once, on level 0's final map
-    if (!j.fill_occ.empty()) fill_holes_classified_map(ctx, d.out, d.rnolr, o.dmin, o.dmax, tau, j.fill_occ, j.fill, j.fill_dirs, j.fill_dist);
-    else if (!j.fill.empty()) fill_holes_map(ctx, d.out, j.fill, j.fill_dirs, j.fill_dist);  // ... and after it
-    if (!j.nolr_file.empty()) j.nolr = download(ctx, d.nolr, u.nx, u.ny, 1);
-    j.outoff = download(ctx, d.out, u.nx, u.ny, 1);
-    sw.mark("device+download");
-    if (!j.f_cost.empty()) j.outcost = download(ctx, d.cost, u.nx, u.ny, 1);
-    if (!j.f_back.empty()) {  // back-projected image (mgm.cc:433-443)
-        image_like(ctx, u.nx, u.ny, u.nch, &d.syn);
-        if ((rc = mgm_backproject_dev(ctx, d.du, d.dv, d.out, d.syn))) die(ctx, rc, "mgm_backproject");
-        j.syn = download(ctx, d.syn, u.nx, u.ny, u.nch);
-    }
+    // (speckle and fill: once, on level 0's final map)
+    finish_job(ctx, j, out.im, rnolr.im, cost.im, nullptr, du.im, dv.im, sw, [&] {
+        if (!pl.nolr_file.empty()) j.nolr = download(ctx, nolr.im, u.nx, u.ny, 1);
+    });
     sw.mark("download(rest)");
 }
 
@@ -743,64 +562,17 @@ static void multiscale_job(Session &S, Job &j, const Opts &o, const HostImg *plo
 // S.L / S.R (kept for the next pair, or torn down by the caller).
 static int device_job(Session &S, Job &j, const std::function<void()> &decoded, Stopwatch &sw)
 {
-    Opts o = j.o;
+    const JobPlan &p = j.p;
+    Opts o = p.o;
     printf("%d %d\n", o.dmin, o.dmax);  // mgm.cc:328
     fflush(stdout);
-    const double TSGM_ITER = env_param("TSGM_ITER", 1), TESTLRRL = env_param("TESTLRRL", 1);
-    const double TAU = env_param("TESTLRRL_TAU", 1.0), MEDIAN = env_param("MEDIAN", 0);
-    (void)env_param("WITH_MGM2", 0);  // accepted: see the header comment
-    // main()'s loops are `for (int i = 0; i < TSGM_ITER(); i++)` on a DOUBLE (mgm.cc:377, 406): ceil() iterations; none at
-    // all for TSGM_ITER <= 0 -- the maps then stay the zero images they were allocated as (mgm.cc:360-365)
-    const int ITER = TSGM_ITER > 0 ? (int)std::ceil(TSGM_ITER) : 0;
-    const bool ranged = !j.min_file.empty();
-    // MGM_RIGHT_FROM_LEFT=1 (this program's own mode): the right map of the left-right test comes out of the left
-    // run's aggregated volume (mgm_wta_right_dev) instead of a second run
-    const bool rfl = env_param("MGM_RIGHT_FROM_LEFT", 0) != 0 && TESTLRRL != 0;
-    if (rfl) {
-        const char *why = nullptr;
-        if (ranged) why = "range images (-m/-M)";
-        else if (j.nscales > 1) why = "-S > 1";
-        else if (ITER != 1) why = "TSGM_ITER != 1";
-        else if (o.refine == "parabola" || o.refine == "cubic" || o.refine == "parabolaOCV") why = "a refinement other than none or vfit";
-        else if (getenv("MGM_DEVICES") && strchr(getenv("MGM_DEVICES"), ',')) why = "several MGM_DEVICES";
-        if (why) {
-            fprintf(stderr, "mgm: MGM_RIGHT_FROM_LEFT=1 does not combine with %s\n", why);
-            return 2;
-        }
-    }
-    // -c FILE / MGM_UNIQUENESS=r (this program's own mode): the runner-up search of a run right behind its aggregation
-    const bool uq = j.uniq != 0 || !j.conf_file.empty();
-    if (uq) {
-        const char *why = nullptr;
-        if (ranged) why = "range images (-m/-M)";
-        else if (j.nscales > 1) why = "-S > 1";
-        else if (ITER != 1) why = "TSGM_ITER != 1";
-        else if (getenv("MGM_DEVICES") && strchr(getenv("MGM_DEVICES"), ',')) why = "several MGM_DEVICES";
-        if (why) {
-            fprintf(stderr, "mgm: -c / MGM_UNIQUENESS does not combine with %s\n", why);
-            return 2;
-        }
-    }
-    // MGM_SUBPIX=2|4 (this program's own mode): both runs on fine volumes, their maps rescaled to pixels
-    if (o.subpix > 1) {
-        const char *why = nullptr;
-        if (ranged) why = "range images (-m/-M)";
-        else if (j.nscales > 1) why = "-S > 1";
-        else if (ITER != 1) why = "TSGM_ITER != 1";
-        else if (rfl) why = "MGM_RIGHT_FROM_LEFT=1";
-        else if (getenv("MGM_DEVICES") && strchr(getenv("MGM_DEVICES"), ',')) why = "several MGM_DEVICES";
-        if (why) {
-            fprintf(stderr, "mgm: MGM_SUBPIX does not combine with %s\n", why);
-            return 2;
-        }
-    }
-    // MGM_FILL_HOLES_OCC: the classification reads the right map that entered the left-right test
-    if (!j.fill_occ.empty() && TESTLRRL == 0) {
-        fprintf(stderr, "mgm: MGM_FILL_HOLES_OCC needs the right view: TESTLRRL=0 leaves none (MGM_RIGHT_FROM_LEFT takes effect only with TESTLRRL != 0)\n");
-        return 2;
-    }
+    auto refused = [](int code, const std::string &err) {
+        fputs(err.c_str(), stderr);
+        return code;
+    };
+    if (p.outcome == JobPlan::REFUSE) return refused(p.code, p.err_text);
     try {
-        bring_up(S, ITER, ranged, j.nscales > 1);
+        bring_up(S, p);
         sw.mark("context");
         decoded();
         sw.mark("decode(rest)");
@@ -815,33 +587,19 @@ static int device_job(Session &S, Job &j, const std::function<void()> &decoded, 
             fprintf(stderr, "mgm: no usable MI355X device (mgm_ctx_create = %d); there is no CPU path\n", S.rc_ctx);
             return 1;
         }
-        if (multi && j.nscales > 1) {  // (resident mode: an earlier line brought several devices up)
+        if (multi && p.nscales > 1) {  // (resident mode: an earlier line brought several devices up)
             fprintf(stderr, "mgm: MGM_DEVICES: -S (coarse to fine) runs on the first device only\n");
             multi = nullptr;
         }
-        if (multi && ranged) {
+        if (multi && p.ranged) {
             fprintf(stderr, "mgm: --batch with MGM_DEVICES: range images are not supported on several devices\n");
             return 1;
         }
         const HostImg &u = j.u, &v = j.v;
-        if (rfl && multi) {  // (resident mode: an earlier line brought several devices up)
-            fprintf(stderr, "mgm: MGM_RIGHT_FROM_LEFT=1 does not combine with several MGM_DEVICES\n");
-            return 2;
-        }
-        if (uq && multi) {  // (resident mode: an earlier line brought several devices up)
-            fprintf(stderr, "mgm: -c / MGM_UNIQUENESS does not combine with several MGM_DEVICES\n");
-            return 2;
-        }
-        if (o.subpix > 1 && multi) {  // (resident mode: an earlier line brought several devices up)
-            fprintf(stderr, "mgm: MGM_SUBPIX does not combine with several MGM_DEVICES\n");
-            return 2;
-        }
-        if (rfl && u.ny != v.ny) {
-            fprintf(stderr, "mgm: MGM_RIGHT_FROM_LEFT=1 needs two images of one height\n");
-            return 2;
-        }
+        const mgm_cli::Refusal no = mgm_cli::refuse_on_session(p, multi != nullptr, u.ny, v.ny);
+        if (no.code) return refused(no.code, no.err_text);
         HostImg &rlo = j.rlo, &rhi = j.rhi;  // -m / -M range images of the left->right run (mgm.cc:342-353); the right->left run keeps -r/-R
-        if (ranged) {
+        if (p.ranged) {
             if (rlo.nx != u.nx || rlo.ny != u.ny || rhi.nx != u.nx || rhi.ny != u.ny || rlo.nch != 1 || rhi.nch != 1) {
                 fprintf(stderr, "mgm: the -m/-M images must have the size of the left image\n");
                 return 1;
@@ -851,17 +609,18 @@ static int device_job(Session &S, Job &j, const std::function<void()> &decoded, 
             for (size_t i = 0; i < rlo.data.size(); i++)
                 if (rhi.data[i] < rlo.data[i] + 1) rhi.data[i] = ceilf(rlo.data[i] + 1);
         }
-        const HostImg *plo = ranged ? &rlo : nullptr, *phi = ranged ? &rhi : nullptr;
+        const HostImg *plo = p.ranged ? &rlo : nullptr, *phi = p.ranged ? &rhi : nullptr;
         o.P1 *= u.nch;  // mgm.cc:356-357
         o.P2 *= u.nch;
 
         int rc;
         Run &L = S.L, &R = S.R;
         ImgHold dconf{ctx};  // -c: the confidence map, until it is downloaded
-        const bool both = TESTLRRL != 0;
-        if (j.nscales > 1) {
-            multiscale_job(S, j, o, plo, phi, ITER, both, (float)TAU, (int)MEDIAN, sw);
-            report_kernels(ctx, multi);
+        const int ITER = p.iterations;
+        const bool both = p.both, rfl = p.rfl;
+        if (p.nscales > 1) {
+            multiscale_job(S, j, o, plo, phi, sw);
+            if (p.kernels && !multi) report_kernels(ctx);
             return 0;
         }
         if (!both && R.C) free_run(ctx, R);  // (kept from an earlier pair, not wanted by this one)
@@ -882,7 +641,7 @@ static int device_job(Session &S, Job &j, const std::function<void()> &decoded, 
             zero_run(L);
             together = true;  // (nothing to aggregate)
         }
-        if (ITER > 0 && !multi && both && !rfl && !plo && u.nx == v.nx && u.ny == v.ny && env_param("MGM_BATCH_LR", 1) != 0) {
+        if (ITER > 0 && !multi && both && !rfl && !plo && u.nx == v.nx && u.ny == v.ny && p.batch_lr) {
             // both runs of the pair (mgm.cc:376-385 and 405-414) through ONE launch of the pass kernel
             prepare_R();
             const mgm_cv *Cs[2] = {L.C, R.C};
@@ -903,10 +662,10 @@ static int device_job(Session &S, Job &j, const std::function<void()> &decoded, 
             report_run(o, L);
             iterate_run(ctx, o, L, ITER, o.dmin, o.dmax, plo, phi);
             rescale_run(ctx, o, L);
-            if (uq) uniqueness_run(ctx, o, L, (float)j.uniq, j.uniq_radius, j.conf_file.empty() ? nullptr : &dconf.im);
+            if (p.uq) uniqueness_run(ctx, o, L, (float)p.uniq, p.uniq_radius, p.conf_file.empty() ? nullptr : &dconf.im);
         }
-        if (MEDIAN != 0) median_run(ctx, L, (int)MEDIAN);
-        if (!j.nolr_file.empty()) j.nolr = download(ctx, L.dout, L.nx, L.ny, 1);
+        if (p.median != 0) median_run(ctx, L, (int)p.median);
+        if (!p.nolr_file.empty()) j.nolr = download(ctx, L.dout, L.nx, L.ny, 1);
         if (rfl) {
             // the right map out of the left run: no volume, no passes (R keeps only its two maps)
             if (R.C || R.nx != v.nx || R.ny != v.ny) free_run(ctx, R);
@@ -916,7 +675,7 @@ static int device_job(Session &S, Job &j, const std::function<void()> &decoded, 
             if ((rc = mgm_wta_right_dev(ctx, L.C, o.NDIR, o.FIX, o.refine.c_str(), R.dout, R.dcost))) die(ctx, rc, "mgm_wta_right");
             printf("right from left\n");
             fflush(stdout);
-            if (MEDIAN != 0) median_run(ctx, R, (int)MEDIAN);
+            if (p.median != 0) median_run(ctx, R, (int)p.median);
         } else if (both) {
             if (!r_ready) prepare_R();
             if (ITER == 0) {
@@ -927,64 +686,33 @@ static int device_job(Session &S, Job &j, const std::function<void()> &decoded, 
                 report_run(o, R);
                 iterate_run(ctx, o, R, ITER, -o.dmax, -o.dmin);
                 rescale_run(ctx, o, R);
-                if (j.uniq != 0) uniqueness_run(ctx, o, R, (float)j.uniq, j.uniq_radius, nullptr);
+                if (p.uniq != 0) uniqueness_run(ctx, o, R, (float)p.uniq, p.uniq_radius, nullptr);
             }
-            if (MEDIAN != 0) median_run(ctx, R, (int)MEDIAN);
+            if (p.median != 0) median_run(ctx, R, (int)p.median);
         }
         if (both) {
             // leftright_test both ways on copies of the unchecked maps (mgm.cc:420-423)
             image_like(ctx, L.nx, L.ny, 1, &L.dspare);
             image_like(ctx, R.nx, R.ny, 1, &R.dspare);
-            if ((rc = mgm_leftright_dev(ctx, R.dout, L.dout, (float)TAU, R.dspare)) ||
-                (rc = mgm_leftright_dev(ctx, L.dout, R.dout, (float)TAU, L.dspare)))
+            if ((rc = mgm_leftright_dev(ctx, R.dout, L.dout, p.tau, R.dspare)) || (rc = mgm_leftright_dev(ctx, L.dout, R.dout, p.tau, L.dspare)))
                 die(ctx, rc, "mgm_leftright");
             std::swap(L.dout, L.dspare);
             std::swap(R.dout, R.dspare);
         }
-        // MGM_SPECKLE: last, on the final left map (with several devices: `ctx` is the device that holds the gathered map)
-        if (j.speckle > 0) speckle_map(ctx, L.dout, j.speckle, j.speckle_diff);
-        // MGM_FILL_HOLES: after every rejection step, before the back-projected image is made
-        // (MGM_FILL_HOLES_OCC: after the swap above R.dspare is the right map as it entered the left-right test)
-        if (!j.fill_occ.empty()) fill_holes_classified_map(ctx, L.dout, R.dspare, o.dmin, o.dmax, (float)TAU, j.fill_occ, j.fill, j.fill_dirs, j.fill_dist);
-        else if (!j.fill.empty()) fill_holes_map(ctx, L.dout, j.fill, j.fill_dirs, j.fill_dist);
-        sw.mark("enqueue(rest)");
-        j.outoff = download(ctx, L.dout, L.nx, L.ny, 1);
-        sw.mark("device+download");
-        if (!j.f_cost.empty()) j.outcost = download(ctx, L.dcost, L.nx, L.ny, 1);
-        if (dconf.im) j.conf = download(ctx, dconf.im, L.nx, L.ny, 1);
-        // back-projected image (mgm.cc:433-443)
-        if (!j.f_back.empty()) {
-            mgm_img *dsyn = nullptr;
-            if ((rc = mgm_img_create(ctx, u.nx, u.ny, u.nch, &dsyn))) die(ctx, rc, "mgm_img_create");
-            if ((rc = mgm_backproject_dev(ctx, L.du, L.dv, L.dout, dsyn))) {
-                mgm_img_free(ctx, dsyn);
-                die(ctx, rc, "mgm_backproject");
-            }
-            try {
-                j.syn = download(ctx, dsyn, u.nx, u.ny, u.nch);
-            } catch (...) {
-                mgm_img_free(ctx, dsyn);
-                throw;
-            }
-            mgm_img_free(ctx, dsyn);
-        }
+        // (with several devices `ctx` is the device that holds the gathered map; after the swap above R.dspare is the right map as it
+        // entered the left-right test)
+        finish_job(ctx, j, L.dout, R.dspare, L.dcost, dconf.im, L.du, L.dv, sw, [&] { sw.mark("enqueue(rest)"); });
         sw.mark("download(rest)");
-        report_kernels(ctx, multi);
-    } catch (const DeviceError &e) {
+        if (p.kernels && !multi) report_kernels(ctx);
+    } catch (const std::exception &e) {  // (a DeviceError, an unreadable input)
         fprintf(stderr, "mgm: %s\n", e.what());
         // whatever the failed job left half-made goes; the context stays (resident mode: the next job starts clean)
         if (S.ctx) {
             free_run(S.ctx, S.R);
             free_run(S.ctx, S.L);
         }
-        return e.code();
-    } catch (const std::exception &e) {
-        fprintf(stderr, "mgm: %s\n", e.what());
-        if (S.ctx) {
-            free_run(S.ctx, S.R);
-            free_run(S.ctx, S.L);
-        }
-        return 1;
+        const DeviceError *de = dynamic_cast<const DeviceError *>(&e);
+        return de ? de->code() : 1;
     }
     return 0;
 }
@@ -1006,13 +734,9 @@ static int run_one(int argc, char **argv)
 {
     Job j;
     for (int i = 0; i < argc; i++) j.tok.push_back(argv[i]);
-    parse_job(j);
-    if (j.early >= 0) {
-        fputs(j.early_out.c_str(), stdout);
-        fputs(j.early_err.c_str(), stderr);
-        return j.early;
-    }
-    Stopwatch sw;
+    j.p = mgm_cli::plan_job(j.tok, getenv);
+    if (ends_early(j)) return j.rc;
+    Stopwatch sw(j.p);
     Session S;
     // decode both inputs on their own threads while this one brings the device up (process start + HIP initialisation
     // + context is most of a run's wall time: the device work of a full-HD pair is ~17 ms)
@@ -1036,7 +760,7 @@ static int run_one(int argc, char **argv)
     // code objects, closing the device: tens of ms that produce nothing).  MGM_HIP_ORDERLY_EXIT=1 keeps them.
     fflush(stdout);
     fflush(stderr);
-    if (!(getenv("MGM_HIP_ORDERLY_EXIT") && atoi(getenv("MGM_HIP_ORDERLY_EXIT")))) _exit(j.rc);
+    if (!j.p.orderly_exit) _exit(j.rc);
     return j.rc;
 }
 
@@ -1084,7 +808,7 @@ static int run_batch(const char *file)
     }
     if (f != stdin) fclose(f);
     const size_t N = jobs.size();
-    for (auto &j : jobs) parse_job(*j);
+    for (auto &j : jobs) j->p = mgm_cli::plan_job(j->tok, getenv);  // (every line with the process's environment)
 
     // the decoder works at most AHEAD jobs ahead of the device stage (each decoded pair holds its images in memory)
     constexpr size_t AHEAD = 2;
@@ -1095,9 +819,9 @@ static int run_batch(const char *file)
     // the decoder then waits for the writer -- needs[k] = how many jobs must have been WRITTEN before job k's inputs are read
     std::vector<size_t> needs(N, 0);
     for (size_t k = 0; k < N; k++) {
-        const Job &j = *jobs[k];
+        const JobPlan &j = jobs[k]->p;
         for (size_t m = 0; m < k; m++) {
-            const Job &e = *jobs[m];
+            const JobPlan &e = jobs[m]->p;
             for (const std::string *in : {&j.f_u, &j.f_v, &j.min_file, &j.max_file})
                 for (const std::string *out : {&e.f_out, &e.f_cost, &e.f_back, &e.nolr_file, &e.conf_file})
                     if (!in->empty() && *in == *out) needs[k] = m + 1;
@@ -1149,12 +873,8 @@ static int run_batch(const char *file)
             on_device = k;
         }
         cv.notify_all();
-        if (j.early >= 0) {
-            fputs(j.early_out.c_str(), stdout);
-            fputs(j.early_err.c_str(), stderr);
-            j.rc = j.early;
-        } else {
-            Stopwatch sw;
+        if (!ends_early(j)) {
+            Stopwatch sw(j.p);
             j.rc = device_job(S, j, [&] {
                 std::unique_lock<std::mutex> lk(mu);
                 cv.wait(lk, [&] { return decoded > k; });

@@ -437,3 +437,41 @@ def test_full_size_ragged_command_line_matches_reference(half, tmp_path):
     assert "k_pass_rel" in kernels, kernels
     for f in ("disp.npy", "cost.npy"):
         assert ndiff(outs["ref"][1][f], outs["ours"][1][f]) == 0, f
+
+
+def test_resident_batch_lines_with_the_last_filters_match_their_one_shot_runs(tmp_path):
+    """The end of a job -- speckle filter, classified hole filling, the downloads, the back-projected image -- is one function for the
+    single-scale and the coarse-to-fine driver, and in `mgm --batch` the device objects of a pair are kept for the next one: four lines
+    under MGM_SPECKLE, MGM_FILL_HOLES, MGM_FILL_HOLES_OCC and MEDIAN, a -S 2 line and another geometry between two equal lines.  Per
+    line, stdout and every output file are, byte for byte, what the same binary writes for that line run on its own; the first and
+    the last line give the same bytes (the kept objects were refilled, not stale)."""
+    env = dict(os.environ, MGM_SPECKLE="8", MGM_FILL_HOLES="median", MGM_FILL_HOLES_OCC="sechigh", MEDIAN="1")
+    for tag, nx, ny, nch, d in (("a", 64, 48, 1, 8), ("b", 48, 40, 3, 6)):
+        u, v, _ = synth.stereo_pair(nx, ny, -d, d, seed=70 + nch, nch=nch)
+        np.save(tmp_path / (tag + "_u.npy"), np.ascontiguousarray(u.transpose(1, 2, 0)) if nch > 1 else u[0])
+        np.save(tmp_path / (tag + "_v.npy"), np.ascontiguousarray(v.transpose(1, 2, 0)) if nch > 1 else v[0])
+    jobs = [("a", "-r -8 -R 8"), ("a", "-r -8 -R 8 -S 2"), ("b", "-r -6 -R 6"), ("a", "-r -8 -R 8")]
+    OUT = ("nolr", "disp", "cost", "back")
+
+    def line(who, k):
+        tag, args = jobs[k]
+        d = tmp_path / ("%s%d" % (who, k))
+        d.mkdir()
+        return ("-t census -O 4 " + args).split() + ["-l", str(d / "nolr.npy"), str(tmp_path / (tag + "_u.npy")), str(tmp_path / (tag + "_v.npy"))] + \
+            [str(d / (f + ".npy")) for f in OUT[1:]]
+
+    stdout = ""
+    for k in range(len(jobs)):
+        r = subprocess.run([OURS] + line("one", k), env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, (k, r.stderr)
+        stdout += r.stdout
+    (tmp_path / "list.txt").write_text("".join(" ".join(line("batch", k)) + "\n" for k in range(len(jobs))))
+    r = subprocess.run([OURS, "--batch", str(tmp_path / "list.txt")], env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr
+    assert r.stdout == stdout and stdout.count("\n") > 3 * len(jobs)
+    files = lambda who, k: [(tmp_path / ("%s%d" % (who, k)) / (f + ".npy")).read_bytes() for f in OUT]
+    for k in range(len(jobs)):
+        assert files("batch", k) == files("one", k), k
+    assert files("batch", 0) == files("batch", 3)
+    disp, nolr = (np.load(tmp_path / "batch0" / (f + ".npy")) for f in ("disp", "nolr"))
+    assert ndiff(disp, nolr) > 0  # (the filters and the fill had something to do)
