@@ -396,6 +396,31 @@ int mgm_wta_runnerup_dev(mgm_ctx *ctx, const mgm_cv *C, int NDIR, int fix_overco
  * All images are one-channel and of one size, ratio is finite and in [0, 1] (else MGM_ERR_INVALID).  No synchronisation. */
 int mgm_uniqueness_dev(mgm_ctx *ctx, const mgm_img *d, const mgm_img *cost1, const mgm_img *cost2, float ratio,
                        mgm_img *out, mgm_img *conf);
+/* The consensus votes (DESIGN.md "consensus votes"; this library's own measure, the reference has none): how many of the NDIR
+ * scan-line passes of the context's last aggregation of C, each taken ALONE, pick the label the map d holds.  Per pixel x:
+ *   pass winner  w_p = the first strict minimum, by rising label, among the finite entries of Lr_p(x, .) over the labels the pixel
+ *                owns: 0..L-1 of a dense volume, its own range [(int)lo, (int)hi] inside the volume for a ragged one.  Padding slots
+ *                of a padded label stride and slots outside the pixel's range are never candidates, whatever they hold; equal values,
+ *                -0 / +0 included, go to the smaller label; no finite entry: the pass has no winner
+ *   vote         w_p exists and fabsf((float)(w_p + dmin) - d(x)) <= tol: one float subtraction, a NaN or infinite d(x) gets no vote
+ *   votes(x)     = (float) number of voting passes, 0..NDIR
+ *   winners      nx x ny x NDIR, planar: winners[p](x) = (float)(w_p + dmin), NaN without a winner
+ * No cost is read and no sum is formed, so the definition is one for a dense volume, a ragged volume whose aggregation ran on its
+ * dense hull and one whose aggregation ran on the range-proportional copy: the call is never MGM_ERR_UNSUPPORTED for a ragged volume,
+ * and the two ragged routes agree bit for bit.  d is any nx x ny x 1 map in labels (a refined, windowed or sub-pixel map is fine).
+ * votes and winners may each be NULL, not both; d may be NULL when only winners is asked for.  MGM_ERR_INVALID: a null argument, a
+ * size or channel mismatch, votes or winners aliasing d (or each other), tol negative or not finite, NDIR outside 1..8, a volume that
+ * is not part of the context's last aggregation with NDIR passes (a trimmed context, a volume or a range-proportional copy refilled
+ * since, an earlier chunk of a chunked batch).  The call leaves what the context holds of that aggregation untouched.  No
+ * synchronisation; the timing table lists the call as k_wta_consensus, with the family that ran (k_wta_consensus_stream / _any /
+ * _rel) as a second name.  MGM_HIP_WTA_CONSENSUS_ANY=1 sends every call to the generic kernel, MGM_HIP_WTA_CONSENSUS_WG=<workgroups
+ * per CU> lowers the grid's cap (both for tests, read at every call). */
+int mgm_wta_consensus_dev(mgm_ctx *ctx, const mgm_cv *C, int NDIR, const mgm_img *d, float tol, mgm_img *votes, mgm_img *winners);
+/* The consensus filter, per pixel: out = votes < (float)minvotes ? NaN : d.  minvotes >= 0 (0 keeps every pixel); out may be d, not
+ * votes; all images one-channel and of one size (else MGM_ERR_INVALID).  No synchronisation.
+ * The command line: -C FILE writes the left run's votes, MGM_CONSENSUS=k (0: off) filters each run's map, MGM_CONSENSUS_TOL (1) is
+ * the tolerance; `mgm --help` does not name them yet (its text is pinned by a recorded table). */
+int mgm_consensus_filter_dev(mgm_ctx *ctx, const mgm_img *d, const mgm_img *votes, int minvotes, mgm_img *out);
 /* The speckle filter (DESIGN.md "speckle filter"; this library's own step, the reference has none): small islands of disparity go.
  * d is an nx x ny x 1 map, maxsize >= 0, maxdiff >= 0 (+INF allowed; negative or NaN: MGM_ERR_INVALID as maxsize < 0 is).
  *   valid pixel  d(p) is finite; NaN and +-INF pixels belong to no component and are copied to out bit for bit
@@ -535,6 +560,11 @@ typedef struct mgm_ms_params {
     mgm_ms_level *levels; /* optional out: `nscales` entries, [s] filled for every level that ran */
     mgm_img *outR_nolr;   /* optional out (NULL or absent: nothing happens): vnx*vny, the finest level's right map after MEDIAN and
                              before its left-right test -- what mgm_classify_holes_dev wants as `other`; untouched with testlrrl = 0 */
+    /* the consensus votes (mgm_wta_consensus_dev), at the finest level only, on each run's map after its iterations and refinement and
+     * before MEDIAN and the left-right test; absent (an older struct_size) or zero: nothing happens */
+    float consensus_tol;  /* the tolerance, finite and >= 0 (looked at only when one of the next two asks for the step) */
+    int consensus_min;    /* > 0: each run's map becomes NaN where fewer passes vote for it (mgm_consensus_filter_dev); < 0: MGM_ERR_INVALID */
+    mgm_img *votesL;      /* optional out: nx*ny, the left->right run's votes (zeros with iterations = 0: no pass has voted) */
 } mgm_ms_params;
 
 /* One stereo pair, coarse to fine.  Per level exactly what the `mgm` command line does for a pair (weights, ranged cost

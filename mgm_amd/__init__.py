@@ -37,6 +37,7 @@ ABI_SYMBOLS = [
     "mgm_classify_holes_dev", "mgm_fill_holes_classified_dev",
     "mgm_subpix_phase_dev", "mgm_costvolume_build_subpix_dev", "mgm_subpix_scale_dev",
     "mgm_debug_rel_lr_device_ptr", "mgm_debug_wta_rel_again_dev", "mgm_debug_lr_device_ptr",
+    "mgm_wta_consensus_dev", "mgm_consensus_filter_dev",
 ]
 
 MGM_OK, MGM_ERR_INVALID, MGM_ERR_UNSUPPORTED, MGM_ERR_HIP, MGM_ERR_NOMEM, MGM_ERR_INTERNAL = range(6)
@@ -66,6 +67,11 @@ class MsParams(C.Structure):
                 ("census_win", C.c_int), ("refine", C.c_char_p), ("iterations", C.c_int), ("median", C.c_int),
                 ("testlrrl", C.c_int), ("tau", C.c_float), ("levels_run", C.POINTER(C.c_int)), ("levels", C.POINTER(MsLevel)),
                 ("outR_nolr", C.c_void_p)]
+
+
+class MsParamsConsensus(C.Structure):
+    """``mgm_ms_params`` as it has grown at its end: ``MsParams`` (kept as the struct of an older caller) and the consensus fields."""
+    _fields_ = MsParams._fields_ + [("consensus_tol", C.c_float), ("consensus_min", C.c_int), ("votesL", C.c_void_p)]
 
 
 def load_library():
@@ -121,6 +127,8 @@ def load_library():
     L.mgm_wta_right_dev.argtypes = [vp, vp, i, i, cp, vp, vp]
     L.mgm_wta_runnerup_dev.argtypes = [vp, vp, i, i, i, vp, vp, vp, vp]
     L.mgm_uniqueness_dev.argtypes = [vp, vp, vp, vp, f, vp, vp]
+    L.mgm_wta_consensus_dev.argtypes = [vp, vp, i, vp, f, vp, vp]
+    L.mgm_consensus_filter_dev.argtypes = [vp, vp, vp, i, vp]
     L.mgm_speckle_dev.argtypes = [vp, vp, i, f, vp, vp]
     L.mgm_fill_holes_dev.argtypes = [vp, vp, cp, i, i, vp, vp]
     L.mgm_classify_holes_dev.argtypes = [vp, vp, vp, i, i, f, vp]
@@ -419,6 +427,45 @@ class Context:
             raise
         return (out if out else None), conf
 
+    def wta_consensus_dev(self, Cv, NDIR, d, tol=1.0, votes=None, want_winners=False):
+        """The consensus votes over the context's last aggregation of Cv (mgm_wta_consensus_dev): device images (votes, winners)
+        -- how many of the NDIR passes, each taken alone, pick a label within tol of the map d, and the passes' own winners
+        (nx x ny x NDIR; None without want_winners).  votes: an image to write, None for a new one, False for none (d may then
+        be None)."""
+        nx, ny, _, _ = Cv.dims
+        mine = []  # the images made here: freed if the call fails
+        try:
+            if votes is None:
+                votes = self.new_image(nx, ny)
+                mine.append(votes)
+            winners = None
+            if want_winners:
+                winners = self.new_image(nx, ny, NDIR)
+                mine.append(winners)
+            self._chk(self.lib.mgm_wta_consensus_dev(self.h, Cv.h, NDIR, d.h if d is not None else None, tol, votes.h if votes else None,
+                                                     winners.h if want_winners else None))
+        except Exception:
+            for im in mine:
+                im.free()
+            raise
+        return (votes if votes else None), winners
+
+    def consensus_filter_dev(self, d, votes, minvotes, out=None):
+        """out = NaN where votes < minvotes, else d (mgm_consensus_filter_dev): the device image out -- one to write (d itself is
+        allowed) or None for a new one."""
+        _, ny, nx = d.shape
+        mine = []  # the image made here: freed if the call fails
+        try:
+            if out is None:
+                out = self.new_image(nx, ny)
+                mine.append(out)
+            self._chk(self.lib.mgm_consensus_filter_dev(self.h, d.h, votes.h, minvotes, out.h))
+        except Exception:
+            for im in mine:
+                im.free()
+            raise
+        return out
+
     def speckle_dev(self, d, maxsize, maxdiff=1.0, out=None, want_size=False):
         """The speckle filter (mgm_speckle_dev): NaN into every 4-connected component of finite pixels, joined where
         |d(p) - d(q)| <= maxdiff, of at most maxsize pixels; device images (out, size_map).  out: an image to write (d itself is
@@ -638,11 +685,13 @@ class Context:
     def multiscale_pair(self, u, v, dmin, dmax, nscales, P1=8.0, P2=32.0, NDIR=4, TSGM=4, use_fh=0, fix_overcount=1, aP2=1.0,
                         aThresh=5.0, prefilter="none", distance="ad", truncDist=float("inf"), census_win=3, refine="none",
                         iterations=1, median=0, testlrrl=1, tau=1.0, slack=3, radius=2, lo=None, hi=None, want_nolr=True,
-                        want_right_nolr=False):
+                        want_right_nolr=False, consensus_min=0, consensus_tol=1.0, want_votes=False):
         """mgm_multiscale_pair_dev on device images u, v (P1 / P2 as given: multiply by the channel count yourself).
         Returns a dict of device images outL, costL, outR, costR (None with testlrrl=0), nolr (None unless wanted), outR_nolr
-        (with want_right_nolr and testlrrl: the full-size right map before its left-right test, else None) and
-        `levels`: one dict per level that ran, [0] = full size."""
+        (with want_right_nolr and testlrrl: the full-size right map before its left-right test, else None), votesL (with
+        want_votes: the left run's consensus votes at full size, else None) and `levels`: one dict per level that ran,
+        [0] = full size.  consensus_min > 0: the finest level's maps are NaN where fewer passes vote for them (tolerance
+        consensus_tol).  Without consensus_min and want_votes the call passes the struct of an older caller."""
         _, ny, nx = u.shape
         _, vny, vnx = v.shape
         res = dict(outL=self.new_image(nx, ny), costL=self.new_image(nx, ny), outR=None, costR=None, nolr=None, outR_nolr=None)
@@ -652,6 +701,7 @@ class Context:
                 res["outR_nolr"] = self.new_image(vnx, vny)
         if want_nolr:
             res["nolr"] = self.new_image(nx, ny)
+        res["votesL"] = self.new_image(nx, ny) if want_votes else None
         n = C.c_int(0)
         lv = (MsLevel * 8)()
         p = MsParams(C.sizeof(MsParams), nscales, slack, radius, dmin, dmax, lo.h if lo is not None else None,
@@ -659,6 +709,11 @@ class Context:
                      distance.encode(), truncDist, census_win, (refine or "none").encode(), iterations, median, testlrrl, tau,
                      C.pointer(n), lv, res["outR_nolr"].h if res["outR_nolr"] is not None else None)
         hnd = lambda im: im.h if im is not None else None
+        if consensus_min or want_votes:  # the struct as it has grown: the same leading bytes, then the consensus fields
+            big = MsParamsConsensus()
+            C.memmove(C.byref(big), C.byref(p), C.sizeof(p))
+            big.struct_size, big.consensus_tol, big.consensus_min, big.votesL = C.sizeof(big), consensus_tol, consensus_min, hnd(res["votesL"])
+            p = C.cast(C.pointer(big), C.POINTER(MsParams)).contents
         r = self.lib.mgm_multiscale_pair_dev(self.h, u.h, v.h, C.byref(p), hnd(res["outL"]), hnd(res["costL"]), hnd(res["outR"]),
                                              hnd(res["costR"]), hnd(res["nolr"]))
         if r:

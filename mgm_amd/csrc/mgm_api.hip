@@ -666,6 +666,49 @@ int mgm_uniqueness_dev(mgm_ctx *c, const mgm_img *d, const mgm_img *cost1, const
     return MGM_OK;
 }
 
+// The consensus votes: dense volumes, ragged volumes on their hull and ragged volumes aggregated on their
+// range-proportional copy alike -- no cost is read and no sum is formed, so nothing ties the measure to one layout.
+int mgm_wta_consensus_dev(mgm_ctx *c, const mgm_cv *C, int NDIR, const mgm_img *d, float tol, mgm_img *votes, mgm_img *winners)
+{
+    if (int jr = pipe_join(c)) return jr;  // (pipelined context: run what has been deferred first)
+    if (!c || !C || (!votes && !winners) || (votes && !d)) return fail(c, MGM_ERR_INVALID, "mgm_wta_consensus: null argument (at least one of votes, winners; d with votes)");
+    if (!(tol >= 0.0f) || !std::isfinite(tol)) return fail(c, MGM_ERR_INVALID, "mgm_wta_consensus: tol must be finite and >= 0");
+    if (NDIR < 1 || NDIR > kMaxDirs) return fail(c, MGM_ERR_INVALID, "mgm_wta_consensus: NDIR must be 1..8");
+    for (const mgm_img *im : {d, (const mgm_img *)votes})
+        if (im && (im->nx != C->nx || im->ny != C->ny || im->nch != 1))
+            return fail(c, MGM_ERR_INVALID, "mgm_wta_consensus: image size mismatch (d and votes are nx x ny x 1, the volume's)");
+    if (winners && (winners->nx != C->nx || winners->ny != C->ny || winners->nch != NDIR))
+        return fail(c, MGM_ERR_INVALID, "mgm_wta_consensus: image size mismatch (winners is nx x ny x NDIR)");
+    if ((votes && votes == d) || (winners && (winners == d || winners == votes)))
+        return fail(c, MGM_ERR_INVALID, "mgm_wta_consensus: votes and winners must be images of their own");
+    const int L = C->dmax - C->dmin + 1;
+    if (const int v = c->rel_last.slot_of(C); v >= 0) {  // the context's last aggregation of this volume ran on its range-proportional copy
+        if (c->rel_last.ndir != NDIR || c->last.ndir != 0 || !c->lr_rel.p || !C->relbuf || C->rel_slots != c->rel_last.slots || (C->rel_slots != 64 && C->rel_slots != 128))
+            return fail(c, MGM_ERR_INVALID, "mgm_wta_consensus: this volume was not part of the context's last aggregation with NDIR passes");
+        HIPCHK(c, hipSetDevice(c->device));
+        return run_wta_consensus(c, C, v, true, NDIR, d ? d->d : nullptr, tol, votes ? votes->d : nullptr, winners ? winners->d : nullptr);
+    }
+    const int slot = c->last.slot_of(C);
+    if (!c->lr.p || slot < 0 || c->last.ndir != NDIR || c->last.L != L)
+        return fail(c, MGM_ERR_INVALID, "mgm_wta_consensus: this volume was not part of the context's last aggregation with NDIR passes");
+    HIPCHK(c, hipSetDevice(c->device));
+    return run_wta_consensus(c, C, slot, false, NDIR, d ? d->d : nullptr, tol, votes ? votes->d : nullptr, winners ? winners->d : nullptr);
+}
+
+int mgm_consensus_filter_dev(mgm_ctx *c, const mgm_img *d, const mgm_img *votes, int minvotes, mgm_img *out)
+{
+    if (int jr = pipe_join(c)) return jr;  // (pipelined context: run what has been deferred first)
+    if (!c || !d || !votes || !out) return fail(c, MGM_ERR_INVALID, "mgm_consensus_filter: null argument");
+    if (minvotes < 0) return fail(c, MGM_ERR_INVALID, "mgm_consensus_filter: minvotes must be >= 0");
+    for (const mgm_img *im : {d, votes, (const mgm_img *)out})
+        if (im->nx != d->nx || im->ny != d->ny || im->nch != 1) return fail(c, MGM_ERR_INVALID, "mgm_consensus_filter: image size mismatch (one channel, one size)");
+    if (votes == d || out == votes) return fail(c, MGM_ERR_INVALID, "mgm_consensus_filter: out may be d, not the votes");
+    HIPCHK(c, hipSetDevice(c->device));
+    TimeScope t(c, "k_consensus_filter");
+    HIPCHK(c, launch_consensus_filter(d->d, votes->d, (long long)d->nx * d->ny, minvotes, out->d, c->stream));
+    return MGM_OK;
+}
+
 int mgm_update_ranges_dev(mgm_ctx *c, const mgm_img *outoff, mgm_img *dminI, mgm_img *dmaxI, int slack, int radius)
 {
     if (int jr = pipe_join(c)) return jr;  // (pipelined context: run what has been deferred first)

@@ -126,6 +126,25 @@ hipError_t launch_wta_runnerup(const WtaRunnerupParams &p, const RunnerupChoice 
 hipError_t launch_uniqueness(const float *d, const float *cost1, const float *cost2, long long n, float ratio, float *out, float *conf,
                              hipStream_t s);
 
+// the consensus votes over the same Lr volumes, each taken alone (mgm_consensus.hip): per pixel and pass the first
+// strict minimum among the finite entries the pixel owns, and how many of those winners lie within tol of the map d.  No costs.
+struct WtaConsensusParams {
+    const float *Lr;         // NDIR volumes [npix][Lk], pass p at Lr + p*nvol
+    const float *d;          // [npix] the map to judge, in labels; nullptr with votes == nullptr
+    float *votes;            // [npix] or nullptr
+    float *winners;          // [NDIR][npix] or nullptr: (float)(w_p + dmin), NaN without a winner
+    const float *rlo, *rhi;  // a ragged volume on its dense hull: the pixel owns [(int)rlo, (int)rhi] inside the volume; else nullptr
+    const int *rec;          // the range-proportional layout: [npix][4] records (disparity of slot 0, lowest, highest, 0); Lk = L = slots
+    long long npix, nvol;
+    int L, Lk;               // labels that exist, label stride (>= L)
+    int NDIR, dmin;
+    float tol;
+};
+struct ConsensusChoice;  // (mgm_planner.h: what plan_wta_consensus decided)
+hipError_t launch_wta_consensus(const WtaConsensusParams &p, const ConsensusChoice &c, hipStream_t s);
+// out = votes < (float)minvotes ? NaN : d (mgm_post.hip); out may be d
+hipError_t launch_consensus_filter(const float *d, const float *votes, long long n, int minvotes, float *out, hipStream_t s);
+
 // the speckle filter (mgm_speckle.hip): connected components of the finite pixels under |d(p) - d(q)| <= maxdiff on
 // 4-neighbours; out = NaN on the components of at most maxsize pixels, size_map = the size of every pixel's component
 struct SpeckleParams {

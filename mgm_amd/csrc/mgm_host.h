@@ -380,6 +380,7 @@ int run_wta(mgm_ctx *c, const mgm_cv *C, long long pix0, long long npix, const f
 int run_wta_right(mgm_ctx *c, const mgm_cv *C, int slot, int NDIR, int fix_overcount, int ridx, int vnx, float *out, float *outcost);
 int run_wta_runnerup(mgm_ctx *c, const mgm_cv *C, int slot, int NDIR, int fix_overcount, int radius, float *out2, float *cost2, float *out1,
                      float *cost1);
+int run_wta_consensus(mgm_ctx *c, const mgm_cv *C, int slot, bool rel, int NDIR, const float *d, float tol, float *votes, float *winners);
 // the range-proportional path of ragged volumes (mgm_plan.hip): is this call one it takes?  then the passes + the winner search
 bool rel_enabled();
 int weights_have_odd_values(mgm_ctx *c, const mgm_img *const *w8s, int nb, long long npix, bool *odd, bool *any = nullptr);

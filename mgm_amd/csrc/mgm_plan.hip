@@ -810,6 +810,45 @@ int run_wta_runnerup(mgm_ctx *c, const mgm_cv *C, int slot, int NDIR, int fix_ov
     return MGM_OK;
 }
 
+// The consensus votes over the Lr volumes of the context's last aggregation of C, each pass taken alone
+// (mgm_wta_consensus_dev has checked that C is such a volume): slot `slot` of the dense run, or with rel = true of the
+// range-proportional one.  Reads the context's record of that aggregation and leaves it, the chunk minima and the search
+// statistics as they are.  No costs are read.
+int run_wta_consensus(mgm_ctx *c, const mgm_cv *C, int slot, bool rel, int NDIR, const float *d, float tol, float *votes, float *winners)
+{
+    WtaConsensusParams w{};
+    w.d = d;
+    w.votes = votes;
+    w.winners = winners;
+    w.npix = (long long)C->nx * C->ny;
+    w.NDIR = NDIR;
+    w.dmin = C->dmin;
+    w.tol = tol;
+    if (rel) {
+        w.Lr = c->rel_last.lr(c->lr_rel, slot, 0);
+        w.nvol = c->rel_last.stride;
+        w.rec = C->rel_records();
+        w.L = w.Lk = C->rel_slots;
+    } else {
+        w.Lr = c->last.lr(c->lr, slot, 0);
+        w.nvol = c->last.stride;
+        w.rlo = C->rlo;  // a ragged volume whose last run was dense: the hull, masked by the pixel's own range
+        w.rhi = C->rhi;
+        w.L = C->dmax - C->dmin + 1;
+        w.Lk = c->last.Lk;
+    }
+    // MGM_HIP_WTA_CONSENSUS_ANY=1 (read at every call: tests switch it inside one process): the generic kernel everywhere
+    // ... MGM_HIP_WTA_CONSENSUS_WG=<workgroups per CU> (the same): a lower cap of the grid, so that small volumes take several turns
+    const char *ea = getenv("MGM_HIP_WTA_CONSENSUS_ANY"), *ew = getenv("MGM_HIP_WTA_CONSENSUS_WG");
+    const ConsensusChoice choice = plan_wta_consensus(ConsensusRequest{w.npix, w.L, w.Lk, NDIR, c->num_cu, rel ? w.Lk : 0, (ea && atoi(ea) != 0) ? 1 : 0,
+                                                                       ew ? std::max(0, atoi(ew)) : 0, (!rel && C->rlo) ? 1 : 0});
+    TimeScope t(c, "k_wta_consensus");
+    // (a second name with the same time: which family ran -- tests assert the route and that the forcing switch was honoured)
+    t.kernel = choice.family == kConsensusAny ? "k_wta_consensus_any" : (choice.family == kConsensusRel ? "k_wta_consensus_rel" : "k_wta_consensus_stream");
+    if (hipError_t e = launch_wta_consensus(w, choice, c->stream)) return hipfail(c, e, "launch_wta_consensus(w, c->stream)");
+    return MGM_OK;
+}
+
 // K4-K6 with any refinement of the reference's table: none/vfit are fused into k_wta; parabola, cubic and
 // parabolaOCV (refine.h:6-145) run as a second kernel on the corrected S (the caller's, or a scratch volume).
 int run_wta_refine(mgm_ctx *c, const mgm_cv *C, long long pix0, long long npix, const float *lr, long long lr_stride,

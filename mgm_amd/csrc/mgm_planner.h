@@ -979,6 +979,65 @@ inline RunnerupChoice plan_wta_runnerup(const RunnerupRequest &q)
     return c;
 }
 
+// the consensus votes (k_wta_consensus<LPL, PPW, MAXD> / k_wta_consensus_any / k_wta_consensus_rel<SPL>, mgm_consensus.hip)
+struct ConsensusRequest {
+    long long npix;  // pixels of the call
+    int L, Lk, NDIR, num_cu;    // labels that exist, label stride, passes; compute units of the device (0: unknown)
+    int slots;                  // 0: the dense layout; 64 / 128: the range-proportional layout with that many label slots per pixel (L, Lk are not looked at)
+    int sw_any, sw_wg_per_cu;   // MGM_HIP_WTA_CONSENSUS_ANY=1: the generic kernel everywhere; MGM_HIP_WTA_CONSENSUS_WG=<workgroups per CU> (0: the family's cap)
+    int hull;                   // a ragged volume on its dense hull: the dense kernels mask by the pixel's own range.  No choice depends on it
+                                // today; it is part of the request so that one that does stays this function's decision
+};
+static_assert(std::has_unique_object_representations_v<ConsensusRequest>, "ConsensusRequest: integers only, no padding");
+enum ConsensusFamily { kConsensusRefuse = 0, kConsensusStream, kConsensusAny, kConsensusRel };
+struct ConsensusChoice {
+    long long grid;                   // workgroups of 256 threads
+    int family, LPL, PPW, MAXD, SPL;  // k_wta_consensus<LPL, PPW, MAXD>, k_wta_consensus_rel<SPL>; those an instance does not have are 0
+    int per_wave;                     // pixels a wave takes per turn of its grid-stride loop: PPW, 1 (generic), 4 (range-proportional)
+};
+static_assert(std::has_unique_object_representations_v<ConsensusChoice>, "ConsensusChoice: integers only, no padding");
+constexpr long long kConsensusWgPerCu = kRunnerupWgPerCu, kConsensusRelWgPerCu = 64;  // (plan_wta_runnerup's and plan_wta_rel's caps)
+inline ConsensusChoice plan_wta_consensus(const ConsensusRequest &q)
+{
+    ConsensusChoice c{};
+    if (q.npix < 1 || q.NDIR < 1 || q.NDIR > kMaxDirs || q.sw_wg_per_cu < 0) return c;
+    if (q.slots != 0 && q.slots != 64 && q.slots != 128) return c;
+    if (q.slots == 0 && (q.L < 1 || q.Lk < q.L)) return c;
+    const long long cus = q.num_cu > 0 ? q.num_cu : 256;
+    long long cap = kConsensusWgPerCu;
+    if (q.sw_any != 0) {  // forced: the generic kernel reads either layout
+        c.family = kConsensusAny, c.per_wave = 1;
+    } else if (q.slots != 0) {
+        c.family = kConsensusRel, c.SPL = q.slots / 16, c.per_wave = 4;
+        cap = kConsensusRelWgPerCu;
+    } else {
+        // the instances, their pixels per wave and turn: those of the runner-up search (plan_wta_runnerup), which keeps the costs and
+        // the sum in registers besides -- what fits there fits here
+        const int lpl = q.Lk % 64 == 0 ? q.Lk / 64 : 0;
+        int ppw = 0;
+        switch (lpl) {
+            case 1: case 2: ppw = 4; break;
+            case 3: ppw = 2; break;
+            case 4: ppw = 3; break;
+            case 6: case 8: case 12: case 16: ppw = 1; break;
+            default: break;
+        }
+        if (ppw == 0) {  // any other stride (no multiple of 64, beyond 1024 labels)
+            c.family = kConsensusAny, c.per_wave = 1;
+        } else {
+            c.family = kConsensusStream, c.LPL = lpl, c.PPW = ppw, c.MAXD = kMaxDirs;
+            if (lpl <= 8 && q.NDIR <= 4) c.PPW = 2 * ppw, c.MAXD = 4;  // at most 4 directions: twice the slabs fit the registers
+            c.per_wave = c.PPW;
+        }
+    }
+    // A bounded grid (workgroups of 4 waves), grid-stride beyond it: exactly the waves the pixels need, at most the cap of the search
+    // that reads the same volumes the same way (plan_wta_runnerup's; plan_wta_rel's on the range-proportional layout).  Neither
+    // figure has been measured for these kernels.  The switch lowers the cap so that small volumes take several turns of the loop (tests).
+    const long long waves = (q.npix + c.per_wave - 1) / c.per_wave;
+    c.grid = std::min((waves + 3) / 4, cus * (q.sw_wg_per_cu > 0 ? q.sw_wg_per_cu : cap));
+    return c;
+}
+
 // the search on the range-proportional layout (k_wta_rel<SPL, CB>): label slots per lane, bytes per cost code
 struct WtaRelRequest {
     long long npix, num_cu;

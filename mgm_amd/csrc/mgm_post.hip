@@ -175,6 +175,22 @@ hipError_t launch_uniqueness(const float *d, const float *cost1, const float *co
     return hipGetLastError();
 }
 
+// The consensus filter on the votes of mgm_wta_consensus_dev: out = votes < (float)minvotes ? NaN : d, so a NaN vote
+// count keeps d.  Both inputs are read before anything is written: out may be d.
+__global__ void __launch_bounds__(256) k_consensus_filter(const float *d, const float *__restrict__ votes, long long n, float minvotes, float *out)
+{
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float v = d[i], k = votes[i];
+    out[i] = k < minvotes ? __builtin_nanf("") : v;
+}
+
+hipError_t launch_consensus_filter(const float *d, const float *votes, long long n, int minvotes, float *out, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_consensus_filter, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, d, votes, n, (float)minvotes, out);
+    return hipGetLastError();
+}
+
 __global__ void __launch_bounds__(256) k_backproject(const float *__restrict__ u, int nx, int ny, int nch,
                                                      const float *__restrict__ v, int vnx, int vny,
                                                      const float *__restrict__ disp, float *__restrict__ out)

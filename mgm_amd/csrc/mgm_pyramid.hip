@@ -314,7 +314,7 @@ struct MsState {
     std::vector<mgm_img *> blo[2], bhi[2];  // base ranges per run [s] (null: uniform run -- no images needed at that level)
     mgm_img *prev[2] = {nullptr, nullptr};  // the coarser level's final maps
     // the current level
-    mgm_img *lo[2] = {}, *hi[2] = {}, *w[2] = {}, *out[2] = {}, *cost[2] = {}, *spare[2] = {}, *ilo = nullptr, *ihi = nullptr;
+    mgm_img *lo[2] = {}, *hi[2] = {}, *w[2] = {}, *out[2] = {}, *cost[2] = {}, *spare[2] = {}, *ilo = nullptr, *ihi = nullptr, *votes = nullptr;
     mgm_cv *C[2] = {};
     explicit MsState(mgm_ctx *ctx) : c(ctx) {}
     void free_level(bool keep_out)
@@ -331,7 +331,7 @@ struct MsState {
                 out[k] = nullptr;
             }
         }
-        for (mgm_img **im : {&ilo, &ihi}) {
+        for (mgm_img **im : {&ilo, &ihi, &votes}) {
             mgm_img_free(c, *im);
             *im = nullptr;
         }
@@ -500,7 +500,18 @@ int ms_run(mgm_ctx *c, const mgm_img *u0, const mgm_img *v0, const mgm_ms_params
                 mgm_img_free(c, st.ihi);
                 st.ilo = st.ihi = nullptr;
             }
+            // the consensus votes: the finest level only, on the run's map as its search, refinement and iterations left
+            // it; the aggregation the context holds is this run's (or the launch both runs shared)
+            if (finest && (p.consensus_min > 0 || (k == 0 && p.votesL))) {
+                mgm_img *vt = (k == 0 && p.votesL) ? p.votesL : nullptr;
+                if (!vt && (r = mgm_img_create(c, O[k]->nx, O[k]->ny, 1, &st.votes))) return r;
+                if ((r = mgm_wta_consensus_dev(c, st.C[k], p.NDIR, O[k], p.consensus_tol, vt ? vt : st.votes, nullptr))) return r;
+                if (p.consensus_min > 0 && (r = mgm_consensus_filter_dev(c, O[k], vt ? vt : st.votes, p.consensus_min, O[k]))) return r;
+                mgm_img_free(c, st.votes);
+                st.votes = nullptr;
+            }
         }
+        if (finest && p.iterations == 0 && p.votesL) HIPCHK(c, launch_fill(p.votesL->d, (long long)p.votesL->nx * p.votesL->ny, 0.0f, c->stream));
         // MEDIAN, the map before the left-right test, the two tests on copies of the unchecked maps (mgm.cc:396-423)
         for (int k = 0; k < nrun; k++) {
             if (p.median != 0 || nrun == 2)
@@ -555,10 +566,15 @@ extern "C" int mgm_multiscale_pair_dev(mgm_ctx *c, const mgm_img *u, const mgm_i
             return fail(c, MGM_ERR_INVALID, "mgm_multiscale_pair: outR / costR must have the right image's size");
     if (p.outR_nolr && (p.outR_nolr->nx != v->nx || p.outR_nolr->ny != v->ny || p.outR_nolr->nch != 1))
         return fail(c, MGM_ERR_INVALID, "mgm_multiscale_pair: outR_nolr must have the right image's size");
+    if (p.consensus_min < 0) return fail(c, MGM_ERR_INVALID, "mgm_multiscale_pair: consensus_min must be >= 0");
+    if ((p.consensus_min > 0 || p.votesL) && (!(p.consensus_tol >= 0.0f) || !std::isfinite(p.consensus_tol)))
+        return fail(c, MGM_ERR_INVALID, "mgm_multiscale_pair: consensus_tol must be finite and >= 0");
+    if (p.votesL && (p.votesL->nx != u->nx || p.votesL->ny != u->ny || p.votesL->nch != 1))
+        return fail(c, MGM_ERR_INVALID, "mgm_multiscale_pair: votesL must be nx*ny");
     {
-        const mgm_img *outs[6] = {outL, costL, outR, costR, outL_nolr, p.outR_nolr};
-        for (int a = 0; a < 6; a++)
-            for (int b = a + 1; b < 6; b++)
+        const mgm_img *outs[7] = {outL, costL, outR, costR, outL_nolr, p.outR_nolr, p.votesL};
+        for (int a = 0; a < 7; a++)
+            for (int b = a + 1; b < 7; b++)
                 if (outs[a] && outs[a] == outs[b]) return fail(c, MGM_ERR_INVALID, "mgm_multiscale_pair: the output images must be different images");
     }
     HIPCHK(c, hipSetDevice(c->device));

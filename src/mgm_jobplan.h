@@ -48,6 +48,9 @@ struct JobPlan {
     int fill_dirs = 8;        // MGM_FILL_HOLES_DIRS: 2, 4 or 8 rays
     int fill_dist = 0;        // MGM_FILL_HOLES_DIST: a candidate is at most this many steps away (0: no limit)
     std::string fill_occ;     // MGM_FILL_HOLES_OCC: the occlusions' rule -- the holes are classified, `fill` is the mismatches' (empty: off)
+    std::string votes_file;   // -C: the left->right run's consensus votes (empty: off)
+    int consensus = 0;        // MGM_CONSENSUS: each run's map is NaN where fewer than this many passes vote for it (0: off)
+    float consensus_tol = 1;  // MGM_CONSENSUS_TOL: a pass votes when its own winner is at most this many labels from the map
     // ---- derived from the environment
     // main()'s loops are `for (int i = 0; i < TSGM_ITER(); i++)` on a DOUBLE (mgm.cc:377, 406): ceil() iterations; none at
     // all for TSGM_ITER <= 0 -- the maps then stay the zero images they were allocated as (mgm.cc:360-365)
@@ -76,7 +79,7 @@ using EnvLookup = std::function<const char *(const char *)>;
 enum Blocker { B_RANGED, B_SCALES, B_ITER, B_REFINE, B_RFL, B_DEVICES, N_BLOCKERS };  // (in the order they are looked at)
 static const char *const BLOCKER_NAME[N_BLOCKERS] = {
     "range images (-m/-M)", "-S > 1", "TSGM_ITER != 1", "a refinement other than none or vfit", "MGM_RIGHT_FROM_LEFT=1", "several MGM_DEVICES"};
-enum Mode { M_RFL, M_UQ, M_SUBPIX, N_MODES };  // (as well)
+enum Mode { M_RFL, M_UQ, M_SUBPIX, M_CONSENSUS, N_MODES };  // (as well)
 static const struct {
     const char *name;
     bool blocked_by[N_BLOCKERS];
@@ -85,6 +88,7 @@ static const struct {
     {"MGM_RIGHT_FROM_LEFT=1", {true, true, true, true, false, true}},
     {"-c / MGM_UNIQUENESS", {true, true, true, false, false, true}},
     {"MGM_SUBPIX", {true, true, true, false, true, true}},
+    {"-C / MGM_CONSENSUS", {false, false, false, false, false, true}},
 };
 
 // "mgm: <mode> does not combine with <blocker>\n" for the first mode that is on and its first blocker that holds; else empty
@@ -222,7 +226,13 @@ inline JobPlan plan_job(const std::vector<std::string> &tokens, const EnvLookup 
     if (!(p.uniq >= 0 && p.uniq <= 1)) return end(1, nullptr, "mgm: MGM_UNIQUENESS must be a ratio in [0, 1]\n");
     if (p.uniq_radius < 0) return end(1, nullptr, "mgm: MGM_UNIQUENESS_RADIUS must be >= 0\n");
     const auto whole = [](double x) { return x >= 0 && x <= 2147483647.0 && x == std::floor(x); };
-    double n, df, nd, dist;
+    double n, df, nd, dist, cs, ct;
+    p.votes_file = pick_option(&argc, argv, "C", "");
+    if (!env_strict(env, "MGM_CONSENSUS", 0, &cs) || !whole(cs)) return end(1, nullptr, "mgm: MGM_CONSENSUS must be an integer >= 0 (passes; 0: off)\n");
+    if (!env_strict(env, "MGM_CONSENSUS_TOL", 1, &ct) || !(ct >= 0) || !std::isfinite(ct) || !std::isfinite((float)ct))
+        return end(1, nullptr, "mgm: MGM_CONSENSUS_TOL must be a finite number >= 0 (labels)\n");
+    p.consensus = (int)cs;
+    p.consensus_tol = (float)ct;
     if (!env_strict(env, "MGM_SPECKLE", 0, &n) || !whole(n)) return end(1, nullptr, "mgm: MGM_SPECKLE must be an integer >= 0 (pixels)\n");
     if (!env_strict(env, "MGM_SPECKLE_DIFF", 1, &df) || !(df >= 0)) return end(1, nullptr, "mgm: MGM_SPECKLE_DIFF must be a number >= 0\n");
     p.speckle = (int)n;
@@ -294,7 +304,7 @@ inline JobPlan plan_job(const std::vector<std::string> &tokens, const EnvLookup 
         }
     }
 
-    const bool mode[N_MODES] = {p.rfl, p.uq, o.subpix > 1};
+    const bool mode[N_MODES] = {p.rfl, p.uq, o.subpix > 1, p.consensus != 0 || !p.votes_file.empty()};
     const bool blocker[N_BLOCKERS] = {p.ranged, p.nscales > 1, p.iterations != 1, o.refine == "parabola" || o.refine == "cubic" || o.refine == "parabolaOCV",
                                       p.rfl, p.devices_comma};
     p.err_text = first_exclusion(mode, blocker);
@@ -317,7 +327,7 @@ struct Refusal {
 };
 inline Refusal refuse_on_session(const JobPlan &p, bool multi_up, int u_ny, int v_ny)
 {
-    const bool mode[N_MODES] = {p.rfl, p.uq, p.o.subpix > 1};
+    const bool mode[N_MODES] = {p.rfl, p.uq, p.o.subpix > 1, p.consensus != 0 || !p.votes_file.empty()};
     bool blocker[N_BLOCKERS] = {};
     blocker[B_DEVICES] = multi_up;
     Refusal r;

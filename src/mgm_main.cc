@@ -8,6 +8,10 @@
 // computed on the CPU.  Image files (src/imgio.h): PNG, TIFF, PGM/PPM, PFM and .npy in -- what the
 // reference's iio decodes them to -- and float TIFF, PFM or .npy out.
 //
+// This program's own modes beside the reference's options (each documented in README.md and DESIGN.md 7a-7h): -S, -c, -C FILE /
+// MGM_CONSENSUS=k / MGM_CONSENSUS_TOL=1 (the consensus votes, 7h: how many passes vote for a run's map; `--help` does not name these
+// three yet), MGM_RIGHT_FROM_LEFT, MGM_UNIQUENESS, MGM_SPECKLE, MGM_FILL_HOLES*, MGM_SUBPIX.
+//
 // A command line is a JOB with three stages: DECODE (host: the input files -> planar float images), DEVICE (this thread:
 // uploads, every kernel of the path, downloads; the job's stdout is written here, in order) and ENCODE (host: the output
 // files).  A 1920x1080x256 pair is ~17 ms of device work between ~19 ms of decoding and ~9 ms of encoding, so the program
@@ -319,6 +323,19 @@ static void uniqueness_run(mgm_ctx *ctx, const Opts &o, Run &r, float ratio, int
         die(ctx, rc, "mgm_uniqueness");
 }
 
+// -C / MGM_CONSENSUS, right behind the search, the refinement and the last iteration of `r` and before its map
+// is rescaled (MGM_SUBPIX: the tolerance is per fine label): how many passes of the aggregation the context still holds vote
+// for the run's map, into *votes (if wanted) and, with minvotes > 0, NaN into the map wherever fewer do
+static void consensus_run(mgm_ctx *ctx, const Opts &o, Run &r, float tol, int minvotes, mgm_img **votes)
+{
+    ImgHold mine{ctx};
+    int rc;
+    if ((rc = mgm_img_create(ctx, r.nx, r.ny, 1, votes ? votes : &mine.im))) die(ctx, rc, "mgm_img_create");
+    mgm_img *vt = votes ? *votes : mine.im;
+    if ((rc = mgm_wta_consensus_dev(ctx, r.C, o.NDIR, r.dout, tol, vt, nullptr))) die(ctx, rc, "mgm_wta_consensus");
+    if (minvotes > 0 && (rc = mgm_consensus_filter_dev(ctx, r.dout, vt, minvotes, r.dout))) die(ctx, rc, "mgm_consensus_filter");
+}
+
 // MGM_SPECKLE=maxsize: the speckle filter, in place, on a job's FINAL left map
 static void speckle_map(mgm_ctx *ctx, mgm_img *d, int maxsize, float maxdiff)
 {
@@ -384,7 +401,7 @@ struct Job {
     HostImg u, v, rlo, rhi;
     std::exception_ptr decode_err;
     // results of the device stage
-    HostImg outoff, outcost, syn, nolr, conf;
+    HostImg outoff, outcost, syn, nolr, conf, votes;
     int rc = 0;  // the job's exit code
 };
 
@@ -430,6 +447,7 @@ static void encode_job(Job &j)
     try {
         if (!p.nolr_file.empty()) imgio::write(p.nolr_file, j.nolr);
         if (!p.conf_file.empty()) imgio::write(p.conf_file, j.conf);
+        if (!p.votes_file.empty()) imgio::write(p.votes_file, j.votes);
         imgio::write(p.f_out, j.outoff);
         if (!p.f_cost.empty()) imgio::write(p.f_cost, j.outcost);
         if (!p.f_back.empty()) imgio::write(p.f_back, j.syn);
@@ -515,7 +533,7 @@ static void multiscale_job(Session &S, Job &j, const Opts &o, const HostImg *plo
     free_run(ctx, S.L);
     const HostImg &u = j.u, &v = j.v;
     // (rnolr -- MGM_FILL_HOLES_OCC: the full-size right map before its left-right test)
-    ImgHold rnolr{ctx}, nolr{ctx}, cost{ctx}, out{ctx}, dhi{ctx}, dlo{ctx}, dv{ctx}, du{ctx};
+    ImgHold votes{ctx}, rnolr{ctx}, nolr{ctx}, cost{ctx}, out{ctx}, dhi{ctx}, dlo{ctx}, dv{ctx}, du{ctx};
     int rc;
     if ((rc = mgm_img_upload(ctx, u.data.data(), u.nx, u.ny, u.nch, &du.im)) || (rc = mgm_img_upload(ctx, v.data.data(), v.nx, v.ny, v.nch, &dv.im)))
         die(ctx, rc, "upload");
@@ -524,6 +542,7 @@ static void multiscale_job(Session &S, Job &j, const Opts &o, const HostImg *plo
     for (mgm_img **im : {&out.im, &cost.im}) image_like(ctx, u.nx, u.ny, 1, im);
     if (!pl.nolr_file.empty()) image_like(ctx, u.nx, u.ny, 1, &nolr.im);
     if (!pl.fill_occ.empty()) image_like(ctx, v.nx, v.ny, 1, &rnolr.im);
+    if (!pl.votes_file.empty()) image_like(ctx, u.nx, u.ny, 1, &votes.im);
     mgm_ms_level levels[8] = {};
     int nlev = 0;
     mgm_ms_params p{};
@@ -540,6 +559,7 @@ static void multiscale_job(Session &S, Job &j, const Opts &o, const HostImg *plo
     p.iterations = pl.iterations, p.median = (int)pl.median, p.testlrrl = pl.both, p.tau = pl.tau;
     p.levels_run = &nlev, p.levels = levels;
     p.outR_nolr = rnolr.im;
+    p.consensus_tol = pl.consensus_tol, p.consensus_min = pl.consensus, p.votesL = votes.im;
     sw.mark("upload");
     if ((rc = mgm_multiscale_pair_dev(ctx, du.im, dv.im, &p, out.im, cost.im, nullptr, nullptr, nolr.im))) die(ctx, rc, "mgm_multiscale_pair");
     for (int s = nlev - 1; s >= 0; s--)
@@ -553,6 +573,7 @@ static void multiscale_job(Session &S, Job &j, const Opts &o, const HostImg *plo
     // (speckle and fill: once, on level 0's final map)
     finish_job(ctx, j, out.im, rnolr.im, cost.im, nullptr, du.im, dv.im, sw, [&] {
         if (!pl.nolr_file.empty()) j.nolr = download(ctx, nolr.im, u.nx, u.ny, 1);
+        if (!pl.votes_file.empty()) j.votes = download(ctx, votes.im, u.nx, u.ny, 1);
     });
     sw.mark("download(rest)");
 }
@@ -616,6 +637,8 @@ static int device_job(Session &S, Job &j, const std::function<void()> &decoded, 
         int rc;
         Run &L = S.L, &R = S.R;
         ImgHold dconf{ctx};  // -c: the confidence map, until it is downloaded
+        ImgHold dvotes{ctx};  // -C: the votes map, until it is downloaded
+        const bool cs = p.consensus != 0 || !p.votes_file.empty();
         const int ITER = p.iterations;
         const bool both = p.both, rfl = p.rfl;
         if (p.nscales > 1) {
@@ -661,6 +684,7 @@ static int device_job(Session &S, Job &j, const std::function<void()> &decoded, 
             else if (!together) aggregate_run(ctx, o, L);
             report_run(o, L);
             iterate_run(ctx, o, L, ITER, o.dmin, o.dmax, plo, phi);
+            if (cs) consensus_run(ctx, o, L, p.consensus_tol, p.consensus, p.votes_file.empty() ? nullptr : &dvotes.im);
             rescale_run(ctx, o, L);
             if (p.uq) uniqueness_run(ctx, o, L, (float)p.uniq, p.uniq_radius, p.conf_file.empty() ? nullptr : &dconf.im);
         }
@@ -685,6 +709,7 @@ static int device_job(Session &S, Job &j, const std::function<void()> &decoded, 
                 else if (!together) aggregate_run(ctx, o, R);
                 report_run(o, R);
                 iterate_run(ctx, o, R, ITER, -o.dmax, -o.dmin);
+                if (p.consensus != 0) consensus_run(ctx, o, R, p.consensus_tol, p.consensus, nullptr);
                 rescale_run(ctx, o, R);
                 if (p.uniq != 0) uniqueness_run(ctx, o, R, (float)p.uniq, p.uniq_radius, nullptr);
             }
@@ -702,6 +727,14 @@ static int device_job(Session &S, Job &j, const std::function<void()> &decoded, 
         // (with several devices `ctx` is the device that holds the gathered map; after the swap above R.dspare is the right map as it
         // entered the left-right test)
         finish_job(ctx, j, L.dout, R.dspare, L.dcost, dconf.im, L.du, L.dv, sw, [&] { sw.mark("enqueue(rest)"); });
+        if (!p.votes_file.empty()) {  // (no iteration: mgm() was never called, no pass has voted)
+            if (!dvotes.im) {
+                image_like(ctx, u.nx, u.ny, 1, &dvotes.im);
+                const std::vector<float> z((size_t)u.npix(), 0.0f);
+                if ((rc = mgm_img_update(ctx, dvotes.im, z.data()))) die(ctx, rc, "upload");
+            }
+            j.votes = download(ctx, dvotes.im, u.nx, u.ny, 1);
+        }
         sw.mark("download(rest)");
         if (p.kernels && !multi) report_kernels(ctx);
     } catch (const std::exception &e) {  // (a DeviceError, an unreadable input)
@@ -823,7 +856,7 @@ static int run_batch(const char *file)
         for (size_t m = 0; m < k; m++) {
             const JobPlan &e = jobs[m]->p;
             for (const std::string *in : {&j.f_u, &j.f_v, &j.min_file, &j.max_file})
-                for (const std::string *out : {&e.f_out, &e.f_cost, &e.f_back, &e.nolr_file, &e.conf_file})
+                for (const std::string *out : {&e.f_out, &e.f_cost, &e.f_back, &e.nolr_file, &e.conf_file, &e.votes_file})
                     if (!in->empty() && *in == *out) needs[k] = m + 1;
         }
     }
@@ -856,7 +889,7 @@ static int run_batch(const char *file)
                 bad = 1;
             }
             // the job is done: its images go
-            j.u = j.v = j.rlo = j.rhi = j.outoff = j.outcost = j.syn = j.nolr = j.conf = HostImg();
+            j.u = j.v = j.rlo = j.rhi = j.outoff = j.outcost = j.syn = j.nolr = j.conf = j.votes = HostImg();
             {
                 std::lock_guard<std::mutex> lk(mu);
                 written = k + 1;
