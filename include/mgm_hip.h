@@ -485,6 +485,54 @@ int mgm_classify_holes_dev(mgm_ctx *ctx, const mgm_img *d, const mgm_img *other,
  * call as k_holes.  The class map is the caller's image: the command line has no file option for it. */
 int mgm_fill_holes_classified_dev(mgm_ctx *ctx, const mgm_img *d, const mgm_img *cls, const char *mode_occ, const char *mode_mis,
                                   int dirs, int maxdist, mgm_img *out, mgm_img *filled);
+/* Solution energy (DESIGN.md "solution energy"): what a disparity map d costs in the terms of the functional that the aggregation
+ * minimises -- the reference's three figures (evaluate_energy_4connected, mgm_print_energy.h:17-96; what TSGM_DEBUG=1 prints) and this
+ * library's own model energy.  C is the cost volume of the run (for a sub-pixel fine volume d is in fine labels too), d any
+ * nx x ny x 1 map.  All per-pixel arithmetic is fp32, one rounding per operation, nothing contracted.
+ *   C(p, l)      the cost of label l at pixel p; +INF for a label the pixel does not own: outside [dmin, dmax], outside the pixel's
+ *                own range of a ragged volume, and for a d(p) that is not finite or has |d(p)| >= 2^24
+ *   kinds 0-2    o = d(p); G = 0 + C(p, (int)o) (truncation); then for t = 0..3 with r = p + dir[t], q = p + dir[t+1], dirs (-1,0) (0,1)
+ *                (1,0) (0,-1) (-1,0), skipped unless BOTH r and q lie inside the image (so a one-pixel-wide or one-row map has no
+ *                edge term at all):
+ *                  kind 0 (truncated L1)  G += (fabsf(d(r) - o) <= 1 ? P1 : P2) / 4
+ *                  kind 1 (L1)            G += fabsf(d(r) - o) / 4
+ *                  kind 2 (L2)            G += sqrtf((d(r) - o)^2 + (d(q) - o)^2) / 4      (correctly rounded)
+ *                E(p) = G.  Whatever IEEE gives: a NaN neighbour makes kinds 1 and 2 NaN and takes the P2 branch of kind 0.  (The
+ *                reference's file /tmp/ENERGY_L1trunc.tif holds the L1 map under that name; here E of kind 0 is the truncated map.)
+ *   kind 3       the model energy over the first `connectivity` (4 or 8) neighbours in the order of the weight planes, W E S N NW NE
+ *                SE SW.  d(p) not finite: E(p) = NaN.  Else data = C(p, (int)rintf(d(p))); for each k whose neighbour q lies inside
+ *                the image and has a finite d(q): a = fabsf(d(q) - d(p)), w = w8[k](p) (1 without w8),
+ *                  use_fh = 0 (Hirschmueller)      V = a == 0 ? 0 : a <= 1 ? fminf(P1*w, P2*w) : P2*w
+ *                  use_fh = 1 (truncated linear)   V = fminf((P1*w) * a, P2*w)
+ *                smooth = 0.5f * (((0 + V_k0) + V_k1) + ...) in k order, E(p) = data + smooth.  Every undirected edge is counted from
+ *                both ends at half weight: the total is sum data + sum over edges of mean(w_pq, w_qp) * V, whatever the weights are.
+ *                It is the energy of the pairwise functional, NOT of MGM's message sums: MGM minimises it approximately.
+ *   totals       serial: the fp32 sum of E in raster order, 0 + E(0) + E(1) + ... -- the number the reference prints, formed on the
+ *                host from the map the device wrote.  total, data, smooth: fp64 sums of E, of the data terms and of the edge terms
+ *                (kinds 0-2: 0 + t_0 + t_1 ... in fp32 per pixel; kind 3: smooth) over the pixels with a finite d(p), which `finite`
+ *                counts; `pixels` = nx * ny.  One fp64 partial per block of 256 pixels in raster order, added in index order: no float
+ *                atomics, two calls give the same bits.
+ * The volume is read in whatever copy is current (fp32, one- or two-byte codes, the padded compact copy, the range-proportional
+ * copy of a ragged volume that has no other): one cost per pixel, nothing is decoded, made or checked.  E and t may each be NULL,
+ * not both.  With t the call synchronises; without it it does not.  It leaves what the context holds of its last aggregation
+ * untouched.  MGM_ERR_INVALID: a null argument, kind outside 0..3, P1 negative or not finite, P2 negative or NaN (+INF is valid),
+ * kind 3 with a connectivity other than 4 or 8, d or E not nx x ny x 1 of the volume's size, E == d, w8 not nx x ny x 8, a volume
+ * whose refill failed.  More than 2^31 - 1 pixels: MGM_ERR_UNSUPPORTED.  The timing table lists the call as k_energy.
+ * The command line: TSGM_DEBUG=1 prints the reference's debug lines, the three figures of every iteration and run among them;
+ * MGM_ENERGY=4|8 prints the model energy of each run and iteration on stderr, MGM_ENERGY_MAP=FILE writes the left run's last map of it. */
+typedef struct mgm_energy_params {
+    int kind;            /* 0 L1trunc, 1 L1, 2 L2: evaluate_energy_4connected; 3: the model energy */
+    float P1, P2;        /* as given (the caller has multiplied by the channel count) */
+    int connectivity;    /* kind 3: 4 or 8 */
+    int use_fh;          /* kind 3: 0 Hirschmueller, 1 truncated linear */
+    const mgm_img *w8;   /* kind 3: NULL (ones) or the 8-channel weight image of mgm_weights_dev / a caller's own */
+} mgm_energy_params;
+typedef struct mgm_energy_totals {
+    float serial;        /* fp32 sum of the map in raster order: what the reference returns */
+    double total, data, smooth;       /* fp64 sums over the pixels counted in `finite` */
+    unsigned long long finite, pixels;
+} mgm_energy_totals;
+int mgm_energy_dev(mgm_ctx *ctx, const mgm_cv *C, const mgm_img *d, const mgm_energy_params *p, mgm_img *E, mgm_energy_totals *t);
 /* update_dmin_dmax (mgm.cc:120-158; main() uses slack 3, radius 2) followed by the two
  * remove_nonfinite_values_Img calls (mgm.cc:387-388): dminI/dmaxI are updated in place from the disparity map. */
 int mgm_update_ranges_dev(mgm_ctx *ctx, const mgm_img *outoff, mgm_img *dminI, mgm_img *dmaxI, int slack, int radius);

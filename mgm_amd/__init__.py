@@ -37,7 +37,7 @@ ABI_SYMBOLS = [
     "mgm_classify_holes_dev", "mgm_fill_holes_classified_dev",
     "mgm_subpix_phase_dev", "mgm_costvolume_build_subpix_dev", "mgm_subpix_scale_dev",
     "mgm_debug_rel_lr_device_ptr", "mgm_debug_wta_rel_again_dev", "mgm_debug_lr_device_ptr",
-    "mgm_wta_consensus_dev", "mgm_consensus_filter_dev",
+    "mgm_wta_consensus_dev", "mgm_consensus_filter_dev", "mgm_energy_dev",
 ]
 
 MGM_OK, MGM_ERR_INVALID, MGM_ERR_UNSUPPORTED, MGM_ERR_HIP, MGM_ERR_NOMEM, MGM_ERR_INTERNAL = range(6)
@@ -72,6 +72,20 @@ class MsParams(C.Structure):
 class MsParamsConsensus(C.Structure):
     """``mgm_ms_params`` as it has grown at its end: ``MsParams`` (kept as the struct of an older caller) and the consensus fields."""
     _fields_ = MsParams._fields_ + [("consensus_tol", C.c_float), ("consensus_min", C.c_int), ("votesL", C.c_void_p)]
+
+
+class EnergyParams(C.Structure):
+    """``mgm_energy_params``."""
+    _fields_ = [("kind", C.c_int), ("P1", C.c_float), ("P2", C.c_float), ("connectivity", C.c_int), ("use_fh", C.c_int), ("w8", C.c_void_p)]
+
+
+class EnergyTotals(C.Structure):
+    """``mgm_energy_totals``."""
+    _fields_ = [("serial", C.c_float), ("total", C.c_double), ("data", C.c_double), ("smooth", C.c_double), ("finite", C.c_ulonglong),
+                ("pixels", C.c_ulonglong)]
+
+
+ENERGY_KINDS = {"l1trunc": 0, "l1": 1, "l2": 2, "model": 3}
 
 
 def load_library():
@@ -130,6 +144,7 @@ def load_library():
     L.mgm_wta_consensus_dev.argtypes = [vp, vp, i, vp, f, vp, vp]
     L.mgm_consensus_filter_dev.argtypes = [vp, vp, vp, i, vp]
     L.mgm_speckle_dev.argtypes = [vp, vp, i, f, vp, vp]
+    L.mgm_energy_dev.argtypes = [vp, vp, vp, C.POINTER(EnergyParams), vp, C.POINTER(EnergyTotals)]
     L.mgm_fill_holes_dev.argtypes = [vp, vp, cp, i, i, vp, vp]
     L.mgm_classify_holes_dev.argtypes = [vp, vp, vp, i, i, f, vp]
     L.mgm_fill_holes_classified_dev.argtypes = [vp, vp, vp, cp, cp, i, i, vp, vp]
@@ -487,6 +502,28 @@ class Context:
                 im.free()
             raise
         return (out if out else None), size_map
+
+    def energy_dev(self, Cv, d, kind, P1, P2, connectivity=4, use_fh=0, w8=None, want_map=True, want_totals=True):
+        """The energy of the map d on the volume Cv (mgm_energy_dev).  kind: 0 / "l1trunc", 1 / "l1", 2 / "l2" -- the reference's
+        evaluate_energy_4connected -- or 3 / "model": data term plus the weighted potentials of the run's kind (use_fh) over 4 or 8
+        neighbours, w8 None (ones) or an 8-channel weight image.  P1 / P2 as given (already multiplied by the channel count).
+        Returns (map, totals): a new device image or None, and a dict (serial: the fp32 sum in raster order; total, data, smooth:
+        fp64 sums over the finite pixels; finite, pixels) or None.  Asking for the totals synchronises."""
+        _, ny, nx = d.shape
+        q = EnergyParams(ENERGY_KINDS.get(kind, kind) if isinstance(kind, str) else int(kind), P1, P2, connectivity, use_fh, w8.h if w8 is not None else None)
+        tot = EnergyTotals()
+        mine = []  # the image made here: freed if the call fails
+        try:
+            E = None
+            if want_map:
+                E = self.new_image(nx, ny)
+                mine.append(E)
+            self._chk(self.lib.mgm_energy_dev(self.h, Cv.h, d.h, C.byref(q), E.h if E else None, C.byref(tot) if want_totals else None))
+        except Exception:
+            for im in mine:
+                im.free()
+            raise
+        return E, ({f: getattr(tot, f) for f, _ in EnergyTotals._fields_} if want_totals else None)
 
     def fill_holes_dev(self, d, mode="median", dirs=8, maxdist=0, out=None, want_filled=False):
         """Hole filling (mgm_fill_holes_dev): every non-finite pixel of d takes the median / min / max of the nearest finite pixels

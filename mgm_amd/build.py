@@ -24,7 +24,7 @@ REL_EXTRA = os.environ.get("MGM_REL_DEFINES", "").split()  # e.g. "-DMGM_REL_PHA
 UNITS = [("mgm_pass.hip", "", ["-fno-honor-nans"]), ("mgm_pass_rel.hip", "", ["-fno-honor-nans"] + REL_EXTRA)]
 P2_EXTRA = os.environ.get("MGM_P2_DEFINES", "").split()  # e.g. "-DMGM_P2_MAXD=3" (tuning experiments)
 UNITS += [("mgm_pass2.hip", "_lpl%d" % n, ["-fno-honor-nans", "-DMGM_P2_LPL=%d" % n] + P2_EXTRA) for n in (1, 2, 3, 4, 6, 8, 12, 16)]
-UNITS += [("mgm_pass2_dispatch.hip", "", P2_EXTRA), ("mgm_cost.hip", "", []), ("mgm_cost_fast.hip", "", []), ("mgm_wta.hip", "", []), ("mgm_consensus.hip", "", []), ("mgm_post.hip", "", []), ("mgm_speckle.hip", "", []), ("mgm_holes.hip", "", []), ("mgm_subpix.hip", "", []), ("mgm_pyramid.hip", "", []),
+UNITS += [("mgm_pass2_dispatch.hip", "", P2_EXTRA), ("mgm_cost.hip", "", []), ("mgm_cost_fast.hip", "", []), ("mgm_wta.hip", "", []), ("mgm_consensus.hip", "", []), ("mgm_post.hip", "", []), ("mgm_speckle.hip", "", []), ("mgm_holes.hip", "", []), ("mgm_energy.hip", "", []), ("mgm_subpix.hip", "", []), ("mgm_pyramid.hip", "", []),
           ("mgm_api.hip", "", []), ("mgm_ctx.hip", "", []), ("mgm_volume.hip", "", []), ("mgm_plan.hip", "", []), ("mgm_multi.hip", "", []),
           ("mgm_pass_exact.hip", "", [])]  # (no -fno-honor-nans: this one exists for the NaNs)
 
@@ -55,7 +55,7 @@ def build(force=False, verbose=False):
     os.makedirs(OBJDIR, exist_ok=True)
     cc = hipcc()
     headers = [os.path.join(CSRC, "mgm_device.h"), os.path.join(CSRC, "mgm_pass_common.h"), os.path.join(CSRC, "mgm_lds_dma.h"), os.path.join(CSRC, "mgm_host.h"), os.path.join(CSRC, "mgm_cost_common.h"),
-               os.path.join(CSRC, "mgm_geom.h"), os.path.join(CSRC, "mgm_planner.h"), os.path.join(CSRC, "mgm_fillplan.h"),
+               os.path.join(CSRC, "mgm_geom.h"), os.path.join(CSRC, "mgm_planner.h"), os.path.join(CSRC, "mgm_fillplan.h"), os.path.join(CSRC, "mgm_energyplan.h"),
                os.path.join(HERE, "..", "include", "mgm_hip.h"),
                os.path.abspath(__file__)]
     jobs = []

@@ -875,6 +875,72 @@ int mgm_fill_holes_classified_dev(mgm_ctx *c, const mgm_img *d, const mgm_img *c
     return MGM_OK;
 }
 
+// Solution energy (mgm_energy.hip): plan_energy_copy names the copy of the volume that is current -- none is made,
+// decoded or checked for this --, plan_energy_launch the blocks; one launch.  Totals: the blocks' partials and the map come back,
+// the partials are added in index order and the map in raster order (the reference's fp32 sum has no other form).
+int mgm_energy_dev(mgm_ctx *c, const mgm_cv *C, const mgm_img *d, const mgm_energy_params *q, mgm_img *E, mgm_energy_totals *tot)
+{
+    if (int jr = pipe_join(c)) return jr;  // (pipelined context: run what has been deferred first)
+    if (!c || !C || !d || !q || (!E && !tot)) return fail(c, MGM_ERR_INVALID, "mgm_energy: null argument (at least one of E, totals)");
+    if (q->kind < 0 || q->kind > 3) return fail(c, MGM_ERR_INVALID, "mgm_energy: kind must be 0 (L1trunc), 1 (L1), 2 (L2) or 3 (model)");
+    if (!(q->P1 >= 0.0f && q->P1 < __builtin_inff())) return fail(c, MGM_ERR_INVALID, "mgm_energy: P1 must be finite and >= 0");
+    if (!(q->P2 >= 0.0f)) return fail(c, MGM_ERR_INVALID, "mgm_energy: P2 must be >= 0 (+INF allowed, NaN not)");
+    if (q->kind == 3 && q->connectivity != 4 && q->connectivity != 8) return fail(c, MGM_ERR_INVALID, "mgm_energy: connectivity must be 4 or 8");
+    const mgm_img *w8 = q->kind == 3 ? q->w8 : nullptr;
+    if (d->nx != C->nx || d->ny != C->ny || d->nch != 1) return fail(c, MGM_ERR_INVALID, "mgm_energy: d must be a one-channel map of the volume's size");
+    if (E && (E->nx != d->nx || E->ny != d->ny || E->nch != 1 || E == d)) return fail(c, MGM_ERR_INVALID, "mgm_energy: E must be a one-channel image of d's size, not d");
+    if (w8 && (w8->nx != d->nx || w8->ny != d->ny || w8->nch != 8 || w8 == E)) return fail(c, MGM_ERR_INVALID, "mgm_energy: w8 must have d's size and 8 channels");
+    const EnergyLaunch launch = plan_energy_launch(d->nx, d->ny);
+    if (launch.blocks < 1) return fail(c, MGM_ERR_UNSUPPORTED, "mgm_energy: more than 2^31 - 1 pixels");
+    const long long L = (long long)C->dmax - C->dmin + 1;
+    EnergyCopyRequest rq{};
+    rq.f32_state = C->f32_state, rq.has_f32 = C->d != nullptr;
+    rq.rel_only = C->rel_only, rq.rel_state = (int)C->rel_state, rq.has_rel = C->relbuf != nullptr, rq.rel_slots = C->rel_slots, rq.rel_cb = C->rel_cb;
+    rq.p8_state = (int)C->p8_state, rq.has_p8 = C->p8 != nullptr, rq.p8_L = C->p8_L, rq.p8_cb = C->p8_cb;
+    rq.c8_state = (int)C->c8_state, rq.has_c8 = C->d8 != nullptr, rq.cbytes = C->cbytes;
+    rq.L = (int)L, rq.unfilled = C->unfilled;
+    const EnergyCopyChoice copy = plan_energy_copy(rq);
+    if (copy.copy == kEnergyCopyNone) return fail(c, MGM_ERR_INVALID, "mgm_energy: the cost volume holds no costs (a refill failed, or no copy of it is current)");
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t npix = (size_t)d->nx * d->ny, pbytes = (size_t)launch.partial_bytes;
+    if (tot)
+        if (int r = reserve(c, c->energy, pbytes + (E ? 0 : npix * sizeof(float)))) return r;
+    EnergyParams p{};
+    p.d = d->d;
+    p.E = E ? E->d : (tot ? reinterpret_cast<float *>((char *)c->energy.p + pbytes) : nullptr);
+    p.partials = tot ? c->energy.p : nullptr;
+    p.w8 = w8 ? w8->d : nullptr;
+    p.cost = copy.copy == kEnergyCopyF32 ? (const void *)C->d : copy.copy == kEnergyCopyRel ? (const void *)C->relbuf : copy.copy == kEnergyCopyPadded ? (const void *)C->p8 : (const void *)C->d8;
+    p.records = copy.copy == kEnergyCopyRel ? C->rel_records() : nullptr;
+    p.rlo = C->rlo, p.rhi = C->rlo ? C->rhi : nullptr;
+    p.cb = copy.cb, p.stride = copy.stride, p.dmin = C->dmin, p.L = (int)L;
+    p.nx = d->nx, p.ny = d->ny, p.kind = q->kind, p.connectivity = q->kind == 3 ? q->connectivity : 4, p.use_fh = q->use_fh != 0;
+    p.P1 = q->P1, p.P2 = q->P2;
+    {
+        TimeScope t(c, "k_energy");
+        if (hipError_t e = launch_energy(p, launch.blocks, c->stream)) return hipfail(c, e, "k_energy");
+    }
+    if (!tot) return MGM_OK;
+    std::vector<double> part((size_t)launch.blocks * kEnergyPartialWords);
+    std::vector<float> map(npix);
+    HIPCHK(c, hipMemcpyAsync(part.data(), p.partials, pbytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(map.data(), p.E, npix * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    mgm_energy_totals r{};
+    for (long long b = 0; b < launch.blocks; b++) {  // in index order
+        unsigned long long n;
+        memcpy(&n, &part[(size_t)b * kEnergyPartialWords + 3], sizeof n);
+        r.data += part[(size_t)b * kEnergyPartialWords], r.smooth += part[(size_t)b * kEnergyPartialWords + 1], r.total += part[(size_t)b * kEnergyPartialWords + 2];
+        r.finite += n;
+    }
+    r.pixels = npix;
+    float serial = 0;
+    for (size_t i = 0; i < npix; i++) serial = serial + map[i];  // ENERGY += G (mgm_print_energy.h:74-80)
+    r.serial = serial;
+    *tot = r;
+    return MGM_OK;
+}
+
 // Sub-pixel label spacing (mgm_subpix.hip): the phase image on its own (the build makes its own in the context's
 // scratch) and the rescale of a map from fine labels to pixels.
 int mgm_subpix_phase_dev(mgm_ctx *c, const mgm_img *v, int s, int k, const char *interp, mgm_img **out)

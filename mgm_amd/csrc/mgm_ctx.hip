@@ -190,7 +190,7 @@ bool pipe_uses(const mgm_ctx *c, const void *obj)  // is `obj` (a volume or an i
 static std::vector<Buf *> workspace_bufs(mgm_ctx *c)
 {
     std::vector<Buf *> bufs = {&c->lr, &c->hand.buf, &c->hand2, &c->handm, &c->exact_mins, &c->exact_scratch, &c->census_u, &c->census_v, &c->dbg, &c->stmp, &c->ones8,
-                               &c->lr_rel, &c->hand_rel.buf, &c->lmin, &c->wta_stats, &c->wvals, &c->speckle, &c->holes};
+                               &c->lr_rel, &c->hand_rel.buf, &c->lmin, &c->wta_stats, &c->wvals, &c->speckle, &c->holes, &c->energy};
     for (int v = 0; v < kMaxBatch; v++) bufs.insert(bufs.end(), {&c->padf[v], &c->pad8[v], &c->wsel[v]});
     return bufs;
 }

@@ -159,6 +159,24 @@ enum SpecklePhase { kSpeckleLocal = 0, kSpeckleSeams, kSpeckleCount, kSpeckleApp
 const char *speckle_phase_name(int phase);  // "k_speckle_local", ...
 hipError_t launch_speckle_phase(int phase, const SpeckleParams &p, const SpeckleChoice &c, hipStream_t s);
 
+// solution energy (mgm_energy.hip): per pixel the cost of the map's label plus edge terms over its neighbours --
+// the reference's evaluate_energy_4connected (kinds 0-2) or the pairwise functional of the run (kind 3) -- into E and / or into one
+// fp64 partial per block of kEnergyThreads pixels
+struct EnergyParams {
+    const float *d;  // [nx*ny] the map
+    float *E;        // [nx*ny] the energy map, or nullptr
+    void *partials;  // [blocks][4] 8-byte words: data, smooth, total (fp64), finite pixels (uint64); or nullptr
+    const float *w8;  // kind 3: [8][nx*ny] weights, or nullptr (ones)
+    // the copy of the volume that is read (plan_energy_copy): `stride` cost slots per pixel of `cb` bytes (4: floats; 1 / 2: codes)
+    const void *cost;
+    const int *records;      // range-proportional copy: four ints per pixel (disparity of slot 0, lo, hi, 0); else nullptr
+    const float *rlo, *rhi;  // ragged volume: the range images a pixel owns its labels by; else nullptr
+    int cb, stride, dmin, L;
+    int nx, ny, kind, connectivity, use_fh;
+    float P1, P2;
+};
+hipError_t launch_energy(const EnergyParams &p, long long blocks, hipStream_t s);
+
 // hole filling (mgm_holes.hip): per hole (a non-finite pixel) the nearest finite pixel along each of `dirs` rays of
 // the ORIGINAL map, at most maxdist steps away (0: any); out = their median / minimum / maximum, filled = 1 where a hole got a value
 struct HolesParams {

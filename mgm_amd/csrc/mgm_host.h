@@ -16,6 +16,7 @@
 
 #include "../../include/mgm_hip.h"
 #include "mgm_device.h"
+#include "mgm_energyplan.h"
 #include "mgm_fillplan.h"
 #include "mgm_planner.h"
 
@@ -209,6 +210,7 @@ struct mgm_ctx {
     Buf lmin, wta_stats;  // (wta_stats: kWtaStatBytes)
     Buf speckle;          // mgm_speckle_dev: the parent and count planes of its labelling (plan_speckle's scratch_bytes)
     Buf holes;            // mgm_fill_holes_dev: the candidate planes and the bands' carries (plan_holes's scratch_bytes)
+    Buf energy;           // mgm_energy_dev: the blocks' partials (plan_energy_launch's partial_bytes), then a map when the caller passes none
     // mgm_costvolume_build_subpix_dev: the phase image, refilled in place for every k > 0, and the s phase volumes the
     // fine volume is gathered from; kept for the next call of the same geometry, released by mgm_ctx_trim (subpix_release)
     mgm_img *subpix_img = nullptr;

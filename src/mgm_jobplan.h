@@ -51,6 +51,8 @@ struct JobPlan {
     std::string votes_file;   // -C: the left->right run's consensus votes (empty: off)
     int consensus = 0;        // MGM_CONSENSUS: each run's map is NaN where fewer than this many passes vote for it (0: off)
     float consensus_tol = 1;  // MGM_CONSENSUS_TOL: a pass votes when its own winner is at most this many labels from the map
+    int energy = 0;           // MGM_ENERGY: 4 or 8 neighbours -- the model energy of every run and iteration on stderr (0: off)
+    std::string energy_map;   // MGM_ENERGY_MAP: the left->right run's last map of it (empty: off)
     // ---- derived from the environment
     // main()'s loops are `for (int i = 0; i < TSGM_ITER(); i++)` on a DOUBLE (mgm.cc:377, 406): ceil() iterations; none at
     // all for TSGM_ITER <= 0 -- the maps then stay the zero images they were allocated as (mgm.cc:360-365)
@@ -62,6 +64,10 @@ struct JobPlan {
     // MGM_RIGHT_FROM_LEFT=1 (this program's own mode), with TESTLRRL != 0 only: the right map of the left-right
     // test comes out of the left run's aggregated volume (mgm_wta_right_dev) instead of a second run
     bool rfl = false;
+    // TSGM_DEBUG != 0 (the reference's, mgm.cc:27): its debug lines on stdout, the three energies of every iteration among them
+    // (DESIGN.md 7i).  Off in the modes the reference does not have -- -S > 1, MGM_SUBPIX, MGM_RIGHT_FROM_LEFT=1 -- and on several
+    // devices (looked at once they are up): there is no reference stdout to equal there, and the variable stays ignored as it always was
+    bool debug = false;
     bool uq = false;          // -c FILE / MGM_UNIQUENESS=r: the runner-up search of a run right behind its aggregation
     bool batch_lr = true;     // MGM_BATCH_LR: both runs of a pair through one launch of the pass kernel
     int ms_slack = 3, ms_radius = 2;  // MGM_MS_SLACK, MGM_MS_RADIUS (-S: the window around the coarser level's disparities)
@@ -76,19 +82,21 @@ struct JobPlan {
 using EnvLookup = std::function<const char *(const char *)>;
 
 // ---- which modes exclude which: THE table ---------------------------------------------------------------------------------
-enum Blocker { B_RANGED, B_SCALES, B_ITER, B_REFINE, B_RFL, B_DEVICES, N_BLOCKERS };  // (in the order they are looked at)
+enum Blocker { B_RANGED, B_SCALES, B_ITER, B_REFINE, B_RFL, B_DEVICES, B_SUBPIX, N_BLOCKERS };  // (in the order they are looked at)
 static const char *const BLOCKER_NAME[N_BLOCKERS] = {
-    "range images (-m/-M)", "-S > 1", "TSGM_ITER != 1", "a refinement other than none or vfit", "MGM_RIGHT_FROM_LEFT=1", "several MGM_DEVICES"};
-enum Mode { M_RFL, M_UQ, M_SUBPIX, M_CONSENSUS, N_MODES };  // (as well)
+    "range images (-m/-M)", "-S > 1", "TSGM_ITER != 1", "a refinement other than none or vfit", "MGM_RIGHT_FROM_LEFT=1", "several MGM_DEVICES",
+    "MGM_SUBPIX"};
+enum Mode { M_RFL, M_UQ, M_SUBPIX, M_CONSENSUS, M_ENERGY, N_MODES };  // (as well)
 static const struct {
     const char *name;
     bool blocked_by[N_BLOCKERS];
 } EXCLUSIONS[N_MODES] = {
-    //                        -m/-M  -S>1   ITER   refine rfl    devices
-    {"MGM_RIGHT_FROM_LEFT=1", {true, true, true, true, false, true}},
-    {"-c / MGM_UNIQUENESS", {true, true, true, false, false, true}},
-    {"MGM_SUBPIX", {true, true, true, false, true, true}},
-    {"-C / MGM_CONSENSUS", {false, false, false, false, false, true}},
+    //                        -m/-M  -S>1   ITER   refine rfl    devices subpix
+    {"MGM_RIGHT_FROM_LEFT=1", {true, true, true, true, false, true, false}},
+    {"-c / MGM_UNIQUENESS", {true, true, true, false, false, true, false}},
+    {"MGM_SUBPIX", {true, true, true, false, true, true, false}},
+    {"-C / MGM_CONSENSUS", {false, false, false, false, false, true, false}},
+    {"MGM_ENERGY", {false, true, false, false, true, true, true}},
 };
 
 // "mgm: <mode> does not combine with <blocker>\n" for the first mode that is on and its first blocker that holds; else empty
@@ -233,6 +241,11 @@ inline JobPlan plan_job(const std::vector<std::string> &tokens, const EnvLookup 
         return end(1, nullptr, "mgm: MGM_CONSENSUS_TOL must be a finite number >= 0 (labels)\n");
     p.consensus = (int)cs;
     p.consensus_tol = (float)ct;
+    double en;
+    if (!env_strict(env, "MGM_ENERGY", 0, &en) || !(en == 0 || en == 4 || en == 8)) return end(1, nullptr, "mgm: MGM_ENERGY must be 4 or 8 (neighbours; 0: off)\n");
+    p.energy = (int)en;
+    if (const char *em = env("MGM_ENERGY_MAP")) p.energy_map = em;
+    if (!p.energy_map.empty() && p.energy == 0) return end(1, nullptr, "mgm: MGM_ENERGY_MAP needs MGM_ENERGY=4 or 8\n");
     if (!env_strict(env, "MGM_SPECKLE", 0, &n) || !whole(n)) return end(1, nullptr, "mgm: MGM_SPECKLE must be an integer >= 0 (pixels)\n");
     if (!env_strict(env, "MGM_SPECKLE_DIFF", 1, &df) || !(df >= 0)) return end(1, nullptr, "mgm: MGM_SPECKLE_DIFF must be a number >= 0\n");
     p.speckle = (int)n;
@@ -285,6 +298,7 @@ inline JobPlan plan_job(const std::vector<std::string> &tokens, const EnvLookup 
     p.ranged = !p.min_file.empty();
     p.rfl = env_param(env, "MGM_RIGHT_FROM_LEFT", 0) != 0 && p.both;
     p.uq = p.uniq != 0 || !p.conf_file.empty();
+    p.debug = env_param(env, "TSGM_DEBUG", 0) != 0 && p.nscales == 1 && o.subpix == 1 && !p.rfl;
     p.batch_lr = env_param(env, "MGM_BATCH_LR", 1) != 0;
     p.ms_slack = (int)env_param(env, "MGM_MS_SLACK", 3);
     p.ms_radius = (int)env_param(env, "MGM_MS_RADIUS", 2);
@@ -304,9 +318,9 @@ inline JobPlan plan_job(const std::vector<std::string> &tokens, const EnvLookup 
         }
     }
 
-    const bool mode[N_MODES] = {p.rfl, p.uq, o.subpix > 1, p.consensus != 0 || !p.votes_file.empty()};
+    const bool mode[N_MODES] = {p.rfl, p.uq, o.subpix > 1, p.consensus != 0 || !p.votes_file.empty(), p.energy != 0};
     const bool blocker[N_BLOCKERS] = {p.ranged, p.nscales > 1, p.iterations != 1, o.refine == "parabola" || o.refine == "cubic" || o.refine == "parabolaOCV",
-                                      p.rfl, p.devices_comma};
+                                      p.rfl, p.devices_comma, o.subpix > 1};
     p.err_text = first_exclusion(mode, blocker);
     // MGM_FILL_HOLES_OCC: the classification reads the right map that entered the left-right test
     if (p.err_text.empty() && !p.fill_occ.empty() && !p.both)
@@ -327,7 +341,7 @@ struct Refusal {
 };
 inline Refusal refuse_on_session(const JobPlan &p, bool multi_up, int u_ny, int v_ny)
 {
-    const bool mode[N_MODES] = {p.rfl, p.uq, p.o.subpix > 1, p.consensus != 0 || !p.votes_file.empty()};
+    const bool mode[N_MODES] = {p.rfl, p.uq, p.o.subpix > 1, p.consensus != 0 || !p.votes_file.empty(), p.energy != 0};
     bool blocker[N_BLOCKERS] = {};
     blocker[B_DEVICES] = multi_up;
     Refusal r;

@@ -8,9 +8,11 @@
 // computed on the CPU.  Image files (src/imgio.h): PNG, TIFF, PGM/PPM, PFM and .npy in -- what the
 // reference's iio decodes them to -- and float TIFF, PFM or .npy out.
 //
-// This program's own modes beside the reference's options (each documented in README.md and DESIGN.md 7a-7h): -S, -c, -C FILE /
+// This program's own modes beside the reference's options (each documented in README.md and DESIGN.md 7a-7i): -S, -c, -C FILE /
 // MGM_CONSENSUS=k / MGM_CONSENSUS_TOL=1 (the consensus votes, 7h: how many passes vote for a run's map; `--help` does not name these
-// three yet), MGM_RIGHT_FROM_LEFT, MGM_UNIQUENESS, MGM_SPECKLE, MGM_FILL_HOLES*, MGM_SUBPIX.
+// three yet), MGM_RIGHT_FROM_LEFT, MGM_UNIQUENESS, MGM_SPECKLE, MGM_FILL_HOLES*, MGM_SUBPIX, and MGM_ENERGY=4|8 / MGM_ENERGY_MAP=FILE
+// (7i: the model energy of every run and iteration on stderr; not in `--help` either).  TSGM_DEBUG=1 is the reference's own: its
+// debug lines on stdout, the three energies of every iteration among them (7i).
 //
 // A command line is a JOB with three stages: DECODE (host: the input files -> planar float images), DEVICE (this thread:
 // uploads, every kernel of the path, downloads; the job's stdout is written here, in order) and ENCODE (host: the output
@@ -271,14 +273,54 @@ static void aggregate_run_multi(mgm_multi *m, const HostImg &u, const HostImg &v
     }
 }
 
-// what mgm() and print_solution_energy put on stdout for one run (mgm_core.cc:420-423, 491; mgm_print_energy.h:109-111)
-static void report_run(const Opts &o, const Run &r)
+// what mgm() and print_solution_energy put on stdout for one run (mgm_core.cc:420-423, 491; mgm_print_energy.h:100-112):
+// `energy` is the rest of the digits' line under TSGM_DEBUG, else the line just ends
+static void report_run(const Opts &o, const Run &r, const std::string &energy = "")
 {
     if (r.weighted_msg) printf(" USING IMAGE DEPENDENT WEIGHTS\n");
     for (int p = 0; p < o.NDIR; p++) printf("%d", p);
-    printf("\n");
+    printf("%s", energy.empty() ? "\n" : energy.c_str());
     fflush(stdout);
 }
+
+// the reference's tables of names (mgm_costvolume.h:170-207, mgm_refine.h:15-35): an unknown name is the first entry
+static int name_index(const std::string &n, std::initializer_list<const char *> names)
+{
+    int r = 0, i = 0;
+    for (const char *s : names) {
+        if (n == s) r = i;
+        i++;
+    }
+    return r;
+}
+static const std::initializer_list<const char *> REFINEMENTS = {"none", "vfit", "parabola", "cubic", "parabolaOCV"};
+
+// TSGM_DEBUG: what allocate_and_fill_sgm_costvolume says about one volume build (mgm_costvolume.h:357-383)
+static void debug_costvolume_lines(const Opts &o)
+{
+    static const char *const dist[] = {"ad", "sd", "census", "ncc", "btad", "btsd"}, *const pre[] = {"none", "census", "sobelx", "gblur"};
+    int di = name_index(o.distance, {"ad", "sd", "census", "ncc", "btad", "btsd"}), pi = name_index(o.prefilter, {"none", "census", "sobelx", "gblur"});
+    if (di == 2 || pi == 1) {
+        printf("costvolume: changing both distance and prefilter to CENSUS\n");
+        di = 2, pi = 1;
+    }
+    printf("costvolume: selecting distance  %s\n", dist[di]);
+    printf("costvolume: selecting prefilter %s\n", pre[pi]);
+    printf("costvolume: truncate distances at %f\n", o.truncDist);
+    if (pi == 1) printf("costvolume: applying census with window of size %d\n", o.census_win / 2 * 2 + 1);
+    if (pi == 2) printf("costvolume: applying sobel filter\n");
+    if (pi == 3) printf("costvolume: applying gblur(s=1) filter\n");
+    fflush(stdout);
+}
+
+// TSGM_DEBUG and MGM_ENERGY: the energy of the UNREFINED map of every iteration of a run
+struct Probe {
+    bool debug = false;       // TSGM_DEBUG: the reference's three figures on stdout, behind the digits of the passes
+    int conn = 0;             // MGM_ENERGY: the model energy over 4 or 8 neighbours on stderr (0: off)
+    mgm_img **map = nullptr;  // MGM_ENERGY_MAP: where the model energy's map of this run goes (nullptr: nowhere)
+    char run = 'L';
+    bool on() const { return debug || conn != 0; }
+};
 
 static HostImg download(mgm_ctx *ctx, const mgm_img *im, int nx, int ny, int nch)
 {
@@ -363,22 +405,68 @@ static void fill_holes_classified_map(mgm_ctx *ctx, mgm_img *d, const mgm_img *o
 // iterations 2..TSGM_ITER of main()'s loop (mgm.cc:377-388): the ranges narrow around the previous solution
 // (update_dmin_dmax), the volume -- and with it every scan-line pass -- stays the same, so only the winner search and
 // the refinement are redone, on the Lr volumes the context still holds
-static void iterate_run(mgm_ctx *ctx, const Opts &o, Run &r, int iterations, int dmin, int dmax, const HostImg *lo0 = nullptr,
+// ... and what the run says about every iteration, the first one included (report_run).  With a probe: the energies of the
+// iteration's UNREFINED map (mgm()'s own outoff, mgm.cc:381-383), against the volume built before the loop -- the run's map itself
+// when there is no refinement, else the same winner search again without one, over the iteration's ranges.
+static std::string probe_iteration(mgm_ctx *ctx, const Opts &o, Run &r, const Probe &pb, int iter, const mgm_img *dlo, const mgm_img *dhi)
+{
+    if (!pb.on()) return "";
+    ImgHold unc{ctx}, un{ctx};
+    const mgm_img *d = r.dout;
+    int rc;
+    if (name_index(o.refine, REFINEMENTS) != 0) {
+        if ((rc = mgm_img_create(ctx, r.nx, r.ny, 1, &un.im)) || (rc = mgm_img_create(ctx, r.nx, r.ny, 1, &unc.im))) die(ctx, rc, "mgm_img_create");
+        if ((rc = mgm_wta_windowed_dev(ctx, r.C, o.NDIR, o.FIX, "none", dlo, dhi, un.im, unc.im))) die(ctx, rc, "mgm_wta_windowed");
+        d = un.im;
+    }
+    mgm_energy_params q{};
+    q.P1 = o.P1, q.P2 = o.P2;
+    mgm_energy_totals t{};
+    std::string line;
+    if (pb.debug) {  // mgm_print_energy.h:104-107
+        float e[3];
+        for (q.kind = 0; q.kind < 3; q.kind++) {
+            if ((rc = mgm_energy_dev(ctx, r.C, d, &q, nullptr, &t))) die(ctx, rc, "mgm_energy");
+            e[q.kind] = t.serial;
+        }
+        char buf[160];
+        snprintf(buf, sizeof buf, " ENERGY L1trunc: %.9e\tL1: %.9e\tL2: %.9e\n", e[0], e[1], e[2]);
+        line = buf;
+    }
+    if (pb.conn) {
+        q.kind = 3, q.connectivity = pb.conn, q.use_fh = o.FH != 0, q.w8 = r.dw;
+        if (pb.map) image_like(ctx, r.nx, r.ny, 1, pb.map);
+        if ((rc = mgm_energy_dev(ctx, r.C, d, &q, pb.map ? *pb.map : nullptr, &t))) die(ctx, rc, "mgm_energy");
+        fprintf(stderr, "[mgm energy] run=%c iter=%d total=%.17g data=%.17g smooth=%.17g finite=%llu/%llu\n", pb.run, iter, t.total, t.data, t.smooth,
+                t.finite, t.pixels);
+    }
+    return line;
+}
+
+static void iterate_run(mgm_ctx *ctx, const Opts &o, Run &r, int iterations, int dmin, int dmax, const Probe &pb, const HostImg *lo0 = nullptr,
                         const HostImg *hi0 = nullptr)
 {
-    if (iterations < 2) return;
-    std::vector<float> lo((size_t)r.nx * r.ny, (float)dmin), hi((size_t)r.nx * r.ny, (float)dmax);
-    if (lo0) {
-        lo = lo0->data;
-        hi = hi0->data;
-    }
+    const int refining = name_index(o.refine, REFINEMENTS);
     ImgHold dhi{ctx}, dlo{ctx};
     int rc;
-    if ((rc = mgm_img_upload(ctx, lo.data(), r.nx, r.ny, 1, &dlo.im)) || (rc = mgm_img_upload(ctx, hi.data(), r.nx, r.ny, 1, &dhi.im))) die(ctx, rc, "upload");
-    for (int it = 1; it < iterations; it++) {
-        if ((rc = mgm_update_ranges_dev(ctx, r.dout, dlo.im, dhi.im, 3, 2))) die(ctx, rc, "mgm_update_ranges");
-        if ((rc = mgm_wta_windowed_dev(ctx, r.C, o.NDIR, o.FIX, o.refine.c_str(), dlo.im, dhi.im, r.dout, r.dcost))) die(ctx, rc, "mgm_wta_windowed");
-        report_run(o, r);
+    if (iterations >= 2 || (pb.on() && refining)) {  // the ranges as device images: of the first iteration, then narrowed in place
+        std::vector<float> lo((size_t)r.nx * r.ny, (float)dmin), hi((size_t)r.nx * r.ny, (float)dmax);
+        if (lo0) {
+            lo = lo0->data;
+            hi = hi0->data;
+        }
+        if ((rc = mgm_img_upload(ctx, lo.data(), r.nx, r.ny, 1, &dlo.im)) || (rc = mgm_img_upload(ctx, hi.data(), r.nx, r.ny, 1, &dhi.im))) die(ctx, rc, "upload");
+    }
+    for (int it = 0; it < iterations; it++) {
+        if (it > 0) {
+            if ((rc = mgm_update_ranges_dev(ctx, r.dout, dlo.im, dhi.im, 3, 2))) die(ctx, rc, "mgm_update_ranges");
+            if ((rc = mgm_wta_windowed_dev(ctx, r.C, o.NDIR, o.FIX, o.refine.c_str(), dlo.im, dhi.im, r.dout, r.dcost))) die(ctx, rc, "mgm_wta_windowed");
+        }
+        report_run(o, r, probe_iteration(ctx, o, r, pb, it, dlo.im, dhi.im));
+        if (pb.debug && refining) {  // mgm_refine.h:47-49
+            printf("refinement: using %s\n", REFINEMENTS.begin()[refining]);
+            fflush(stdout);
+        }
     }
 }
 
@@ -401,7 +489,7 @@ struct Job {
     HostImg u, v, rlo, rhi;
     std::exception_ptr decode_err;
     // results of the device stage
-    HostImg outoff, outcost, syn, nolr, conf, votes;
+    HostImg outoff, outcost, syn, nolr, conf, votes, energy;
     int rc = 0;  // the job's exit code
 };
 
@@ -448,6 +536,7 @@ static void encode_job(Job &j)
         if (!p.nolr_file.empty()) imgio::write(p.nolr_file, j.nolr);
         if (!p.conf_file.empty()) imgio::write(p.conf_file, j.conf);
         if (!p.votes_file.empty()) imgio::write(p.votes_file, j.votes);
+        if (!p.energy_map.empty() && !j.energy.data.empty()) imgio::write(p.energy_map, j.energy);  // (no iteration: no map)
         imgio::write(p.f_out, j.outoff);
         if (!p.f_cost.empty()) imgio::write(p.f_cost, j.outcost);
         if (!p.f_back.empty()) imgio::write(p.f_back, j.syn);
@@ -639,6 +728,12 @@ static int device_job(Session &S, Job &j, const std::function<void()> &decoded, 
         ImgHold dconf{ctx};  // -c: the confidence map, until it is downloaded
         ImgHold dvotes{ctx};  // -C: the votes map, until it is downloaded
         const bool cs = p.consensus != 0 || !p.votes_file.empty();
+        ImgHold denergy{ctx};  // MGM_ENERGY_MAP: the left run's model-energy map, until it is downloaded
+        Probe probeL, probeR;  // TSGM_DEBUG (ignored on several devices, as ever) / MGM_ENERGY
+        probeL.debug = probeR.debug = p.debug && !multi;
+        probeL.conn = probeR.conn = p.energy;
+        probeL.map = p.energy_map.empty() ? nullptr : &denergy.im;
+        probeR.run = 'R';
         const int ITER = p.iterations;
         const bool both = p.both, rfl = p.rfl;
         if (p.nscales > 1) {
@@ -679,11 +774,11 @@ static int device_job(Session &S, Job &j, const std::function<void()> &decoded, 
             // (UNSUPPORTED: one image weighted, the other not -- the two runs take different update functions)
         }
         sw.mark("upload+enqueue");
+        if (probeL.debug) debug_costvolume_lines(o);  // (of the left->right volume: built above, said here, where the reference builds it)
         if (ITER > 0) {
             if (multi) aggregate_run_multi(multi, u, v, o.dmin, o.dmax, o, L);
             else if (!together) aggregate_run(ctx, o, L);
-            report_run(o, L);
-            iterate_run(ctx, o, L, ITER, o.dmin, o.dmax, plo, phi);
+            iterate_run(ctx, o, L, ITER, o.dmin, o.dmax, probeL, plo, phi);
             if (cs) consensus_run(ctx, o, L, p.consensus_tol, p.consensus, p.votes_file.empty() ? nullptr : &dvotes.im);
             rescale_run(ctx, o, L);
             if (p.uq) uniqueness_run(ctx, o, L, (float)p.uniq, p.uniq_radius, p.conf_file.empty() ? nullptr : &dconf.im);
@@ -702,13 +797,13 @@ static int device_job(Session &S, Job &j, const std::function<void()> &decoded, 
             if (p.median != 0) median_run(ctx, R, (int)p.median);
         } else if (both) {
             if (!r_ready) prepare_R();
+            if (probeR.debug) debug_costvolume_lines(o);
             if (ITER == 0) {
                 zero_run(R);
             } else {
                 if (multi) aggregate_run_multi(multi, v, u, -o.dmax, -o.dmin, o, R);
                 else if (!together) aggregate_run(ctx, o, R);
-                report_run(o, R);
-                iterate_run(ctx, o, R, ITER, -o.dmax, -o.dmin);
+                iterate_run(ctx, o, R, ITER, -o.dmax, -o.dmin, probeR);
                 if (p.consensus != 0) consensus_run(ctx, o, R, p.consensus_tol, p.consensus, nullptr);
                 rescale_run(ctx, o, R);
                 if (p.uniq != 0) uniqueness_run(ctx, o, R, (float)p.uniq, p.uniq_radius, nullptr);
@@ -735,6 +830,7 @@ static int device_job(Session &S, Job &j, const std::function<void()> &decoded, 
             }
             j.votes = download(ctx, dvotes.im, u.nx, u.ny, 1);
         }
+        if (denergy.im) j.energy = download(ctx, denergy.im, u.nx, u.ny, 1);
         sw.mark("download(rest)");
         if (p.kernels && !multi) report_kernels(ctx);
     } catch (const std::exception &e) {  // (a DeviceError, an unreadable input)
@@ -856,7 +952,7 @@ static int run_batch(const char *file)
         for (size_t m = 0; m < k; m++) {
             const JobPlan &e = jobs[m]->p;
             for (const std::string *in : {&j.f_u, &j.f_v, &j.min_file, &j.max_file})
-                for (const std::string *out : {&e.f_out, &e.f_cost, &e.f_back, &e.nolr_file, &e.conf_file, &e.votes_file})
+                for (const std::string *out : {&e.f_out, &e.f_cost, &e.f_back, &e.nolr_file, &e.conf_file, &e.votes_file, &e.energy_map})
                     if (!in->empty() && *in == *out) needs[k] = m + 1;
         }
     }
@@ -889,7 +985,7 @@ static int run_batch(const char *file)
                 bad = 1;
             }
             // the job is done: its images go
-            j.u = j.v = j.rlo = j.rhi = j.outoff = j.outcost = j.syn = j.nolr = j.conf = j.votes = HostImg();
+            j.u = j.v = j.rlo = j.rhi = j.outoff = j.outcost = j.syn = j.nolr = j.conf = j.votes = j.energy = HostImg();
             {
                 std::lock_guard<std::mutex> lk(mu);
                 written = k + 1;
